@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the matrix-factorization training hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets the workload up, runs W untimed and K timed steps, writes the outputs of the last step when --dump-outputs DIR
+is given (dump_outputs) and prints the JSON line.  Everything else the benchmark measures - the CPU baseline, predict / ranking,
+recall parity, the public-API fits, BASELINE configs 1-3, the strong-scaling projection, the two HBM legs and the extras file -
+runs only with --full.
 
 Both forms work for N > 1: started WITHOUT a launcher (no WORLD_SIZE in the environment) `--gpus N` starts its own ranks -
 `python -m torch.distributed.run --standalone --nproc-per-node N bench.py ...` as a CHILD process, before this process has made
@@ -16,7 +21,7 @@ configuration: 1M users x 100K items, r = 128, WMRB with S = 1024 static negativ
 the ranks, V is replicated and its gradient is exchanged by RCCL reduce-scatter / all-gather
 (teamoflow_amd/dist.py).  Default for N > 1 is STRONG scaling: the ONE 1M-user problem (BASELINE config 4 as written) cut
 into contiguous cost-balanced user blocks; `--scaling weak` gives every rank its own 1M users and says so in the line.
-The default N = 1 run also times one rank's shard of the 8-way split on this one GPU (`strong_scaling_projection`: a
+With --full an N = 1 run also times one rank's shard of the 8-way split on this one GPU (`strong_scaling_projection`: a
 PROJECTION of the 1 -> 8 curve from measured shard time + modelled wire time, not a measured N > 1 run).
 Rank 0 prints ONE JSON line; DESIGN.md §4 defines every field of its `roofline` object.
 """
@@ -576,6 +581,34 @@ def write_extras(out, path=None):
         return None
 
 
+DUMP_BYTES = 48 << 20   # factor rows --dump-outputs writes at most, both tables together (row ids and loss add < 1 MB)
+
+
+def sampled_rows(table, rows, r, seed):
+    """Rows of table[:rows, :r] at a fixed, seeded, sorted sample (all rows when they fit half of DUMP_BYTES) as float32 [k, r],
+    and their ids as float64 [k].  The table is copied to the host whole and sampled there: no torch row gather on a large
+    device tensor."""
+    k = min(rows, max(1, DUMP_BYTES // 2 // (r * 4)))
+    ids = np.arange(rows) if k == rows else np.sort(np.random.default_rng(seed).choice(rows, k, replace=False))
+    host = table.cpu()
+    return host[torch.from_numpy(ids)][:, :r].float().numpy(), ids.astype(np.float64)
+
+
+def dump_outputs(path, U, m, V, n, r, loss):
+    """--dump-outputs DIR: what the timed path computed in its last step, as DIR/<name>.npy - the updated user and item factor
+    tables (a seeded sample of rows of each: user_factors / item_factors, float32, with their row ids user_rows / item_rows)
+    and the loss that step returned (loss, float64 [1]).  The inputs are seeded, so two builds run with the same arguments
+    can be compared array for array."""
+    os.makedirs(path, exist_ok=True)
+    Ux, Ui = sampled_rows(U, m, r, 1)
+    Vx, Vi = sampled_rows(V, n, r, 2)
+    arrays = dict(user_factors=Ux, user_rows=Ui, item_factors=Vx, item_rows=Vi,
+                  loss=np.asarray(loss, dtype=np.float64).reshape(1))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    log(f'[bench] outputs of the last step written to {path}: ' + ', '.join(f'{k} {list(a.shape)}' for k, a in arrays.items()))
+
+
 class Workload:
     """One rank's problem, resident in HBM: interactions, negative table, plans, factor tables."""
 
@@ -866,6 +899,9 @@ def sharded_run(args, rank, world, dev, rehearse, red_dev, json_out):
         losses[args.warmup + i] = ep.step()
     fence()
     elapsed, warm = time.perf_counter() - t0, t0 - tw
+    if args.dump_outputs and rank == 0:   # this rank's users and its owned rows of the item table
+        V_own = backend.V_own()
+        dump_outputs(args.dump_outputs, backend.U, m, V_own, V_own.shape[0], r, losses[args.warmup + args.steps - 1].cpu().numpy())
     nnz_total = float(val.numel())
     if multi:
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -899,7 +935,8 @@ def sharded_run(args, rank, world, dev, rehearse, red_dev, json_out):
                                 note='per window: all-gather of the rows (async, prefetched one window ahead), reduce-scatter of the fp32 '
                                      'gradient (async); overlapped with the window\'s kernels'),
                loss_first_last=[lh[0], lh[-1]])
-    out['extras'] = write_extras(out)
+    if args.full:
+        out['extras'] = write_extras(out)
     print(compact_line(out), file=json_out, flush=True)
 
 
@@ -965,13 +1002,20 @@ def main():
     ap.add_argument('--item-dist', choices=['zipf', 'uniform'], default='zipf')
     ap.add_argument('--lr', type=float, default=0.1)
     ap.add_argument('--dtype', choices=['f32', 'bf16'], default='f32', help='factor storage (arithmetic is fp32 either way)')
-    ap.add_argument('--small-configs', action='store_true', help='time BASELINE configs 1-3 in full (GPU fit vs dense CPU restatement)')
-    ap.add_argument('--no-extras', action='store_true', help='skip cpu baseline / predict / API / HBM legs / small configs')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the timed steps: cpu baseline, predict, recall parity, API fits, small configs, strong-scaling projection, '
+                         'HBM legs and the extras file (a plain run times the steps and prints the line, nothing else)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last step computed (sampled factor rows, loss) as DIR/<name>.npy')
+    ap.add_argument('--small-configs', action='store_true', help='with --full: time BASELINE configs 1-3 in full (GPU fit vs dense CPU restatement)')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip cpu baseline / predict / API / HBM legs / small configs')
     ap.add_argument('--shard-items', type=int, default=0, metavar='Q',
                     help='item-row-sharded V (BASELINE config 4 as written): Q windows per rank, per-window all-gather / reduce-scatter '
                          '(dist.ItemShardedEpoch) instead of the replicated table; one JSON line with an epoch-level roofline entry')
     ap.add_argument('--no-legs', action='store_true', help='skip the two HBM-streaming side legs (C4 MSE, config-5 shard)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     rc = spawn_ranks(args, sys.argv[1:])
     if rc is not None:
         raise SystemExit(rc)
@@ -1025,6 +1069,9 @@ def main():
         backend = tdist.HipBackend(wl.st, args.loss, wl.c, wl.adam, prof=None)
         dp = tdist.DataParallelEpoch(backend, wl.plan.n_pos if args.loss == 'wmrb' else wl.nnz)
     elapsed, warm_elapsed, prof, loss_buf = run_steps(wl, args.steps, args.warmup, dp, backend)
+    if args.dump_outputs and rank == 0:   # the tables after the last step (st.swap() made them current) and its loss
+        last = args.warmup + args.steps - 1
+        dump_outputs(args.dump_outputs, wl.st.U, wl.m, wl.st.V, wl.n, wl.r, loss_buf[last:last + 1].cpu().numpy())
     comm = None
     if dp_mode:
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -1090,7 +1137,7 @@ def main():
     if comm is not None:
         out['collectives'] = comm
 
-    if rank == 0 and not args.no_extras and world == 1:
+    if rank == 0 and args.full and not args.no_extras and world == 1:
         denom = wl.plan.n_pos if args.loss == 'wmrb' else wl.nnz
         losses = loss_buf[:args.steps + args.warmup].cpu().numpy() / denom
         out['loss_first_last'] = [float(losses[0]), float(losses[-1])]
@@ -1164,7 +1211,7 @@ def main():
             out['item_sharded_fit'].update(windows=q, over_resident=out['item_sharded_fit']['ms_per_epoch'] / out['api_fit']['ms_per_epoch'],
                                            note='model.shard_items = 4 on ONE rank: the catalog walked in 4 windows (twice for WMRB), per-window '
                                                 'launches of the same kernels, user-gradient partials summed in window order; no collective runs')
-    if rank == 0 and world == 1 and (args.small_configs or not args.no_extras):
+    if rank == 0 and world == 1 and args.full and (args.small_configs or not args.no_extras):
         # the reference's own (dense, full-batch) formulation on the host cores next to the engine, BASELINE configs 1-3
         out['reference_formulation_cpu'] = small_configs(dev, quick=not args.small_configs)
         c2 = out['reference_formulation_cpu'].get('C2', {})
@@ -1172,7 +1219,7 @@ def main():
             out['recall_at_10']['end_to_end_C2'] = dict(engine=c2['recall_at_10'], oracle=c2['recall_at_10_cpu_restatement'],
                                                         abs_diff=c2['recall_at_10_abs_diff'],
                                                         case='C2 (943 x 1682, r=32, MSE): 100 epochs trained by each side from the same start')
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_projection and default_workload:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.no_projection and default_workload:
         try:
             wl.st = None
         except NameError:
@@ -1182,7 +1229,7 @@ def main():
         out['strong_scaling_projection'] = strong_scaling_projection(args, dev, ms_per_step, kms)
         log(f"[bench] projected 1 -> 8 scaling {out['strong_scaling_projection']['projected_scaling']:.2f}x "
             f"(slowest shard {out['strong_scaling_projection']['slowest_shard_ms']:.2f} ms, full problem {ms_per_step:.2f} ms)")
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_legs and default_workload:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.no_legs and default_workload:
         # workloads whose factor rows really come from HBM (the C4 tables sit in L2 / Infinity Cache): DESIGN.md §4
         del wl
         torch.cuda.empty_cache()
@@ -1191,7 +1238,8 @@ def main():
             c5_shard_bf16=hbm_leg(args, dev, 'config-5 shard (1/8 of 10M x 1M)', 1_250_000, 1_000_000, 125_000_000, 256, 1024, 'wmrb',
                                   'bf16', 5, 2, 'c5_shard_bf16'))
     if rank == 0:
-        out['extras'] = write_extras(out)
+        if args.full:
+            out['extras'] = write_extras(out)
         log('[bench] roofline kernels: ' + json.dumps(_short({e['kernel']: dict(ms=e['ms'], bound=e['bound'], frac=e['frac'],
                                                                                traffic_over_compulsory=e.get('traffic_over_compulsory'),
                                                                                useful_hbm_frac=e.get('useful_hbm_frac'))

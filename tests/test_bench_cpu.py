@@ -240,3 +240,38 @@ def test_cpu_baseline_sample_is_selected_column_by_column(bench, monkeypatch):
     monkeypatch.setattr(bench._engine, 'take_interactions', lambda i, v, keep, **k: (i[-int(keep.sum()):], v[-int(keep.sum()):]))
     with pytest.raises(AssertionError, match='row-major prefix'):
         bench.baseline_sample(idx, val, 100, 50)
+
+
+def test_dump_outputs_writes_a_fixed_float_sample_within_the_cap(bench, tmp_path):
+    """--dump-outputs: float32 / float64 arrays only, at most 64 MB in all even for tables far beyond that, and the same rows
+    whenever the same table is dumped (a seeded sample, so two builds can be compared array for array)."""
+    m, n, r, ld = 1_000_000, 100_000, 128, 128
+    U = torch.arange(m, dtype=torch.float32).repeat_interleave(ld).reshape(m, ld)
+    V = torch.randn(n + 64, ld, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)   # padded rows and bf16 storage
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), U, m, V, n, r, np.array([123.5]))
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['item_factors.npy', 'item_rows.npy', 'loss.npy', 'user_factors.npy', 'user_rows.npy']
+    got = {f[:-4]: np.load(tmp_path / 'a' / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64 << 20
+    rows = got['user_rows'].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and rows[-1] < m and got['user_factors'].shape == (len(rows), r)
+    assert np.array_equal(got['user_factors'][:, 0], rows.astype(np.float32))            # the rows named are the rows written
+    items = got['item_rows'].astype(np.int64)
+    assert items[-1] < n and np.array_equal(got['item_factors'], V[torch.from_numpy(items)][:, :r].float().numpy())
+    assert got['loss'].tolist() == [123.5]
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / 'b' / f), got[f[:-4]]), f
+    # a small table is written whole
+    bench.dump_outputs(str(tmp_path / 'c'), U[:100], 100, V, 50, r, np.array([1.0]))
+    assert np.array_equal(np.load(tmp_path / 'c' / 'user_rows.npy'), np.arange(100.0))
+
+
+def test_plain_run_options(bench):
+    """`--full` (off by default) and `--dump-outputs DIR` exist, and --steps below 1 is refused before any GPU work."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and '--full' in r.stdout and '--dump-outputs' in r.stdout, r.stderr[-2000:]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and '--steps must be at least 1' in r.stderr
