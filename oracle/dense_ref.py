@@ -66,6 +66,30 @@ def tf_top_k(x, k):
     return vals[..., :k], idx[..., :k]
 
 
+def tf_top_k_chunked(U, V, k, chunk=1 << 20, clamp=False, excluded=None):
+    """tf.math.top_k(U V^T, k) in fp64 without the [m, n] matrix: the scores of `chunk` items at a time, a stable top-k per
+    chunk, the chunks' lists merged in item order by one more stable sort (equal values keep the lower item id first).  Plain
+    torch on whatever device U and V are on, no project code.  clamp: scores below 0 become 0 (tf.maximum(x, 0)).
+    excluded: (rows, cols) int64 tensors of pairs scored -inf.  -> (values fp64 [m, k], ids int64 [m, k])."""
+    U64 = U.to(torch.float64)
+    n = V.shape[0]
+    vs, ids = [], []
+    for c0 in range(0, n, chunk):
+        s = U64 @ V[c0:c0 + chunk].to(torch.float64).T
+        if clamp:
+            s.clamp_min_(0)
+        if excluded is not None:
+            rows, cols = excluded
+            sel = (cols >= c0) & (cols < c0 + s.shape[1])
+            s[rows[sel], cols[sel] - c0] = float('-inf')
+        v, p = torch.sort(s, dim=1, descending=True, stable=True)
+        vs.append(v[:, :k])
+        ids.append(p[:, :k] + c0)
+        del s, v, p
+    v, p = torch.sort(torch.cat(vs, 1), dim=1, descending=True, stable=True)
+    return v[:, :k], torch.gather(torch.cat(ids, 1), 1, p[:, :k])
+
+
 def adam_fresh_constants(lr, dtype=np.float32):
     """Scalars of a Keras Adam step at iteration 1, computed in ``dtype`` like TF does
     (matrix_factorization.py:176 builds a NEW optimizer every epoch => t = 1, m = v = 0)."""

@@ -61,6 +61,7 @@ constexpr int SMAXK = 40 /* bf16 planes (round 5: two 4-wave workgroups' lists f
 __host__ __device__ constexpr int split_cap(int waves, int k) { return waves == 4 ? (k <= 12 ? 16 : 8) : (k <= 16 ? 16 : 8); }   // never below 8: an overflowing tile is re-offered in groups of 8 columns
 // LDS ring slots: the two-plane chunks of the fp16 form are small enough for three of them beside two workgroups' lists
 __host__ __device__ constexpr int split_ring(int waves, bool half2) { return (waves == 4 && !half2) ? 2 : 3; }
+constexpr size_t kSplitMaxLds = 160 * 1024;   // LDS of a CU (gfx950)
 constexpr int kSplitRowsPad = 128;   // the item planes are padded to a multiple of this many rows (a multiple of every tile width)
 
 // max of two accumulator values without the canonicalising v_max(x, x) hipcc puts in front of fmaxf (NaNs do not matter here:
@@ -566,6 +567,10 @@ static int launch_predict_topk_split_w(const float* A, const uint16_t* Bp, int64
     constexpr int SBM = 32 * WAVES, SRING = split_ring(WAVES, HALF2), NP = HALF2 ? 2 : 3;
     const size_t lds = (size_t)SRING * NP * (32 * NJ) * (32 * KS) + 3 * sizeof(float) * SBM + 8 * (size_t)split_cap(WAVES, k) * SBM +
                        8 * (size_t)k * SBM + TMF_SPLIT_LDS_PAD;
+    if (lds > kSplitMaxLds) {   // never launched: more LDS than a CU has
+        set_error("predict_topk_split: %d-wave workgroup at k=%d needs %zu bytes of LDS (a CU has %zu)", WAVES, k, lds, kSplitMaxLds);
+        return TMF_E_UNSUPPORTED;
+    }
     static LdsGrant grant;  // per template instance
     if (int rc = grant_dynamic_lds(reinterpret_cast<const void*>(&k_predict_topk_split<NJ, KS, NCH, WAVES, HALF2, EXCL>), lds, grant)) return rc;
     const int64_t blocks = (m + SBM - 1) / SBM;
@@ -575,12 +580,15 @@ static int launch_predict_topk_split_w(const float* A, const uint16_t* Bp, int64
     return check_launch(HALF2 ? "tmf_predict_topk_half2_f32" : "tmf_predict_topk_split_f32");
 }
 
-static bool split_force8() {   // TMF_SPLIT_WAVES=8: the 8-wave instances for every k (A/B runs)
+// TMF_SPLIT_WAVES=8: the 8-wave instances (A/B runs) for every k whose lists fit beside their 3-slot ring: the bf16 ring is 72 KB,
+// and 256 users' lists of 8 bytes per entry take the rest of the CU's LDS past k = 34 (73728 + 3072 + 16384 + 2048 k bytes)
+constexpr int kSplitForce8MaxK = 34;
+static bool split_force8(int k) {
     static const bool forced = [] { const char* e = getenv("TMF_SPLIT_WAVES"); return e && atoi(e) == 8; }();
-    return forced;
+    return forced && k <= kSplitForce8MaxK;
 }
 static int split_waves(int k) {
-    if (split_force8() || k > 22) return 8;   // k <= 22: two workgroups' lists still fit beside their rings of 64-wide k-chunks (80 KB each)
+    if (split_force8(k) || k > 22) return 8;   // k <= 22: two workgroups' lists still fit beside their rings of 64-wide k-chunks (80 KB each)
     return 4;
 }
 
@@ -593,7 +601,7 @@ static int launch_predict_topk_split(int ldp, int k, const float* A, const uint1
     return w4 ? launch_predict_topk_split_w<NJ, KS, NCH, 4, HALF2, EXCL>(A, Bp, m, n, n_pad, K, lda, k, clamp, out_idx, out_val, item_scale, ex, s)  \
               : launch_predict_topk_split_w<NJ, KS, NCH, 8, HALF2, EXCL>(A, Bp, m, n, n_pad, K, lda, k, clamp, out_idx, out_val, item_scale, ex, s)
     if constexpr (HALF2) {   // 64 A registers at r = 128: 128-item tiles throughout, k-chunks of 32
-        if (!w4 && !split_force8()) {   // k > 22: 4-wave workgroups on 64-item tiles, like the bf16 planes below
+        if (!w4 && !split_force8(k)) {   // k > 22: 4-wave workgroups on 64-item tiles, like the bf16 planes below
             if (ldp == 32) return launch_predict_topk_split_w<2, 2, 1, 4, HALF2, EXCL>(A, Bp, m, n, n_pad, K, lda, k, clamp, out_idx, out_val, item_scale, ex, s);
             if (ldp == 64) return launch_predict_topk_split_w<2, 2, 2, 4, HALF2, EXCL>(A, Bp, m, n, n_pad, K, lda, k, clamp, out_idx, out_val, item_scale, ex, s);
             if (ldp == 128) return launch_predict_topk_split_w<2, 2, 4, 4, HALF2, EXCL>(A, Bp, m, n, n_pad, K, lda, k, clamp, out_idx, out_val, item_scale, ex, s);
@@ -612,7 +620,7 @@ static int launch_predict_topk_split(int ldp, int k, const float* A, const uint1
         // candidates holds the other seven at the chunk barrier.  262144 x 100000, 8-wave -> 4-wave instances, same box:
         //   r = 128: k = 23 144 -> 164 TF, 25: 136 -> 156, 28: 124 -> 148, 32: 108 -> 133;  r = 256: k = 25 145 -> 152, 32: 128 -> 140;  r = 96, k = 32: 82 -> 103
         // TMF_SPLIT_WAVES=8 brings the 8-wave instances back (A/B runs).
-        if (!w4 && !split_force8()) {
+        if (!w4 && !split_force8(k)) {
             if (ldp == 32) return launch_predict_topk_split_w<2, 2, 1, 4, HALF2, EXCL>(A, Bp, m, n, n_pad, K, lda, k, clamp, out_idx, out_val, item_scale, ex, s);
             if (ldp == 64) return launch_predict_topk_split_w<2, 2, 2, 4, HALF2, EXCL>(A, Bp, m, n, n_pad, K, lda, k, clamp, out_idx, out_val, item_scale, ex, s);
             if (ldp == 128) return launch_predict_topk_split_w<2, 2, 4, 4, HALF2, EXCL>(A, Bp, m, n, n_pad, K, lda, k, clamp, out_idx, out_val, item_scale, ex, s);

@@ -122,9 +122,9 @@ def test_half2_keeps_22_bits_per_value(ops):
 @pytest.mark.parametrize('arith', ['half2', 'split'])
 @pytest.mark.parametrize('r', [129, 200, 256])
 def test_wide_tables(ops, r, arith):
-    """Both plane forms reach width 256 (fp16: 128 A registers per lane; bf16 x 3 since round 5: 192, eight waves per workgroup at two
-    per SIMD): exact on integer factors, fp32-accurate on Gaussian ones, with clamping and both workgroup shapes (k = 10: 4 waves,
-    k = 30: 8 waves)."""
+    """Both plane forms reach width 256 (fp16: 128 A registers per lane; bf16 x 3 since round 5: 192): exact on integer factors,
+    fp32-accurate on Gaussian ones, with clamping, at k = 10 and k = 30 - both on 4-wave workgroups (k > 22 takes the narrower
+    k-chunks); the 8-wave instances (TMF_SPLIT_WAVES=8 only) are run by tests/test_gpu_split_8waves.py."""
     rng = np.random.default_rng(r)
     m, n = 300, 33001
     for k, clamp in ((10, False), (30, True)):

@@ -346,3 +346,18 @@ def test_scores6_entry_streams_on_the_host():
         for e in pads:                                                             # a padding entry repeats a valid id of the chunk
             assert (ids[e] & 0xffffff) // width == sl
     assert len(seen_neg) == m * S and len(seen_pos) == plan.nnz
+
+
+def test_32bit_offset_forms_switch_at_4_gb():
+    """tmf_wmrb_scores6 / scores5 walk V with 32-bit byte offsets: they exist for tables whose last row ends below byte 2^32 and
+    hand everything larger to tmf_wmrb_scores3's general form.  512-byte rows (fp32 r = 128, bf16 r = 256): 2^23 - 1 items take
+    them, 2^23 do not (tests/test_gpu_large_tables.py runs both sides of the edge)."""
+    from teamoflow_amd import _lib
+    lib = _lib.load_library()
+    for r, bf16 in ((128, 0), (256, 1)):
+        row_bytes = _lib.padded_ld(r, torch.bfloat16 if bf16 else torch.float32) * (2 if bf16 else 4)
+        assert row_bytes == 512
+        last = (1 << 32) // row_bytes - 1
+        assert last * row_bytes < (1 << 32) <= (last + 1) * row_bytes
+        for fn in (lib.tmf_wmrb_scores6_supported, lib.tmf_wmrb_scores5_supported):
+            assert fn(r, bf16, last) == 1 and fn(r, bf16, last + 1) == 0 and fn(r, bf16, 9_000_000) == 0, (fn, r)

@@ -42,6 +42,28 @@ def test_tf_maximum_subgradient_at_tie():
     assert x.grad.tolist() == [0.0, 1.0, 1.0]
 
 
+def test_chunked_top_k_equals_the_whole_row_sort():
+    """oracle.dense_ref.tf_top_k_chunked (the fp64 reference of the multi-GB ranking tests) against sparse_ref.topk_stable on the
+    whole score matrix: small integer factors (heavy ties, the same value in many chunks), chunk widths that leave a ragged last
+    chunk, chunks narrower than k, clamping and excluded pairs."""
+    rng = np.random.default_rng(11)
+    for m, n, r, k, chunk in ((7, 1000, 3, 10, 128), (33, 517, 2, 50, 64), (5, 300, 1, 20, 7), (9, 64, 4, 64, 10), (1, 999, 5, 1, 1000)):
+        U = rng.integers(-2, 3, (m, r)).astype(np.float32)
+        V = rng.integers(-1, 2, (n, r)).astype(np.float32)
+        sc = U.astype(np.float64) @ V.astype(np.float64).T
+        for clamp in (False, True):
+            want = S.topk_stable(np.maximum(sc, 0) if clamp else sc, k)
+            v, i = D.tf_top_k_chunked(torch.tensor(U), torch.tensor(V), k, chunk=chunk, clamp=clamp)
+            assert np.array_equal(i.numpy(), want), (m, n, chunk, clamp)
+            assert np.array_equal(v.numpy(), np.take_along_axis(np.maximum(sc, 0) if clamp else sc, want, 1))
+        rows = torch.tensor(rng.integers(0, m, 40))
+        cols = torch.tensor(rng.integers(0, n, 40))
+        sx = sc.copy()
+        sx[rows.numpy(), cols.numpy()] = -np.inf
+        v, i = D.tf_top_k_chunked(torch.tensor(U), torch.tensor(V), k, chunk=chunk, excluded=(rows, cols))
+        assert np.array_equal(i.numpy(), S.topk_stable(sx, k)), (m, n, chunk, 'excluded')
+
+
 def test_adam_fresh_is_near_sign():
     w = torch.zeros(4)
     g = torch.tensor([1.0, -3.0, 0.0, 1e-6])
