@@ -443,6 +443,52 @@ int tmf_topk_stable_exclude_f32(float* X, int64_t rows, int64_t cols, int64_t ld
                                 const tmf_exclusion* exclude, int32_t* out_idx, float* out_val, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* Full-catalog ranks of held-out (user, item) pairs (LightFM's predict_rank; auc_score and reciprocal_rank reduce them).
+ * rank(u, i) = the number of ELIGIBLE items j != i - not excluded; other positives count - that the order of the fused top-k
+ * (value desc, index asc) puts before i, so rank 0 is the top and, under the same arithmetic and exclusion, rank(u, i) < k holds
+ * exactly when i is in the top-k list of u.  Scores are the raw u.v (no clamp); an item whose score is NaN is never counted above
+ * anyone, and a positive whose own score is NaN ranks behind every non-NaN eligible item.
+ *
+ * The positives are addressed through VIRTUAL rows: a user with P positives is ceil(P / TMF_RANK_ROW_PAIRS) rows, each with at
+ * most TMF_RANK_ROW_PAIRS of them; pos_item[begin[v] .. begin[v] + count[v]) are the (distinct) items of row v, user[v] its user
+ * (rows of one user in any order; users without positives need no row).  Ranks are written to out_rank at the positives' own
+ * positions.  A pair that is also excluded is the caller's error (its rank is undefined). */
+#define TMF_RANK_ROW_PAIRS 16
+typedef struct tmf_rank_rows {
+    const int32_t* user;    /* [n_rows] */
+    const int64_t* begin;   /* [n_rows] */
+    const int32_t* count;   /* [n_rows], 1 .. TMF_RANK_ROW_PAIRS */
+    int64_t n_rows;
+} tmf_rank_rows;
+
+/* out[p] = <A[pair_user[p]], B[pair_item[p]]> computed exactly as the fused rank kernel's tile computes it: _f32 on the fp32 MFMA
+ * (as tmf_predict_topk_f32 / tmf_item_ranks_f32), _split on the three bf16 planes (as tmf_predict_topk_split_f32 /
+ * tmf_item_ranks_split).  r <= 256 (TMF_E_UNSUPPORTED above for _split); tables as the top-k calls. */
+int tmf_pair_scores_f32(const float* A, const float* B, int r, int64_t lda, int64_t ldb, const int32_t* pair_user,
+                        const int32_t* pair_item, int64_t n_pairs, float* out, void* stream);
+int tmf_pair_scores_split(const float* A, const float* B, int r, int64_t lda, int64_t ldb, const int32_t* pair_user,
+                          const int32_t* pair_item, int64_t n_pairs, float* out, void* stream);
+
+/* Fused GEMM + rank count over all n items, no [m, n] scores: pos_score = the pairs' scores from tmf_pair_scores_* of the SAME
+ * form, exclude = NULL or the pairs to leave out (rows = users, ids as tmf_exclusion).  _f32: the fp32 MFMA arithmetic of
+ * tmf_predict_topk_f32; _split: the three bf16 planes of tmf_predict_topk_split_f32, `workspace` holds the item planes
+ * (tmf_item_ranks_split_workspace_bytes; overwritten per call).  r <= 256 (the _supported queries), TMF_E_UNSUPPORTED otherwise. */
+int tmf_item_ranks_f32_supported(int r);
+int tmf_item_ranks_split_supported(int r);
+size_t tmf_item_ranks_split_workspace_bytes(int64_t n, int r);
+int tmf_item_ranks_f32(const float* A, const float* B, int64_t n, int r, int64_t lda, int64_t ldb, const tmf_rank_rows* rows,
+                       const int32_t* pos_item, const float* pos_score, const tmf_exclusion* exclude, int32_t* out_rank,
+                       void* stream);
+int tmf_item_ranks_split(const float* A, const float* B, int64_t n, int r, int64_t lda, int64_t ldb, const tmf_rank_rows* rows,
+                         const int32_t* pos_item, const float* pos_score, const tmf_exclusion* exclude, int32_t* out_rank,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* The non-fused count (r > 256, bf16 tables, any arithmetic whose scores tmf_predict_gemm_f32 gives): X [rows, cols] holds the scores
+ * of users [user_base, user_base + rows); `vrows` are the virtual rows of those users only.  With `exclude` (rows = global user ids)
+ * the excluded entries of X are OVERWRITTEN with NaN first.  A positive's score is read from X. */
+int tmf_rank_count_rows_f32(float* X, int64_t rows, int64_t cols, int64_t ldx, int64_t user_base, const tmf_rank_rows* vrows,
+                            const int32_t* pos_item, const tmf_exclusion* exclude, int32_t* out_rank, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,8 +47,13 @@ class Exclusion(ctypes.Structure):
     _fields_ = [('rowptr', ctypes.c_void_p), ('cols', ctypes.c_void_p), ('item_base', ctypes.c_int64)]
 
 
+class RankRows(ctypes.Structure):
+    _fields_ = [('user', ctypes.c_void_p), ('begin', ctypes.c_void_p), ('count', ctypes.c_void_p), ('n_rows', ctypes.c_int64)]
+
+
 _P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _EX = ctypes.POINTER(Exclusion)
+_RR = ctypes.POINTER(RankRows)
 _SEG = ctypes.POINTER(Segments)
 _SL = ctypes.POINTER(SliceLists)
 _I32, _SZ = ctypes.c_int32, ctypes.c_size_t
@@ -124,6 +129,14 @@ _BASE_SIGNATURES = {
     'tmf_predict_topk_split_exclude_f32': (_I, [_P, _P, _L, _L, _I, _L, _L, _I, _I, _EX, _P, _P, _P, _SZ, _P]),
     'tmf_predict_topk_half2_exclude_f32': (_I, [_P, _P, _L, _L, _I, _L, _L, _I, _I, _EX, _P, _P, _P, _SZ, _P]),
     'tmf_topk_stable_exclude_f32': (_I, [_P, _L, _L, _L, _I, _I, _EX, _P, _P, _P, _SZ, _P]),
+    'tmf_pair_scores_f32': (_I, [_P, _P, _I, _L, _L, _P, _P, _L, _P, _P]),
+    'tmf_pair_scores_split': (_I, [_P, _P, _I, _L, _L, _P, _P, _L, _P, _P]),
+    'tmf_item_ranks_f32_supported': (_I, [_I]),
+    'tmf_item_ranks_split_supported': (_I, [_I]),
+    'tmf_item_ranks_split_workspace_bytes': (_SZ, [_L, _I]),
+    'tmf_item_ranks_f32': (_I, [_P, _P, _L, _I, _L, _L, _RR, _P, _P, _EX, _P, _P]),
+    'tmf_item_ranks_split': (_I, [_P, _P, _L, _I, _L, _L, _RR, _P, _P, _EX, _P, _P, _SZ, _P]),
+    'tmf_rank_count_rows_f32': (_I, [_P, _L, _L, _L, _L, _RR, _P, _EX, _P, _P]),
 }
 
 SIGNATURES.update(_BASE_SIGNATURES)

@@ -398,3 +398,207 @@ def gather_rows_cols(x, idx):
     _lib.check(lib.tmf_gather_rows_cols_f32(_lib.ptr(x), _lib.ptr(idx), _lib.ptr(out), rows, cols, k,
                                             _lib.stream_ptr()), lib)
     return out
+
+
+# ---- full-catalog ranks of held-out pairs (tmf_item_ranks_*: LightFM's predict_rank / auc_score / reciprocal_rank) ----
+RANK_ROW_PAIRS = 16          # include/tmf.h TMF_RANK_ROW_PAIRS: positives per virtual row of the rank kernels
+RANK_BLOCK_BYTES = 1 << 30   # score block of the non-fused path (tmf_predict_gemm_f32 + tmf_rank_count_rows_f32)
+
+
+class _Pairs:
+    def __init__(self, indices, values):
+        self.indices, self.values = indices, values
+
+
+def positive_pairs(A, n_users, n_items, device=None):
+    """CSR (an Exclusion: sorted, de-duplicated, range-checked) of the held-out positives: the entries of A with a value > 0 -
+    recall_at_k's "relevant".  A: SparseInteractions (or indices / values / dense_shape) or a dense [n_users, n_items] table."""
+    if not torch.is_tensor(A) and hasattr(A, 'indices') and hasattr(A, 'values'):
+        idx, val = torch.as_tensor(A.indices), torch.as_tensor(A.values)
+        if device is not None:
+            idx, val = idx.to(device), val.to(device)
+        idx, keep = idx.to(torch.int64).reshape(-1, 2), val.reshape(-1) > 0
+        u, i = idx[:, 0][keep], idx[:, 1][keep]   # column first, mask second (see _hits_and_relevant)
+        return build_exclusion(_Pairs(torch.stack([u, i], 1), torch.ones(u.numel(), device=u.device)), n_users, n_items)
+    D = A if torch.is_tensor(A) else torch.as_tensor(__import__('numpy').asarray(A))
+    if device is not None:
+        D = D.to(device)
+    if D.dim() != 2 or tuple(D.shape) != (int(n_users), int(n_items)):
+        raise ValueError(f'a dense table of positives must be [{n_users}, {n_items}], got {tuple(D.shape)}')
+    return build_exclusion(D > 0, n_users, n_items)
+
+
+def _csr_rows(rowptr):
+    """Row of every entry of a CSR (int64)."""
+    m = rowptr.numel() - 1
+    return torch.repeat_interleave(torch.arange(m, device=rowptr.device), rowptr[1:] - rowptr[:-1])
+
+
+def _exclusion_view_pairs(ex, m, n):
+    """(rows, local item ids) of an Exclusion view for m users x n items: ids outside the window are dropped (as the kernels do)."""
+    rp = ex.rowptr[ex.user_base:ex.user_base + m + 1]
+    lo, hi = int(rp[0]), int(rp[-1])
+    cols = ex.cols[lo:hi].to(torch.int64) - ex.item_base
+    rows = _csr_rows(rp - lo)
+    keep = (cols >= 0) & (cols < n)
+    return rows[keep], cols[keep]
+
+
+def exclusion_counts(ex, m, n):
+    """Distinct excluded items of each of the m users inside the n-item catalog (int64 [m])."""
+    rows, _ = _exclusion_view_pairs(ex, m, n)
+    return torch.bincount(rows, minlength=m)
+
+
+def overlap_count(pos, ex, m, n):
+    """Number of (user, item) pairs that are both positives and excluded: the two sorted key lists merged by searchsorted."""
+    P = int(pos.rowptr[-1])
+    er, ec = _exclusion_view_pairs(ex, m, n)
+    if P == 0 or er.numel() == 0:
+        return 0
+    kp = _csr_rows(pos.rowptr) * n + pos.cols[:P].to(torch.int64)
+    ke = (er * n + ec).to(kp.device)
+    at = torch.clamp(torch.searchsorted(ke, kp), max=ke.numel() - 1)
+    return int((ke[at] == kp).sum())
+
+
+def virtual_rows(rowptr, pairs_per_row=RANK_ROW_PAIRS):
+    """The rank kernels' rows: a user with P > 0 positives becomes ceil(P / pairs_per_row) rows of at most pairs_per_row of them
+    (same user, consecutive CSR ranges), users in ascending order; users without positives get none.
+    Returns (user int32, begin int64, count int32)."""
+    counts = rowptr[1:] - rowptr[:-1]
+    nv = (counts + pairs_per_row - 1) // pairs_per_row
+    users = torch.repeat_interleave(torch.arange(counts.numel(), device=rowptr.device), nv)
+    first = torch.cumsum(nv, 0) - nv
+    part = torch.arange(users.numel(), device=rowptr.device) - first[users]
+    begin = rowptr[users] + pairs_per_row * part
+    count = torch.clamp(counts[users] - pairs_per_row * part, max=pairs_per_row)
+    return users.to(torch.int32), begin.to(torch.int64), count.to(torch.int32)
+
+
+def _rank_rows(vu, vb, vc, lo=0, hi=None):
+    hi = vu.numel() if hi is None else hi
+    return _lib.RankRows(vu.data_ptr() + 4 * lo, vb.data_ptr() + 8 * lo, vc.data_ptr() + 4 * lo, hi - lo)
+
+
+def item_ranks(user_embedding, item_embedding, positives, exclude=None, arithmetic=None, return_pairs=False):
+    """Full-catalog rank of every held-out positive: int32 [P] in the order of the positives' CSR (positive_pairs: row-major,
+    ascending).  rank(u, i) = the number of ELIGIBLE items j != i (not excluded; other positives count) that the fused top-k's
+    order (value desc, index asc) puts before i - 0 is the top.  Scores are the raw u.v (no clamp); an item whose score is NaN is
+    never counted above anyone, a positive whose own score is NaN gets the number of its user's non-NaN eligible items (itself
+    excluded).  No [m, n] score matrix is built.
+    positives: SparseInteractions or a dense table (entries > 0; duplicates count once).  exclude: as predict_topk; a pair that is
+    both positive and excluded raises ValueError (checked on the device before any launch), ids out of range IndexError.
+    arithmetic: 'fp32' (fp32 MFMA) or 'split' (three bf16 planes, r <= 256) run the fused GEMM + count (tmf_item_ranks_*) with the
+    pair scores of the same form (tmf_pair_scores_*); 'auto' takes 'split' where r <= 256, the scores computed (virtual rows x n)
+    reach SPLIT_MIN_SCORES and the item planes fit, else 'fp32'.  'half2', bf16 tables and r > 256 score blocks of users with
+    tmf_predict_gemm_f32 (bf16 rows cast to fp32 per block: the products are exact) and count with tmf_rank_count_rows_f32.
+    Under the same arithmetic and exclusion, rank < k holds exactly when the item is in predict_topk(..., k) - claimed for the
+    'fp32' and 'split' forms, whose pair scores are bit for bit those of their tiles.
+    return_pairs: also the CSR -> (rowptr int64 [m + 1], cols int32, ranks)."""
+    arithmetic = arithmetic or PREDICT_ARITHMETIC
+    if arithmetic not in ('auto', 'fp32', 'split', 'half2'):
+        raise ValueError(f"arithmetic={arithmetic!r}: expected 'auto', 'fp32', 'split' or 'half2'")
+    (m, r), (n, rb) = tuple(user_embedding.shape), tuple(item_embedding.shape)
+    if r != rb:
+        raise ValueError(f'embedding widths differ: {r} vs {rb}')
+    # the pairs are checked where the tables are, before anything is launched
+    home = user_embedding.device if torch.is_tensor(user_embedding) else torch.device('cpu')
+    pos = positive_pairs(positives, m, n, device=home)
+    ex = None if exclude is None else build_exclusion(exclude, m, n, device=home)
+    if ex is not None:
+        both = overlap_count(pos, ex, m, n)
+        if both:
+            raise ValueError(f'{both} (user, item) pairs are both positives and excluded: a held-out pair cannot be left out of '
+                             f'its own ranking')
+    lib = _lib.get()
+    U = _cuda(user_embedding).detach()
+    V = _cuda(item_embedding).detach()
+    dev = U.device
+    pos = _exclusion_on(pos, dev)
+    ex = None if ex is None else _exclusion_on(ex, dev)
+    P = int(pos.rowptr[-1])
+    ranks = torch.zeros(P, dtype=torch.int32, device=dev)
+    out = (pos.rowptr, pos.cols, ranks) if return_pairs else ranks
+    if P == 0:
+        return out
+    if arithmetic == 'split' and not lib.tmf_item_ranks_split_supported(r):
+        raise ValueError(f"arithmetic='split' ranks widths <= 256 (got {r})")
+    vu, vb, vc = virtual_rows(pos.rowptr)
+    bf16 = U.dtype == torch.bfloat16 and V.dtype == torch.bfloat16
+    fused = not bf16 and arithmetic != 'half2' and lib.tmf_item_ranks_f32_supported(r)
+    if not fused:
+        _item_ranks_blocks(lib, U, V, pos, ex, vu, vb, vc, ranks)
+        return out
+    A, _, _, lda = _gemm_operand(U)
+    B, _, _, ldb = _gemm_operand(V)
+    ws = None
+    if arithmetic in ('auto', 'split'):
+        if arithmetic == 'split' or vu.numel() * n >= SPLIT_MIN_SCORES:
+            need = lib.tmf_item_ranks_split_workspace_bytes(n, r)
+            try:
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            except torch.OutOfMemoryError:
+                if arithmetic == 'split':
+                    raise
+    pair_user = _csr_rows(pos.rowptr).to(torch.int32)
+    scores = torch.empty(P, dtype=torch.float32, device=dev)
+    pair_fn = lib.tmf_pair_scores_f32 if ws is None else lib.tmf_pair_scores_split
+    _lib.check(pair_fn(_lib.ptr(A), _lib.ptr(B), r, lda, ldb, _lib.ptr(pair_user), _lib.ptr(pos.cols), P, _lib.ptr(scores),
+                       _lib.stream_ptr()), lib)
+    rows = _rank_rows(vu, vb, vc)
+    exs = None if ex is None else ctypes.byref(ex.struct(m))
+    if ws is None:
+        _lib.check(lib.tmf_item_ranks_f32(_lib.ptr(A), _lib.ptr(B), n, r, lda, ldb, ctypes.byref(rows), _lib.ptr(pos.cols),
+                                          _lib.ptr(scores), exs, _lib.ptr(ranks), _lib.stream_ptr()), lib)
+    else:
+        _lib.check(lib.tmf_item_ranks_split(_lib.ptr(A), _lib.ptr(B), n, r, lda, ldb, ctypes.byref(rows), _lib.ptr(pos.cols),
+                                            _lib.ptr(scores), exs, _lib.ptr(ranks), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), lib)
+    return out
+
+
+def _item_ranks_blocks(lib, U, V, pos, ex, vu, vb, vc, ranks):
+    """The non-fused path: fp32 score blocks of users (tmf_predict_gemm_f32), counted by tmf_rank_count_rows_f32; blocks without a
+    positive are not scored."""
+    m, n = U.shape[0], V.shape[0]
+    Vf = V if V.dtype == torch.float32 else V.float()
+    step = max(1, min(m, RANK_BLOCK_BYTES // (4 * max(n, 1))))
+    bounds = torch.arange(0, m + step, step, device=vu.device).clamp_(max=m)
+    cut = torch.searchsorted(vu, bounds.to(torch.int32)).tolist()
+    bounds = bounds.tolist()
+    exs = None if ex is None else ctypes.byref(ex.struct(m))
+    for blk in range(len(bounds) - 1):
+        b, e, lo, hi = bounds[blk], bounds[blk + 1], cut[blk], cut[blk + 1]
+        if hi <= lo or e <= b:
+            continue
+        X = predict_gemm(U[b:e].float(), Vf)
+        rows = _rank_rows(vu, vb, vc, lo, hi)
+        _lib.check(lib.tmf_rank_count_rows_f32(_lib.ptr(X), e - b, n, X.stride(0), b, ctypes.byref(rows), _lib.ptr(pos.cols), exs,
+                                               _lib.ptr(ranks), _lib.stream_ptr()), lib)
+
+
+def auc_from_ranks(rowptr, ranks, n_items, excluded=None):
+    """Per-user AUC from the positives' ranks (CSR order; item_ranks): P positives, N = n_items - excluded - P negatives; with the
+    user's ranks sorted r_0 < ... < r_{P-1}, r_t - t negatives rank above the t-th positive, AUC = 1 - sum_t (r_t - t) / (P N) in
+    fp64, 1.0 where N = 0 (NaN where P = 0).  Returns (auc float32 [m], P int64 [m])."""
+    m = rowptr.numel() - 1
+    counts = rowptr[1:] - rowptr[:-1]
+    users = _csr_rows(rowptr)
+    ranks = ranks.to(device=rowptr.device, dtype=torch.int64)
+    srt = torch.sort(users * (n_items + 1) + ranks)[0] - users * (n_items + 1)   # ranks ascending inside each user
+    t = torch.arange(users.numel(), device=users.device) - rowptr[users]
+    above = torch.zeros(m, dtype=torch.float64, device=users.device).index_add_(0, users, (srt - t).to(torch.float64))
+    excluded = torch.zeros_like(counts) if excluded is None else excluded.to(counts.device)
+    neg = (n_items - excluded - counts).to(torch.float64)
+    auc = 1.0 - above / (counts.to(torch.float64) * neg)
+    auc = torch.where((neg == 0) & (counts > 0), torch.ones_like(auc), auc)
+    return auc.to(torch.float32), counts
+
+
+def reciprocal_rank_from_ranks(rowptr, ranks, n_items):
+    """Per-user 1 / (1 + min rank) of the positives (CSR order), float32 (1 / (1 + n_items) where P = 0).  Returns (rr, P)."""
+    m = rowptr.numel() - 1
+    counts = rowptr[1:] - rowptr[:-1]
+    best = torch.full((m,), int(n_items), dtype=torch.int64, device=rowptr.device)
+    best = best.scatter_reduce(0, _csr_rows(rowptr), ranks.to(device=rowptr.device, dtype=torch.int64), reduce='amin')
+    return (1.0 / (1.0 + best.to(torch.float64))).to(torch.float32), counts

@@ -663,6 +663,19 @@ __device__ __forceinline__ void excl_apply(ACC (&acc)[NJ], const unsigned (&w)[N
     }
 }
 
+// The three-plane split of the bf16-plane kernels (tmf_predict_split.hip, tmf_rank.hip).
+// x -> (x1, x2, x3) with x1 + x2 + x3 == x exactly for every finite x whose residuals stay normal.  A value that rounds to
+// +-inf in bf16 is truncated instead; non-finite inputs keep their class in x1 and contribute nothing through x2, x3.
+__device__ __forceinline__ void split3(float x, __bf16& x1, __bf16& x2, __bf16& x3) {
+    __bf16 h = (__bf16)x;
+    if (__builtin_isinf((float)h) && !__builtin_isinf(x)) h = __builtin_bit_cast(__bf16, (uint16_t)(__float_as_uint(x) >> 16));
+    x1 = h;
+    if (!__builtin_isfinite(x)) { x2 = (__bf16)0.0f; x3 = (__bf16)0.0f; return; }
+    const float r1 = x - (float)h;
+    x2 = (__bf16)r1;
+    x3 = (__bf16)(r1 - (float)x2);
+}
+
 // Unfilled list slots (the fill entry of the lists) leave as id -1
 __device__ __forceinline__ int32_t excl_out_id(int32_t ix) { return ix == 0x7fffffff ? -1 : ix; }
 

@@ -80,17 +80,7 @@ __device__ __forceinline__ float max3_raw(float a, float b, float c) {
 
 __device__ __forceinline__ bool before_s(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
 
-// x -> (x1, x2, x3) with x1 + x2 + x3 == x exactly for every finite x whose residuals stay normal.  A value that rounds to
-// +-inf in bf16 is truncated instead; non-finite inputs keep their class in x1 and contribute nothing through x2, x3.
-__device__ __forceinline__ void split3(float x, __bf16& x1, __bf16& x2, __bf16& x3) {
-    __bf16 h = (__bf16)x;
-    if (__builtin_isinf((float)h) && !__builtin_isinf(x)) h = __builtin_bit_cast(__bf16, (uint16_t)(__float_as_uint(x) >> 16));
-    x1 = h;
-    if (!__builtin_isfinite(x)) { x2 = (__bf16)0.0f; x3 = (__bf16)0.0f; return; }
-    const float r1 = x - (float)h;
-    x2 = (__bf16)r1;
-    x3 = (__bf16)(r1 - (float)x2);
-}
+// split3 (x -> three exact bf16 planes) lives in tmf_common.h: the rank kernels (tmf_rank.hip) split with the same routine.
 
 // Two-plane fp16 split of x * scale (scale a power of two that puts the largest magnitude of the row / table into
 // [2^14, 2^15)): x = (h1 + h2) / scale to 22 bits, and to 2^-25 / scale absolutely where h2 is subnormal.  Non-finite values
@@ -154,6 +144,12 @@ __global__ __launch_bounds__(256) void k_split3_rows(const float* __restrict__ X
     *reinterpret_cast<bf16x8_s*>(out + o) = p1;
     *reinterpret_cast<bf16x8_s*>(out + plane + o) = p2;
     *reinterpret_cast<bf16x8_s*>(out + 2 * plane + o) = p3;
+}
+
+// The item planes for the rank kernels of tmf_rank.hip (the same planes, from the same routine, as the top-k's)
+void launch_split3_rows(const float* X, int64_t rows, int r, int64_t ld, __bf16* out, int64_t rows_pad, int ldp, hipStream_t s) {
+    const int64_t blocks = (rows_pad * (ldp / 8) + 255) / 256;
+    hipLaunchKernelGGL(k_split3_rows, dim3((unsigned)blocks), dim3(256), 0, s, X, rows, r, ld, out, rows_pad, ldp);
 }
 
 // max |x| over rows [0, rows) x columns [0, r) -> *out (as the bits of a non-negative float: atomicMax on the integer)

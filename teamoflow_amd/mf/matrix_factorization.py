@@ -492,6 +492,53 @@ class MatrixFactorization:
             return ndcg[torch.count_nonzero(A, dim=1) > 0]
         return torch.where(~torch.isnan(ndcg), ndcg, torch.zeros_like(ndcg))
 
+    def _rank_pairs(self, A, exclude):
+        """(positives' CSR rowptr, cols, int32 ranks, exclusion CSR or None) of item_ranks."""
+        ep = getattr(self, '_sharded_epoch', None)
+        if ep is not None and ep.world > 1:
+            raise NotImplementedError('item-row-sharded fit: this rank holds only its item rows; full-catalog ranks need every '
+                                      'window (dist.gather_item_embedding assembles the table where it fits)')
+        ex = None if exclude is None else self._exclusion(exclude)
+        rowptr, cols, ranks = _ops.item_ranks(self.user_embedding, self.item_embedding, A, exclude=ex,
+                                              arithmetic=getattr(self, 'predict_arithmetic', None), return_pairs=True)
+        return rowptr, cols, ranks, ex
+
+    def item_ranks(self, A, *, exclude=None):
+        """Extension (LightFM's predict_rank): the full-catalog rank of every held-out positive, without the [m, n] scores.
+        A: SparseInteractions or a dense table; its entries > 0 are the positives (recall_at_k's "relevant"; duplicates count
+        once).  rank(u, i) = the number of eligible items j != i - not in ``exclude`` (LightFM's train_interactions); the other
+        positives count - that score above i, equal scores ordered by ascending id (retrieve_user_recs' order), so 0 is the top
+        and rank < k exactly when i is in retrieve_user_recs(k=k, exclude=exclude)[u] (fp32 and split arithmetic).  Scores are the
+        raw u.v (no clamp); a NaN score is never counted above anyone.  A pair both positive and excluded raises ValueError.
+        Returns (indices [P, 2] int64 (user, item), row-major ascending; ranks [P] int64), on the model's device."""
+        rowptr, cols, ranks, _ = self._rank_pairs(A, exclude)
+        P = ranks.numel()
+        users = _ops._csr_rows(rowptr)
+        return torch.stack([users, cols[:P].to(torch.int64)], 1), ranks.to(torch.int64)
+
+    def _per_user(self, value, counts, preserve_rows):
+        if not preserve_rows:
+            return value[counts > 0]
+        return torch.where(counts > 0, value, torch.zeros_like(value))
+
+    def auc_score(self, A, preserve_rows=False, *, exclude=None):
+        """Extension (LightFM's auc_score): per-user AUC of the held-out positives against the eligible negatives, from
+        item_ranks (same arguments); the caller takes the mean.  With P positives and N = n_items - |excluded| - P negatives and the
+        ranks sorted r_0 < ... < r_{P-1}, r_t - t negatives score above the t-th positive: AUC = 1 - sum_t (r_t - t) / (P N), in
+        fp64, returned as float32; 1.0 when N = 0.  Users without positives are dropped, or get 0 with preserve_rows
+        (recall_at_k's convention)."""
+        rowptr, _, ranks, ex = self._rank_pairs(A, exclude)
+        m, n = rowptr.numel() - 1, self.item_embedding.shape[0]
+        auc, counts = _ops.auc_from_ranks(rowptr, ranks, n, _ops.exclusion_counts(ex, m, n) if ex is not None else None)
+        return self._per_user(auc, counts, preserve_rows)
+
+    def reciprocal_rank(self, A, preserve_rows=False, *, exclude=None):
+        """Extension (LightFM's reciprocal_rank): per user 1 / (1 + the best rank of a held-out positive), from item_ranks (same
+        arguments); float32, the caller takes the mean.  Users without positives as in auc_score."""
+        rowptr, _, ranks, _ = self._rank_pairs(A, exclude)
+        rr, counts = _ops.reciprocal_rank_from_ranks(rowptr, ranks, self.item_embedding.shape[0])
+        return self._per_user(rr, counts, preserve_rows)
+
     def retrieve_user_recs(self, user=None, k=None, *, exclude=None):
         """:416-438.  Item ids ranked by score (numpy int32, like tf.math.top_k(...).indices.numpy()).  exclude (extension):
         (user, item) pairs left out - SparseInteractions or a dense table over all users (also with `user`); slots past a
