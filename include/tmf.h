@@ -489,6 +489,16 @@ int tmf_item_ranks_split(const float* A, const float* B, int64_t n, int r, int64
 int tmf_rank_count_rows_f32(float* X, int64_t rows, int64_t cols, int64_t ldx, int64_t user_base, const tmf_rank_rows* vrows,
                             const int32_t* pos_item, const tmf_exclusion* exclude, int32_t* out_rank, void* stream);
 
+/* DCG@k and IDCG@k of a graded test table (matrix_factorization.py:320-413) without the [m, n] scores.  Row u of the table is
+ * cols / gain [rowptr[u] .. rowptr[u+1]): distinct item ids ascending and their gains (2^a - 1); every other eligible item has gain 0.
+ *   dcg[u]  = sum_{j < k} gain(u, top[u * ldt + j]) / den[j]   (top: the user's ranked list, -1 = an empty slot; NULL without dcg)
+ *   idcg[u] = sum_{j < k} g_(j) / den[j] over the k largest values of {the row's gains} + n_zero[u] zeros (fewer slots when the
+ *             multiset is smaller); n_zero NULL = n_items - stored.
+ * den [k]: the discount of every slot.  Sums run over the slots in order, slot 0 first (deterministic; no atomics).  dcg or idcg may
+ * be NULL.  Any k >= 1; a row of any length (long rows are radix-selected by a workgroup, never sorted whole). */
+int tmf_dcg_idcg_f32(const int64_t* rowptr, const int32_t* cols, const float* gain, int64_t m, int64_t n_items, const int32_t* top,
+                     int64_t ldt, int k, const float* den, const int64_t* n_zero, float* dcg, float* idcg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

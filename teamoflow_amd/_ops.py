@@ -595,6 +595,127 @@ def auc_from_ranks(rowptr, ranks, n_items, excluded=None):
     return auc.to(torch.float32), counts
 
 
+class GradedTable:
+    """A graded test table as a CSR (graded_csr): row u's item ids are cols[rowptr[u]:rowptr[u + 1]] (ascending, distinct), their
+    gains 2^a - 1 in gain; cols / gain hold at least one element (valid pointers for the kernel)."""
+
+    def __init__(self, rowptr, cols, gain, n_users, n_items):
+        self.rowptr, self.cols, self.gain = rowptr, cols, gain
+        self.n_users, self.n_items = int(n_users), int(n_items)
+
+    def stored(self):
+        """Stored (non-zero) entries of every user (int64 [m]): the rows ndcg_at_k keeps without preserve_rows."""
+        return self.rowptr[1:] - self.rowptr[:-1]
+
+
+def graded_csr(A, n_users, n_items, device=None):
+    """The graded test table of dcg_at_k / idcg_at_k / ndcg_at_k: every entry of A with its value a, duplicates summed (as
+    SparseInteractions.to_dense does, in input order), entries whose sum is 0 dropped, gain = 2^a - 1 computed with the dense path's
+    expression (torch.pow(2.0, a) - 1.0) where the table is.  A: SparseInteractions (or indices / values / dense_shape) or a dense
+    [n_users, n_items] table.  A dense_shape or a dense shape other than (n_users, n_items) raises ValueError, an id out of range
+    IndexError.  On the device the rows are ordered by tmf_csr_build; CPU tables (argument checks, tests) by a stable torch sort."""
+    n_users, n_items = int(n_users), int(n_items)
+    if not torch.is_tensor(A) and hasattr(A, 'indices') and hasattr(A, 'values'):
+        shape = getattr(A, 'dense_shape', None)
+        if shape is not None and (int(shape[0]), int(shape[1])) != (n_users, n_items):
+            raise ValueError(f'the test table is {tuple(int(x) for x in shape)}, the model ranks [{n_users}, {n_items}]')
+        idx, val = torch.as_tensor(A.indices), torch.as_tensor(A.values)
+        if device is not None:
+            idx, val = idx.to(device), val.to(device)
+        idx = idx.to(torch.int64).reshape(-1, 2)
+        u, i = idx[:, 0].contiguous(), idx[:, 1].contiguous()   # columns, never masked rows of [nnz, 2] (see _hits_and_relevant)
+        val = val.reshape(-1).to(torch.float32).contiguous()
+    else:
+        D = A if torch.is_tensor(A) else torch.as_tensor(__import__('numpy').asarray(A))
+        if device is not None:
+            D = D.to(device)
+        if D.dim() != 2 or tuple(D.shape) != (n_users, n_items):
+            raise ValueError(f'a dense test table must be [{n_users}, {n_items}], got {tuple(D.shape)}')
+        D = D.to(torch.float32)
+        nz = torch.nonzero(D)
+        u, i = nz[:, 0].contiguous(), nz[:, 1].contiguous()
+        val = D[u, i]
+    if u.numel() != val.numel():
+        raise ValueError('indices and values disagree on the number of entries')
+    nnz = u.numel()
+    if nnz:
+        if int(u.min()) < 0 or int(u.max()) >= n_users:
+            raise IndexError(f'test user id out of range [0, {n_users})')
+        if int(i.min()) < 0 or int(i.max()) >= n_items:
+            raise IndexError(f'test item id out of range [0, {n_items})')
+    dev = u.device
+    if dev.type == 'cuda' and 0 < nnz < 2 ** 31:
+        lib = _lib.get()
+        rowptr = torch.empty(n_users + 1, dtype=torch.int64, device=dev)
+        cols = torch.empty(nnz, dtype=torch.int32, device=dev)
+        vals = torch.empty(nnz, dtype=torch.float32, device=dev)
+        rows = torch.empty(nnz, dtype=torch.int32, device=dev)
+        ws = torch.empty(lib.tmf_csr_build_workspace_bytes(nnz), dtype=torch.uint8, device=dev)
+        pairs = torch.stack([u, i], 1)
+        _lib.check(lib.tmf_csr_build(_lib.ptr(pairs), _lib.ptr(val), nnz, n_users, n_items, _lib.ptr(rowptr), _lib.ptr(cols),
+                                     _lib.ptr(vals), _lib.ptr(rows), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), lib)
+        del ws, pairs
+    else:
+        key = u * n_items + i
+        perm = torch.sort(key, stable=True)[1]
+        rows, cols, vals, rowptr = u[perm], i[perm].to(torch.int32), val[perm], None
+    if nnz > 1:
+        key = rows.to(torch.int64) * n_items + cols.to(torch.int64)
+        first = torch.ones(nnz, dtype=torch.bool, device=dev)
+        torch.ne(key[1:], key[:-1], out=first[1:])
+        del key
+        if not bool(first.all()):   # duplicates: adjacent, in input order
+            starts = torch.nonzero(first).flatten()
+            lengths = torch.diff(starts, append=torch.tensor([nnz], device=dev))
+            vals = torch.segment_reduce(vals, 'sum', lengths=lengths)
+            rows, cols, rowptr = rows[starts], cols[starts], None
+    keep = vals != 0
+    if not bool(keep.all()):
+        rows, cols, vals, rowptr = rows[keep], cols[keep], vals[keep], None
+    if rowptr is None:
+        rowptr = torch.zeros(n_users + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(torch.bincount(rows.to(torch.int64), minlength=n_users), 0, out=rowptr[1:])
+    gain = torch.pow(2.0, vals) - 1.0
+    if cols.numel() == 0:
+        cols = torch.zeros(1, dtype=torch.int32, device=dev)
+        gain = torch.zeros(1, dtype=torch.float32, device=dev)
+    return GradedTable(rowptr, cols.contiguous(), gain.contiguous(), n_users, n_items)
+
+
+def dcg_discounts(k, device):
+    """log1p(j + 1) / log(2) for slots j = 0 .. k - 1: the expression of MatrixFactorization._dcg_terms, so that every term
+    gain / discount is the dense path's term bit for bit."""
+    import numpy as np
+    order = torch.arange(1, k + 1, dtype=torch.float32, device=device)
+    return torch.log1p(order) / float(np.log(np.float32(2.0)))
+
+
+def dcg_idcg(table, top, k, n_zero=None, want_dcg=True, want_idcg=True):
+    """Per-user DCG@k from the ranked lists top (int32 [m, >= k], -1 = empty slot) and IDCG@k of the graded table (GradedTable)
+    with n_zero[u] zero gains beside the stored ones (None: every unstored item) - one launch of tmf_dcg_idcg_f32.
+    Returns (dcg, idcg) float32 [m] on the device (None for what was not asked)."""
+    lib = _lib.get()
+    m, n, k = table.n_users, table.n_items, int(k)
+    if k < 1:
+        raise ValueError(f'k={k} must be >= 1')
+    rowptr, cols, gain = (_cuda(table.rowptr, torch.int64).contiguous(), _cuda(table.cols, torch.int32).contiguous(),
+                          _cuda(table.gain, torch.float32).contiguous())
+    dev = rowptr.device
+    den = dcg_discounts(k, dev)
+    dcg = torch.empty(m, dtype=torch.float32, device=dev) if want_dcg else None
+    idcg = torch.empty(m, dtype=torch.float32, device=dev) if want_idcg else None
+    ldt = 0
+    if want_dcg:
+        top = _cuda(top, torch.int32)
+        if top.dim() != 2 or top.shape[0] != m or top.shape[1] < k or top.stride(1) != 1:
+            raise ValueError(f'top must be [{m}, >= {k}] int32 with unit column stride, got {tuple(top.shape)}')
+        ldt = top.stride(0)
+    nz = None if n_zero is None else _cuda(n_zero, torch.int64).contiguous()
+    _lib.check(lib.tmf_dcg_idcg_f32(_lib.ptr(rowptr), _lib.ptr(cols), _lib.ptr(gain), m, n, _lib.ptr(top) if want_dcg else None, ldt, k,
+                                    _lib.ptr(den), _lib.ptr(nz), _lib.ptr(dcg), _lib.ptr(idcg), _lib.stream_ptr()), lib)
+    return dcg, idcg
+
+
 def reciprocal_rank_from_ranks(rowptr, ranks, n_items):
     """Per-user 1 / (1 + min rank) of the positives (CSR order), float32 (1 / (1 + n_items) where P = 0).  Returns (rr, P)."""
     m = rowptr.numel() - 1

@@ -473,19 +473,71 @@ class MatrixFactorization:
         denominator = torch.log1p(order) / float(np.log(np.float32(2.0)))
         return numerator, denominator
 
-    def dcg_at_k(self, dense_interactions, k=10):
-        """:320-351."""
+    @staticmethod
+    def _sparse_dcg_path(A, exclude):
+        """Sparse test tables and exclude= take the top-k + tmf_dcg_idcg_f32 path; a dense table without exclude keeps the reference's
+        full sort (_dcg_terms)."""
+        return exclude is not None or (not torch.is_tensor(A) and hasattr(A, 'indices') and hasattr(A, 'values'))
+
+    def _dcg_setup(self, A, k, exclude):
+        """(graded test table, effective k, exclusion or None, zero gains per user or None) of the sparse DCG path, every argument
+        checked before anything is launched."""
+        ep = getattr(self, '_sharded_epoch', None)
+        if ep is not None and ep.world > 1:
+            raise NotImplementedError('item-row-sharded fit: this rank holds only its item rows; dcg / idcg / ndcg need every window '
+                                      '(dist.gather_item_embedding assembles the table where it fits)')
+        k = int(k)
+        if k < 1:
+            raise ValueError(f'k={k} must be >= 1')
+        m, n = self.user_embedding.shape[0], self.item_embedding.shape[0]
+        table = _ops.graded_csr(A, m, n, device=self.user_embedding.device)
+        ex, n_zero = None, None
+        if exclude is not None:
+            ex = self._exclusion(exclude)
+            both = _ops.overlap_count(table, ex, m, n)
+            if both:
+                raise ValueError(f'{both} (user, item) pairs are both test entries and excluded: an excluded item cannot be retrieved, '
+                                 f'so it cannot count in the ideal ranking')
+            if ex.user_base == 0 and ex.item_base == 0 and ex.n_items == n:   # a whole table (build_exclusion): distinct ids < n
+                excluded = ex.rowptr[1:m + 1] - ex.rowptr[:m]
+            else:
+                excluded = _ops.exclusion_counts(ex, m, n)
+            n_zero = n - excluded.to(table.rowptr.device) - table.stored()
+        return table, min(k, n), ex, n_zero
+
+    def _dcg_idcg(self, A, k, exclude, want_dcg, want_idcg):
+        table, k, ex, n_zero = self._dcg_setup(A, k, exclude)
+        top = self._top_items(k, clamp=False, exclude=ex) if want_dcg else None
+        dcg, idcg = _ops.dcg_idcg(table, top, k, n_zero=n_zero, want_dcg=want_dcg, want_idcg=want_idcg)
+        return dcg, idcg, table
+
+    def dcg_at_k(self, dense_interactions, k=10, *, exclude=None):
+        """:320-351.  Extension: a SparseInteractions table and exclude (as recall_at_k) rank the top-k of the fused kernels (raw
+        scores, exclude= left out; retrieve_user_recs' lists) and look up the gains 2^a - 1 of the listed items in the test table's
+        CSR (tmf_dcg_idcg_f32) - no [m, n] scores.  A dense table without exclude keeps the reference's full sort."""
+        if self._sparse_dcg_path(dense_interactions, exclude):
+            return self._dcg_idcg(dense_interactions, k, exclude, True, False)[0]
         numerator, denominator = self._dcg_terms(dense_interactions)
         return (numerator / denominator[None, :])[:, :k].sum(dim=1)
 
-    def idcg_at_k(self, dense_interactions, k=10):
-        """:353-384."""
+    def idcg_at_k(self, dense_interactions, k=10, *, exclude=None):
+        """:353-384.  Extension (sparse table or exclude, as dcg_at_k): the k largest gains of the user's row, padded with the zero
+        gains of the eligible items the row does not store - independent of the model, no GEMM."""
+        if self._sparse_dcg_path(dense_interactions, exclude):
+            return self._dcg_idcg(dense_interactions, k, exclude, False, True)[1]
         numerator, denominator = self._dcg_terms(dense_interactions)
         ideal = torch.sort(numerator, dim=1, descending=True, stable=True)[0]
         return (ideal / denominator[None, :])[:, :k].sum(dim=1)
 
-    def ndcg_at_k(self, A, k=10, preserve_rows=False):
-        """:386-413."""
+    def ndcg_at_k(self, A, k=10, preserve_rows=False, *, exclude=None):
+        """:386-413.  Extension (sparse A or exclude, as dcg_at_k): one top-k and one launch for DCG and IDCG.  A pair that is both a
+        test entry and excluded raises ValueError."""
+        if self._sparse_dcg_path(A, exclude):
+            dcg, idcg, table = self._dcg_idcg(A, k, exclude, True, True)
+            ndcg = dcg / idcg
+            if not preserve_rows:
+                return ndcg[table.stored().to(ndcg.device) > 0]
+            return torch.where(~torch.isnan(ndcg), ndcg, torch.zeros_like(ndcg))
         ndcg = self.dcg_at_k(A, k) / self.idcg_at_k(A, k)
         if not preserve_rows:
             A = torch.as_tensor(A).to(ndcg.device)
