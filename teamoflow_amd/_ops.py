@@ -2,6 +2,7 @@
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -18,14 +19,16 @@ def _cuda(t, dtype=None):
     return t
 
 
-def _gemm_operand(t):
-    """[rows, r] fp32 tensor -> (tensor kept alive, rows, r, ld) with 16-byte aligned rows."""
-    t = _cuda(t, torch.float32).detach()
+def _operand(t, per16=4):
+    """[rows, r] tensor -> (tensor kept alive, rows, r, ld) with 16-byte aligned rows: ld a multiple of per16, the elements per
+    16 bytes (4: the tensor as fp32, 8: a bf16 tensor)."""
+    dtype = torch.float32 if per16 == 4 else torch.bfloat16
+    t = _cuda(t, dtype).detach()
     rows, r = t.shape
-    ok = t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= r and t.data_ptr() % 16 == 0
+    ok = t.stride(1) == 1 and t.stride(0) % per16 == 0 and t.stride(0) >= r and t.data_ptr() % 16 == 0
     if not ok:
-        ld = (r + 3) // 4 * 4
-        p = torch.zeros(rows, ld, dtype=torch.float32, device=t.device)
+        ld = (r + per16 - 1) // per16 * per16
+        p = torch.zeros(rows, ld, dtype=dtype, device=t.device)
         p[:, :r] = t
         t = p[:, :r]
     return t, rows, r, t.stride(0)
@@ -34,8 +37,8 @@ def _gemm_operand(t):
 def predict_gemm(user_embedding, item_embedding, out=None):
     """user_embedding [m, r] @ item_embedding [n, r]^T -> [m, n] fp32 (exact-fp32 MFMA)."""
     lib = _lib.get()
-    A, m, r, lda = _gemm_operand(user_embedding)
-    B, n, rb, ldb = _gemm_operand(item_embedding)
+    A, m, r, lda = _operand(user_embedding)
+    B, n, rb, ldb = _operand(item_embedding)
     if r != rb:
         raise ValueError(f'embedding widths differ: {r} vs {rb}')
     if out is None:
@@ -66,6 +69,55 @@ class Exclusion:
         return _lib.Exclusion(self.rowptr.data_ptr() + 8 * self.user_base, self.cols.data_ptr(), self.item_base)
 
 
+def _decode_table(A, what, device=None, shape=None, keep=None):
+    """(u, i, val, stated shape) of a table of (user, item) entries: a SparseInteractions-like object (indices / values, optional
+    dense_shape: the stated shape, else None) or a dense [rows, cols] table (torch or NumPy; its non-zeros; ``shape``: what it must
+    be), moved to ``device`` when one is given.  keep: 'nonzero' or 'positive' - only the ids of the entries with such a value are
+    wanted (val is None); None: every entry with its value."""
+    if not torch.is_tensor(A) and hasattr(A, 'indices') and hasattr(A, 'values'):
+        idx, val = torch.as_tensor(A.indices), torch.as_tensor(A.values)
+        if device is not None:
+            idx, val = idx.to(device), val.to(device)
+        idx, val = idx.to(torch.int64).reshape(-1, 2), val.reshape(-1)
+        # column first, mask second: masked ROW selection of a [nnz, 2] tensor is unreliable beyond ~6e7 rows on this
+        # PyTorch-ROCm build (tools/torch_row_index_probe.py)
+        u, i = idx[:, 0], idx[:, 1]
+        if keep is not None:
+            mask = val > 0 if keep == 'positive' else val != 0
+            u, i, val = u[mask], i[mask], None
+        stated = getattr(A, 'dense_shape', None)
+        return u, i, val, None if stated is None else (int(stated[0]), int(stated[1]))
+    D = A if torch.is_tensor(A) else torch.as_tensor(np.asarray(A))
+    if device is not None:
+        D = D.to(device)
+    if D.dim() != 2 or (shape is not None and tuple(D.shape) != shape):
+        raise ValueError(f'a dense table of {what} must be {"2-D" if shape is None else list(shape)}, got shape {tuple(D.shape)}')
+    nz = torch.nonzero(D > 0 if keep == 'positive' else D)   # the non-zeros of D itself: no [rows, cols] mask for them
+    u, i = nz[:, 0], nz[:, 1]
+    return u, i, D[u, i] if keep is None else None, None
+
+
+def _check_ids(u, i, n_users, n_items, what):
+    if u.numel():
+        if int(u.min()) < 0 or int(u.max()) >= n_users:
+            raise IndexError(f'{what} user id out of range [0, {n_users})')
+        if int(i.min()) < 0 or int(i.max()) >= n_items:
+            raise IndexError(f'{what} item id out of range [0, {n_items})')
+
+
+def _pairs_csr(u, i, n_users, n_items):
+    """Exclusion (CSR: rows sorted and de-duplicated) of (user, item) pairs whose ids are in range."""
+    dev = u.device
+    keys = torch.unique(u * n_items + i)   # sorted and distinct: row-major (user, item) order
+    rows = torch.div(keys, n_items, rounding_mode='floor') if n_items else keys
+    rowptr = torch.zeros(n_users + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(rows, minlength=n_users), 0, out=rowptr[1:])
+    cols = (keys - rows * n_items).to(torch.int32)
+    if cols.numel() == 0:
+        cols = torch.zeros(1, dtype=torch.int32, device=dev)   # a valid pointer for the kernels; rowptr says there is nothing
+    return Exclusion(rowptr, cols, n_users, n_items)
+
+
 def build_exclusion(exclude, n_users, n_items, device=None):
     """CSR of the pairs to leave out of a ranking.  ``exclude``: an Exclusion (returned as it is), SparseInteractions or an object
     with indices / values / dense_shape (every stored entry with a value != 0 is a pair), or a dense [rows, cols] table (every
@@ -78,35 +130,9 @@ def build_exclusion(exclude, n_users, n_items, device=None):
                              f'{exclude.user_base + n_users})')
         return exclude
     n_users, n_items = int(n_users), int(n_items)
-    if not torch.is_tensor(exclude) and hasattr(exclude, 'indices') and hasattr(exclude, 'values'):
-        idx, val = torch.as_tensor(exclude.indices), torch.as_tensor(exclude.values)
-        if device is not None:
-            idx, val = idx.to(device), val.to(device)
-        idx = idx.to(torch.int64).reshape(-1, 2)
-        keep = val.reshape(-1) != 0
-        u, i = idx[:, 0][keep], idx[:, 1][keep]
-    else:
-        A = exclude if torch.is_tensor(exclude) else torch.as_tensor(__import__('numpy').asarray(exclude))
-        if device is not None:
-            A = A.to(device)
-        if A.dim() != 2:
-            raise ValueError(f'a dense exclusion table must be 2-D, got shape {tuple(A.shape)}')
-        nz = torch.nonzero(A)
-        u, i = nz[:, 0], nz[:, 1]
-    dev = u.device
-    if u.numel():
-        if int(u.min()) < 0 or int(u.max()) >= n_users:
-            raise IndexError(f'excluded user id out of range [0, {n_users})')
-        if int(i.min()) < 0 or int(i.max()) >= n_items:
-            raise IndexError(f'excluded item id out of range [0, {n_items})')
-    keys = torch.unique(u * n_items + i)   # sorted and distinct: row-major (user, item) order
-    rows = torch.div(keys, n_items, rounding_mode='floor') if n_items else keys
-    rowptr = torch.zeros(n_users + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(torch.bincount(rows, minlength=n_users), 0, out=rowptr[1:])
-    cols = (keys - rows * n_items).to(torch.int32)
-    if cols.numel() == 0:
-        cols = torch.zeros(1, dtype=torch.int32, device=dev)   # a valid pointer for the kernels; rowptr says there is nothing
-    return Exclusion(rowptr, cols, n_users, n_items)
+    u, i, _, _ = _decode_table(exclude, 'exclusions', device, keep='nonzero')
+    _check_ids(u, i, n_users, n_items, 'excluded')
+    return _pairs_csr(u, i, n_users, n_items)
 
 
 def _exclusion_on(ex, device):
@@ -124,23 +150,21 @@ def merge_lists(vals, ids, k):
     return torch.gather(v, 1, order)[:, :k], torch.gather(i, 1, order)[:, :k]
 
 
+def merge_windows(vals, ids, k, fill, return_values=True):
+    """(values, ids) of the k best of per-window top lists laid side by side in catalog order, so that equal values keep ascending
+    item order.  fill: the lists may hold -1 / -inf fill entries (rankings with an exclusion) -> merge_lists; without them one
+    stable top-k over the candidates (the window values carry their clamp already), its values only when asked for."""
+    if fill:
+        return merge_lists(vals, ids, k)
+    out = topk_stable(vals, k, return_values=return_values)
+    v, pos = out if return_values else (None, out)
+    return v, torch.gather(ids, 1, pos.long())
+
+
 FUSED_MAX_K, FUSED_MAX_K_BF16, FUSED_MAX_R, FUSED_MAX_R_BF16 = 64, 32, 256, 256
 SPLIT_MIN_SCORES = 1 << 26   # arithmetic='auto' takes the three-plane bf16 split from this many scores (m * n) on: below, the pass that
                              # splits the item table and its workspace are not worth it and the fp32 MFMA kernel answers
 SORT_MAX_ELEMS = 1 << 29   # elements ranked per call of the wide-row path (2 GB of keys + 2 GB of ids, twice)
-
-
-def _bf16_operand(t):
-    """[rows, r] bf16 tensor -> (tensor, rows, r, ld) with 16-byte aligned rows (ld % 8 == 0)."""
-    t = t.detach()
-    rows, r = t.shape
-    ok = t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.stride(0) >= r and t.data_ptr() % 16 == 0
-    if not ok:
-        ld = (r + 7) // 8 * 8
-        p = torch.zeros(rows, ld, dtype=torch.bfloat16, device=t.device)
-        p[:, :r] = t
-        t = p[:, :r]
-    return t, rows, r, t.stride(0)
 
 
 def fused_topk_supported(user_embedding, item_embedding, k):
@@ -208,129 +232,108 @@ def predict_topk(user_embedding, item_embedding, k, clamp_negatives=False, retur
     arithmetic = arithmetic or PREDICT_ARITHMETIC
     if arithmetic not in ('auto', 'fp32', 'split', 'half2'):
         raise ValueError(f"arithmetic={arithmetic!r}: expected 'auto', 'fp32', 'split' or 'half2'")
-    if torch.is_tensor(user_embedding) and torch.is_tensor(item_embedding) and \
-            user_embedding.dtype == torch.bfloat16 and item_embedding.dtype == torch.bfloat16:
-        A, m, r, lda = _bf16_operand(_cuda(user_embedding))
-        B, n, rb, ldb = _bf16_operand(_cuda(item_embedding))
-        if r != rb:
-            raise ValueError(f'embedding widths differ: {r} vs {rb}')
-        k = int(k)
-        if not 1 <= k <= n:
-            raise ValueError(f'k={k} must be in [1, {n}]')
-        ex = None if exclude is None else _exclusion_on(build_exclusion(exclude, m, n), A.device)
-        if FUSED_MAX_K_BF16 < k <= FUSED_MAX_K:
-            # The bf16 kernel keeps 256 users' lists in LDS: k <= 32.  Beyond it the fp32 fused kernel (k <= 64) ranks exact fp32
-            # copies of the rows - a bf16 x bf16 product is exact in fp32 either way, the fp32 sums differ in order only.
-            # Costs a transient fp32 copy of the item table (twice its size); when that does not fit the catalog is ranked in windows
-            # of rows (a copy of one window at a time) and the per-window lists are merged by one stable top-k - windows in catalog
-            # order, so equal scores keep ascending item order.
-            if m == 0:
-                idx = torch.empty(0, k, dtype=torch.int32, device=A.device)
-                return (torch.empty(0, k, dtype=torch.float32, device=A.device), idx) if return_values else idx
-            try:
-                windows = [(0, _upcast_table(B))]
-            except torch.OutOfMemoryError:
-                step = max(k, -(-n // BF16_UPCAST_WINDOWS))
-                windows = [(c0, None) for c0 in range(0, n, step)]
-                if n - windows[-1][0] < k:   # a last window narrower than k joins the one before it
-                    windows.pop()
-            out_i, out_v = [], []
-            for b in range(0, m, BF16_UPCAST_USERS):
-                Au = A[b:b + BF16_UPCAST_USERS].float()
-                cand_v, cand_i = [], []
-                for w, (c0, Bf) in enumerate(windows):
-                    c1 = windows[w + 1][0] if w + 1 < len(windows) else n
-                    v_, i_ = predict_topk(Au, Bf if Bf is not None else B[c0:c1].float(), k, clamp_negatives=clamp_negatives,
-                                          return_values=True, arithmetic='fp32',
-                                          exclude=None if ex is None else ex.shifted(b, c0))
-                    cand_v.append(v_)
-                    cand_i.append(i_ + c0 if ex is None else torch.where(i_ >= 0, i_ + c0, i_))
-                if len(windows) > 1 and ex is not None:
-                    v_, i_ = merge_lists(torch.cat(cand_v, dim=1), torch.cat(cand_i, dim=1), k)
-                    cand_v, cand_i = [v_], [i_]
-                elif len(windows) > 1:
-                    cv, ci = torch.cat(cand_v, dim=1), torch.cat(cand_i, dim=1)
-                    v_, pos = topk_stable(cv, k, return_values=True)
-                    cand_v, cand_i = [v_], [torch.gather(ci, 1, pos.long())]
-                out_v.append(cand_v[0])
-                out_i.append(cand_i[0])
-            idx = torch.cat(out_i) if len(out_i) > 1 else out_i[0]
-            return ((torch.cat(out_v) if len(out_v) > 1 else out_v[0]), idx) if return_values else idx
-        idx = torch.empty(m, k, dtype=torch.int32, device=A.device)
-        vals = torch.empty(m, k, dtype=torch.float32, device=A.device) if return_values else None
-        if ex is not None:
-            _lib.check(lib.tmf_predict_topk_exclude_bf16(_lib.ptr(A), _lib.ptr(B), m, n, r, lda, ldb, k, int(bool(clamp_negatives)),
-                                                         ctypes.byref(ex.struct(m)), _lib.ptr(idx), _lib.ptr(vals), _lib.stream_ptr()), lib)
-            return (vals, idx) if return_values else idx
-        _lib.check(lib.tmf_predict_topk_bf16(_lib.ptr(A), _lib.ptr(B), m, n, r, lda, ldb, k, int(bool(clamp_negatives)),
-                                             _lib.ptr(idx), _lib.ptr(vals), _lib.stream_ptr()), lib)
-        return (vals, idx) if return_values else idx
-    A, m, r, lda = _gemm_operand(user_embedding)
-    B, n, rb, ldb = _gemm_operand(item_embedding)
+    bf16 = torch.is_tensor(user_embedding) and torch.is_tensor(item_embedding) and \
+        user_embedding.dtype == torch.bfloat16 and item_embedding.dtype == torch.bfloat16
+    A, m, r, lda = _operand(user_embedding, 8 if bf16 else 4)
+    B, n, rb, ldb = _operand(item_embedding, 8 if bf16 else 4)
     if r != rb:
         raise ValueError(f'embedding widths differ: {r} vs {rb}')
     k = int(k)
     if not 1 <= k <= n:
         raise ValueError(f'k={k} must be in [1, {n}]')
+    ex = None if exclude is None else _exclusion_on(build_exclusion(exclude, m, n), A.device)
+    if bf16 and FUSED_MAX_K_BF16 < k <= FUSED_MAX_K:
+        # The bf16 kernel keeps 256 users' lists in LDS: k <= 32.  Beyond it the fp32 fused kernel (k <= 64) ranks exact fp32
+        # copies of the rows - a bf16 x bf16 product is exact in fp32 either way, the fp32 sums differ in order only.
+        # Costs a transient fp32 copy of the item table (twice its size); when that does not fit the catalog is ranked in windows
+        # of rows (a copy of one window at a time) and the per-window lists are merged (merge_windows).
+        if m == 0:
+            idx = torch.empty(0, k, dtype=torch.int32, device=A.device)
+            return (torch.empty(0, k, dtype=torch.float32, device=A.device), idx) if return_values else idx
+        try:
+            windows = [(0, _upcast_table(B))]
+        except torch.OutOfMemoryError:
+            step = max(k, -(-n // BF16_UPCAST_WINDOWS))
+            windows = [(c0, None) for c0 in range(0, n, step)]
+            if n - windows[-1][0] < k:   # a last window narrower than k joins the one before it
+                windows.pop()
+        out_i, out_v = [], []
+        for b in range(0, m, BF16_UPCAST_USERS):
+            Au = A[b:b + BF16_UPCAST_USERS].float()
+            cand_v, cand_i = [], []
+            for w, (c0, Bf) in enumerate(windows):
+                c1 = windows[w + 1][0] if w + 1 < len(windows) else n
+                v_, i_ = predict_topk(Au, Bf if Bf is not None else B[c0:c1].float(), k, clamp_negatives=clamp_negatives,
+                                      return_values=True, arithmetic='fp32',
+                                      exclude=None if ex is None else ex.shifted(b, c0))
+                cand_v.append(v_)
+                cand_i.append(i_ + c0 if ex is None else torch.where(i_ >= 0, i_ + c0, i_))
+            v_, i_ = cand_v[0], cand_i[0]
+            if len(windows) > 1:
+                v_, i_ = merge_windows(torch.cat(cand_v, dim=1), torch.cat(cand_i, dim=1), k, fill=ex is not None)
+            out_v.append(v_)
+            out_i.append(i_)
+        idx = torch.cat(out_i) if len(out_i) > 1 else out_i[0]
+        return ((torch.cat(out_v) if len(out_v) > 1 else out_v[0]), idx) if return_values else idx
     idx = torch.empty(m, k, dtype=torch.int32, device=A.device)
     vals = torch.empty(m, k, dtype=torch.float32, device=A.device) if return_values else None
-    ex = None if exclude is None else _exclusion_on(build_exclusion(exclude, m, n), A.device)
+
+    def launch(form, ws=None):
+        """tmf_predict_topk_<form>, or its _exclude twin with the exclusion struct; the plane forms take their workspace."""
+        name = {'f32': 'tmf_predict_topk_%sf32', 'bf16': 'tmf_predict_topk_%sbf16', 'split': 'tmf_predict_topk_split_%sf32',
+                'half2': 'tmf_predict_topk_half2_%sf32'}[form] % ('' if ex is None else 'exclude_')
+        args = [_lib.ptr(A), _lib.ptr(B), m, n, r, lda, ldb, k, int(bool(clamp_negatives))]
+        if ex is not None:
+            args.append(ctypes.byref(ex.struct(m)))
+        args += [_lib.ptr(idx), _lib.ptr(vals)]
+        if ws is not None:
+            args += [_lib.ptr(ws), ws.numel()]
+        _lib.check(getattr(lib, name)(*args, _lib.stream_ptr()), lib)   # looked up per call: tests wrap the entry points of lib
+        return (vals, idx) if return_values else idx
+
+    if bf16:
+        return launch('bf16')
     if (arithmetic == 'split' and not split_topk_supported(r, k)) or (arithmetic == 'half2' and not half2_topk_supported(r, k)):
         raise ValueError(f"the plane kernels support widths <= 256 and k <= {SPLIT_MAX_K} ('split') / 32 ('half2') (got {r}, {k})")
+    planes_optional = arithmetic == 'auto'   # 'auto' may fall back to the fp32 kernel (it needs no workspace) when memory is short
     if arithmetic == 'auto':
         # 32 < k <= 40 on tables of width <= 32: the fp32 kernel is the faster one (262144 x 100000, r = 32, k = 40: 43.9 against 38.1 TF;
         # r = 64: 65 against 69, r = 96: 65 against 86, r = 128: 86 against 113, r = 256: 100 against 127)
         planes = split_topk_supported(r, k) and not (k > 32 and r <= 32)
         arithmetic = 'split' if m * n >= SPLIT_MIN_SCORES and planes else 'fp32'
-        planes_optional = True    # 'auto' may fall back to the fp32 kernel (it needs no workspace) when memory is short
-    else:
-        planes_optional = False
     if arithmetic in ('half2', 'split'):
         size = lib.tmf_predict_topk_half2_workspace_bytes if arithmetic == 'half2' else lib.tmf_predict_topk_split_workspace_bytes
-        run = lib.tmf_predict_topk_half2_f32 if arithmetic == 'half2' else lib.tmf_predict_topk_split_f32
-        need = size(n, r)
         try:
-            ws = torch.empty(need, dtype=torch.uint8, device=A.device)
+            ws = torch.empty(size(n, r), dtype=torch.uint8, device=A.device)
         except torch.OutOfMemoryError:
             if not planes_optional:
                 raise
             ws = None   # the planes of the item table (1.5x its size) do not fit: the fp32 MFMA kernel ranks without them
-        if ws is not None and ex is not None:
-            run = lib.tmf_predict_topk_half2_exclude_f32 if arithmetic == 'half2' else lib.tmf_predict_topk_split_exclude_f32
-            _lib.check(run(_lib.ptr(A), _lib.ptr(B), m, n, r, lda, ldb, k, int(bool(clamp_negatives)), ctypes.byref(ex.struct(m)),
-                           _lib.ptr(idx), _lib.ptr(vals), _lib.ptr(ws), need, _lib.stream_ptr()), lib)
-            return (vals, idx) if return_values else idx
         if ws is not None:
-            _lib.check(run(_lib.ptr(A), _lib.ptr(B), m, n, r, lda, ldb, k, int(bool(clamp_negatives)),
-                           _lib.ptr(idx), _lib.ptr(vals), _lib.ptr(ws), need, _lib.stream_ptr()), lib)
-            return (vals, idx) if return_values else idx
-    if ex is not None:
-        _lib.check(lib.tmf_predict_topk_exclude_f32(_lib.ptr(A), _lib.ptr(B), m, n, r, lda, ldb, k, int(bool(clamp_negatives)),
-                                                    ctypes.byref(ex.struct(m)), _lib.ptr(idx), _lib.ptr(vals), _lib.stream_ptr()), lib)
-        return (vals, idx) if return_values else idx
-    _lib.check(lib.tmf_predict_topk_f32(_lib.ptr(A), _lib.ptr(B), m, n, r, lda, ldb, k, int(bool(clamp_negatives)),
-                                        _lib.ptr(idx), _lib.ptr(vals), _lib.stream_ptr()), lib)
-    return (vals, idx) if return_values else idx
+            return launch(arithmetic, ws)
+    return launch('f32')
 
 
 def topk_stable(x, k, clamp_negatives=False, return_values=False, exclude=None, overwrite=False):
     """Row-wise top-k indices (int32) ordered like tf.math.top_k: value desc, ties -> lower index.
     exclude: pairs to leave out (build_exclusion; rows = the rows of x, columns = its columns unless an Exclusion view says
     otherwise): trailing slots past a row's eligible items hold -1 / -inf.  The ranking then works on x itself when ``overwrite``
-    (the clamp and -inf for excluded entries are written into it), on a copy otherwise."""
+    (the clamp and -inf for excluded entries are written into it), on a copy otherwise.  Without exclude x is only read."""
     lib = _lib.get()
-    if exclude is not None:
-        return _topk_stable_exclude(lib, x, k, clamp_negatives, return_values, exclude, overwrite)
     x = _cuda(x, torch.float32)
     squeeze = x.dim() == 1
     if squeeze:
         x = x[None, :]
     if x.stride(1) != 1:
         x = x.contiguous()
+    elif exclude is not None and not overwrite:
+        x = x.clone()
     rows, cols = x.shape
     k = int(k)
     if not 1 <= k <= cols:
         raise ValueError(f'k={k} must be in [1, {cols}]')  # tf.math.top_k raises for k > last dim
+    ex = None if exclude is None else _exclusion_on(build_exclusion(exclude, rows, cols), x.device)
+    run = lib.tmf_topk_stable_f32 if ex is None else lib.tmf_topk_stable_exclude_f32
     idx = torch.empty(rows, k, dtype=torch.int32, device=x.device)
     vals = torch.empty(rows, k, dtype=torch.float32, device=x.device) if return_values else None
     # large k over wide rows goes through a segmented radix sort with a workspace: a bounded number of rows per call
@@ -341,42 +344,11 @@ def topk_stable(x, k, clamp_negatives=False, return_values=False, exclude=None, 
         need = lib.tmf_topk_workspace_bytes(e - b, cols, k)
         if need and (ws is None or ws.numel() < need):
             ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        _lib.check(lib.tmf_topk_stable_f32(_lib.ptr(x[b:e]), e - b, cols, x.stride(0), k, int(bool(clamp_negatives)),
-                                           _lib.ptr(idx[b:e]), _lib.ptr(vals[b:e]) if return_values else None, _lib.ptr(ws),
-                                           ws.numel() if ws is not None else 0, _lib.stream_ptr()), lib)
-    if squeeze:
-        idx = idx[0]
-        vals = vals[0] if return_values else None
-    return (vals, idx) if return_values else idx
-
-
-def _topk_stable_exclude(lib, x, k, clamp_negatives, return_values, exclude, overwrite):
-    x = _cuda(x, torch.float32)
-    squeeze = x.dim() == 1
-    if squeeze:
-        x = x[None, :]
-    if x.stride(1) != 1:
-        x = x.contiguous()
-    elif not overwrite:
-        x = x.clone()
-    rows, cols = x.shape
-    k = int(k)
-    if not 1 <= k <= cols:
-        raise ValueError(f'k={k} must be in [1, {cols}]')
-    ex = _exclusion_on(build_exclusion(exclude, rows, cols), x.device)
-    idx = torch.empty(rows, k, dtype=torch.int32, device=x.device)
-    vals = torch.empty(rows, k, dtype=torch.float32, device=x.device) if return_values else None
-    step = rows if lib.tmf_topk_workspace_bytes(1, cols, k) == 0 else max(1, SORT_MAX_ELEMS // cols)
-    ws = None
-    for b in range(0, rows, step):
-        e = min(b + step, rows)
-        need = lib.tmf_topk_workspace_bytes(e - b, cols, k)
-        if need and (ws is None or ws.numel() < need):
-            ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        _lib.check(lib.tmf_topk_stable_exclude_f32(_lib.ptr(x[b:e]), e - b, cols, x.stride(0), k, int(bool(clamp_negatives)),
-                                                   ctypes.byref(ex.shifted(b).struct(e - b)), _lib.ptr(idx[b:e]),
-                                                   _lib.ptr(vals[b:e]) if return_values else None, _lib.ptr(ws),
-                                                   ws.numel() if ws is not None else 0, _lib.stream_ptr()), lib)
+        args = [_lib.ptr(x[b:e]), e - b, cols, x.stride(0), k, int(bool(clamp_negatives))]
+        if ex is not None:
+            args.append(ctypes.byref(ex.shifted(b).struct(e - b)))
+        _lib.check(run(*args, _lib.ptr(idx[b:e]), _lib.ptr(vals[b:e]) if return_values else None, _lib.ptr(ws),
+                       ws.numel() if ws is not None else 0, _lib.stream_ptr()), lib)
     if squeeze:
         idx = idx[0]
         vals = vals[0] if return_values else None
@@ -405,27 +377,13 @@ RANK_ROW_PAIRS = 16          # include/tmf.h TMF_RANK_ROW_PAIRS: positives per v
 RANK_BLOCK_BYTES = 1 << 30   # score block of the non-fused path (tmf_predict_gemm_f32 + tmf_rank_count_rows_f32)
 
 
-class _Pairs:
-    def __init__(self, indices, values):
-        self.indices, self.values = indices, values
-
-
 def positive_pairs(A, n_users, n_items, device=None):
     """CSR (an Exclusion: sorted, de-duplicated, range-checked) of the held-out positives: the entries of A with a value > 0 -
     recall_at_k's "relevant".  A: SparseInteractions (or indices / values / dense_shape) or a dense [n_users, n_items] table."""
-    if not torch.is_tensor(A) and hasattr(A, 'indices') and hasattr(A, 'values'):
-        idx, val = torch.as_tensor(A.indices), torch.as_tensor(A.values)
-        if device is not None:
-            idx, val = idx.to(device), val.to(device)
-        idx, keep = idx.to(torch.int64).reshape(-1, 2), val.reshape(-1) > 0
-        u, i = idx[:, 0][keep], idx[:, 1][keep]   # column first, mask second (see _hits_and_relevant)
-        return build_exclusion(_Pairs(torch.stack([u, i], 1), torch.ones(u.numel(), device=u.device)), n_users, n_items)
-    D = A if torch.is_tensor(A) else torch.as_tensor(__import__('numpy').asarray(A))
-    if device is not None:
-        D = D.to(device)
-    if D.dim() != 2 or tuple(D.shape) != (int(n_users), int(n_items)):
-        raise ValueError(f'a dense table of positives must be [{n_users}, {n_items}], got {tuple(D.shape)}')
-    return build_exclusion(D > 0, n_users, n_items)
+    n_users, n_items = int(n_users), int(n_items)
+    u, i, _, _ = _decode_table(A, 'positives', device, shape=(n_users, n_items), keep='positive')
+    _check_ids(u, i, n_users, n_items, 'positive')
+    return _pairs_csr(u, i, n_users, n_items)
 
 
 def _csr_rows(rowptr):
@@ -530,8 +488,8 @@ def item_ranks(user_embedding, item_embedding, positives, exclude=None, arithmet
     if not fused:
         _item_ranks_blocks(lib, U, V, pos, ex, vu, vb, vc, ranks)
         return out
-    A, _, _, lda = _gemm_operand(U)
-    B, _, _, ldb = _gemm_operand(V)
+    A, _, _, lda = _operand(U)
+    B, _, _, ldb = _operand(V)
     ws = None
     if arithmetic in ('auto', 'split'):
         if arithmetic == 'split' or vu.numel() * n >= SPLIT_MIN_SCORES:
@@ -615,34 +573,14 @@ def graded_csr(A, n_users, n_items, device=None):
     [n_users, n_items] table.  A dense_shape or a dense shape other than (n_users, n_items) raises ValueError, an id out of range
     IndexError.  On the device the rows are ordered by tmf_csr_build; CPU tables (argument checks, tests) by a stable torch sort."""
     n_users, n_items = int(n_users), int(n_items)
-    if not torch.is_tensor(A) and hasattr(A, 'indices') and hasattr(A, 'values'):
-        shape = getattr(A, 'dense_shape', None)
-        if shape is not None and (int(shape[0]), int(shape[1])) != (n_users, n_items):
-            raise ValueError(f'the test table is {tuple(int(x) for x in shape)}, the model ranks [{n_users}, {n_items}]')
-        idx, val = torch.as_tensor(A.indices), torch.as_tensor(A.values)
-        if device is not None:
-            idx, val = idx.to(device), val.to(device)
-        idx = idx.to(torch.int64).reshape(-1, 2)
-        u, i = idx[:, 0].contiguous(), idx[:, 1].contiguous()   # columns, never masked rows of [nnz, 2] (see _hits_and_relevant)
-        val = val.reshape(-1).to(torch.float32).contiguous()
-    else:
-        D = A if torch.is_tensor(A) else torch.as_tensor(__import__('numpy').asarray(A))
-        if device is not None:
-            D = D.to(device)
-        if D.dim() != 2 or tuple(D.shape) != (n_users, n_items):
-            raise ValueError(f'a dense test table must be [{n_users}, {n_items}], got {tuple(D.shape)}')
-        D = D.to(torch.float32)
-        nz = torch.nonzero(D)
-        u, i = nz[:, 0].contiguous(), nz[:, 1].contiguous()
-        val = D[u, i]
+    u, i, val, stated = _decode_table(A, 'test entries', device, shape=(n_users, n_items))
+    if stated is not None and stated != (n_users, n_items):
+        raise ValueError(f'the test table is {stated}, the model ranks [{n_users}, {n_items}]')
+    u, i, val = u.contiguous(), i.contiguous(), val.to(torch.float32).contiguous()
     if u.numel() != val.numel():
         raise ValueError('indices and values disagree on the number of entries')
     nnz = u.numel()
-    if nnz:
-        if int(u.min()) < 0 or int(u.max()) >= n_users:
-            raise IndexError(f'test user id out of range [0, {n_users})')
-        if int(i.min()) < 0 or int(i.max()) >= n_items:
-            raise IndexError(f'test item id out of range [0, {n_items})')
+    _check_ids(u, i, n_users, n_items, 'test')
     dev = u.device
     if dev.type == 'cuda' and 0 < nnz < 2 ** 31:
         lib = _lib.get()
@@ -685,7 +623,6 @@ def graded_csr(A, n_users, n_items, device=None):
 def dcg_discounts(k, device):
     """log1p(j + 1) / log(2) for slots j = 0 .. k - 1: the expression of MatrixFactorization._dcg_terms, so that every term
     gain / discount is the dense path's term bit for bit."""
-    import numpy as np
     order = torch.arange(1, k + 1, dtype=torch.float32, device=device)
     return torch.log1p(order) / float(np.log(np.float32(2.0)))
 

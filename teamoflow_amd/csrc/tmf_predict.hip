@@ -1039,9 +1039,10 @@ static int launch_predict_topk(const float* A, const float* B, int64_t m, int64_
 }  // namespace tmf
 
 namespace tmf {
-// the checks of tmf_predict_topk_f32 / _exclude_f32 (TMF_OK: go on and launch)
-static int check_predict_topk_args(const float* A, const float* B, int64_t m, int64_t n, int r, int64_t lda, int64_t ldb, int k,
-                                   int32_t* out_idx) {
+// tmf_predict_topk_f32 / _exclude_f32 behind their m == 0 and exclusion-pointer checks: the argument checks and the width ladder
+template <bool EXCL>
+static int predict_topk_f32(const float* A, const float* B, int64_t m, int64_t n, int r, int64_t lda, int64_t ldb, int k,
+                            int clamp_negatives, const tmf_exclusion& ex, int32_t* out_idx, float* out_val, void* stream) {
     TMF_REQUIRE(A && B && out_idx && m > 0 && n > 0 && r > 0, "predict_topk: bad arguments");
     TMF_REQUIRE(lda >= r && ldb >= r && (lda % 4 == 0) && (ldb % 4 == 0) && ((uintptr_t)A % 16 == 0) &&
                     ((uintptr_t)B % 16 == 0), "predict_topk: operands must be 16-byte aligned with ld %% 4 == 0");
@@ -1051,7 +1052,11 @@ static int check_predict_topk_args(const float* A, const float* B, int64_t m, in
         set_error("predict_topk: fused kernel supports k <= %d and n_components <= 256 (got k=%d, r=%d)", FMAXK, k, r);
         return TMF_E_UNSUPPORTED;
     }
-    return TMF_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (r <= 32) return launch_predict_topk<1, EXCL>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
+    if (r <= 64) return launch_predict_topk<2, EXCL>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
+    if (r <= 128) return launch_predict_topk<4, EXCL>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
+    return launch_predict_topk<8, EXCL>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);  // 128 A registers per lane
 }
 }  // namespace tmf
 
@@ -1060,33 +1065,14 @@ extern "C" int tmf_predict_topk_exclude_f32(const float* A, const float* B, int6
                                             int32_t* out_idx, float* out_val, void* stream) {
     if (m == 0) return TMF_OK;
     TMF_REQUIRE(exclude && exclude->rowptr && exclude->cols && exclude->item_base >= 0, "predict_topk_exclude: bad exclusion");
-    if (int rc = tmf::check_predict_topk_args(A, B, m, n, r, lda, ldb, k, out_idx)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const tmf_exclusion& ex = *exclude;
-    if (r <= 32) return tmf::launch_predict_topk<1, true>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
-    if (r <= 64) return tmf::launch_predict_topk<2, true>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
-    if (r <= 128) return tmf::launch_predict_topk<4, true>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
-    return tmf::launch_predict_topk<8, true>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
+    return tmf::predict_topk_f32<true>(A, B, m, n, r, lda, ldb, k, clamp_negatives, *exclude, out_idx, out_val, stream);
 }
 
 extern "C" int tmf_predict_topk_f32(const float* A, const float* B, int64_t m, int64_t n, int r, int64_t lda,
                                     int64_t ldb, int k, int clamp_negatives, int32_t* out_idx, float* out_val,
                                     void* stream) {
     if (m == 0) return TMF_OK;
-    TMF_REQUIRE(A && B && out_idx && m > 0 && n > 0 && r > 0, "predict_topk: bad arguments");
-    TMF_REQUIRE(lda >= r && ldb >= r && (lda % 4 == 0) && (ldb % 4 == 0) && ((uintptr_t)A % 16 == 0) &&
-                    ((uintptr_t)B % 16 == 0), "predict_topk: operands must be 16-byte aligned with ld %% 4 == 0");
-    TMF_REQUIRE(k >= 1 && k <= n, "predict_topk: k=%d must be in [1, n=%lld]", k, (long long)n);
-    TMF_REQUIRE(n < ((int64_t)1 << 31), "predict_topk: too many items");
-    if (k > tmf::FMAXK || r > 256) {
-        tmf::set_error("predict_topk: fused kernel supports k <= %d and n_components <= 256 (got k=%d, r=%d)", tmf::FMAXK, k, r);
-        return TMF_E_UNSUPPORTED;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (r <= 32) return tmf::launch_predict_topk<1>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s);
-    if (r <= 64) return tmf::launch_predict_topk<2>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s);
-    if (r <= 128) return tmf::launch_predict_topk<4>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s);
-    return tmf::launch_predict_topk<8>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s);  // 128 A registers per lane
+    return tmf::predict_topk_f32<false>(A, B, m, n, r, lda, ldb, k, clamp_negatives, tmf_exclusion{}, out_idx, out_val, stream);
 }
 
 // =============================================================================================
@@ -1356,6 +1342,25 @@ static int launch_predict_topk_bf16(const void* A, const void* B, int64_t m, int
     return launch_predict_topk_bf16_impl<NCH, 0, EXCL>(A, B, m, n, K, lda, ldb, k, clamp, out_idx, out_val, ex, stream);
 }
 
+// tmf_predict_topk_bf16 / _exclude_bf16 behind their m == 0 and exclusion-pointer checks
+template <bool EXCL>
+static int predict_topk_bf16(const void* A, const void* B, int64_t m, int64_t n, int r, int64_t lda, int64_t ldb, int k,
+                             int clamp_negatives, const tmf_exclusion& ex, int32_t* out_idx, float* out_val, void* stream) {
+    TMF_REQUIRE(A && B && out_idx && m > 0 && n > 0 && r > 0, "predict_topk_bf16: bad arguments");
+    TMF_REQUIRE(lda >= r && ldb >= r && (lda % 8 == 0) && (ldb % 8 == 0) && ((uintptr_t)A % 16 == 0) &&
+                    ((uintptr_t)B % 16 == 0), "predict_topk_bf16: operands must be 16-byte aligned with ld %% 8 == 0");
+    TMF_REQUIRE(k >= 1 && k <= n, "predict_topk_bf16: k=%d must be in [1, n=%lld]", k, (long long)n);
+    TMF_REQUIRE(n < ((int64_t)1 << 31), "predict_topk_bf16: too many items");
+    if (k > HMAXK || r > 256) {
+        set_error("predict_topk_bf16: supports k <= %d and n_components <= 256 (got k=%d, r=%d)", HMAXK, k, r);
+        return TMF_E_UNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (r <= 64) return launch_predict_topk_bf16<1, EXCL>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
+    if (r <= 128) return launch_predict_topk_bf16<2, EXCL>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
+    return launch_predict_topk_bf16<4, EXCL>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
+}
+
 }  // namespace tmf
 
 extern "C" int tmf_predict_topk_exclude_bf16(const void* A, const void* B, int64_t m, int64_t n, int r, int64_t lda,
@@ -1363,37 +1368,12 @@ extern "C" int tmf_predict_topk_exclude_bf16(const void* A, const void* B, int64
                                              int32_t* out_idx, float* out_val, void* stream) {
     if (m == 0) return TMF_OK;
     TMF_REQUIRE(exclude && exclude->rowptr && exclude->cols && exclude->item_base >= 0, "predict_topk_exclude_bf16: bad exclusion");
-    TMF_REQUIRE(A && B && out_idx && m > 0 && n > 0 && r > 0, "predict_topk_bf16: bad arguments");
-    TMF_REQUIRE(lda >= r && ldb >= r && (lda % 8 == 0) && (ldb % 8 == 0) && ((uintptr_t)A % 16 == 0) &&
-                    ((uintptr_t)B % 16 == 0), "predict_topk_bf16: operands must be 16-byte aligned with ld %% 8 == 0");
-    TMF_REQUIRE(k >= 1 && k <= n, "predict_topk_bf16: k=%d must be in [1, n=%lld]", k, (long long)n);
-    TMF_REQUIRE(n < ((int64_t)1 << 31), "predict_topk_bf16: too many items");
-    if (k > tmf::HMAXK || r > 256) {
-        tmf::set_error("predict_topk_bf16: supports k <= %d and n_components <= 256 (got k=%d, r=%d)", tmf::HMAXK, k, r);
-        return TMF_E_UNSUPPORTED;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const tmf_exclusion& ex = *exclude;
-    if (r <= 64) return tmf::launch_predict_topk_bf16<1, true>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
-    if (r <= 128) return tmf::launch_predict_topk_bf16<2, true>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
-    return tmf::launch_predict_topk_bf16<4, true>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s, ex);
+    return tmf::predict_topk_bf16<true>(A, B, m, n, r, lda, ldb, k, clamp_negatives, *exclude, out_idx, out_val, stream);
 }
 
 extern "C" int tmf_predict_topk_bf16(const void* A, const void* B, int64_t m, int64_t n, int r, int64_t lda,
                                      int64_t ldb, int k, int clamp_negatives, int32_t* out_idx, float* out_val,
                                      void* stream) {
     if (m == 0) return TMF_OK;
-    TMF_REQUIRE(A && B && out_idx && m > 0 && n > 0 && r > 0, "predict_topk_bf16: bad arguments");
-    TMF_REQUIRE(lda >= r && ldb >= r && (lda % 8 == 0) && (ldb % 8 == 0) && ((uintptr_t)A % 16 == 0) &&
-                    ((uintptr_t)B % 16 == 0), "predict_topk_bf16: operands must be 16-byte aligned with ld %% 8 == 0");
-    TMF_REQUIRE(k >= 1 && k <= n, "predict_topk_bf16: k=%d must be in [1, n=%lld]", k, (long long)n);
-    TMF_REQUIRE(n < ((int64_t)1 << 31), "predict_topk_bf16: too many items");
-    if (k > tmf::HMAXK || r > 256) {
-        tmf::set_error("predict_topk_bf16: supports k <= %d and n_components <= 256 (got k=%d, r=%d)", tmf::HMAXK, k, r);
-        return TMF_E_UNSUPPORTED;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (r <= 64) return tmf::launch_predict_topk_bf16<1>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s);
-    if (r <= 128) return tmf::launch_predict_topk_bf16<2>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s);
-    return tmf::launch_predict_topk_bf16<4>(A, B, m, n, r, lda, ldb, k, clamp_negatives, out_idx, out_val, s);
+    return tmf::predict_topk_bf16<false>(A, B, m, n, r, lda, ldb, k, clamp_negatives, tmf_exclusion{}, out_idx, out_val, stream);
 }

@@ -442,29 +442,18 @@ def sharded_top_items(model, k, clamp_negatives=False, users=None, exclude=None)
             continue
         kt = min(int(k), valid)
         W = Vwin[:valid, :r]
-        if ex is not None:
-            exw = ex.shifted(0, t * be.rows)
-            if _ops.fused_topk_supported(U, W, kt):
-                v, i = _ops.predict_topk(U, W, kt, clamp_negatives=clamp_negatives, return_values=True, exclude=exw)
-            else:
-                v, i = _ops.topk_stable(_ops.predict_gemm(U.float(), W.float()), kt, clamp_negatives=clamp_negatives,
-                                        return_values=True, exclude=exw, overwrite=True)
-            vals.append(v)
-            ids.append(torch.where(i >= 0, i + t * be.rows, i))
-            continue
+        exw = None if ex is None else ex.shifted(0, t * be.rows)
         if _ops.fused_topk_supported(U, W, kt):
-            v, i = _ops.predict_topk(U, W, kt, clamp_negatives=clamp_negatives, return_values=True)
+            v, i = _ops.predict_topk(U, W, kt, clamp_negatives=clamp_negatives, return_values=True, exclude=exw)
         else:
-            v, i = _ops.topk_stable(_ops.predict_gemm(U.float(), W.float()), kt, clamp_negatives=clamp_negatives, return_values=True)
+            v, i = _ops.topk_stable(_ops.predict_gemm(U.float(), W.float()), kt, clamp_negatives=clamp_negatives,
+                                    return_values=True, exclude=exw, overwrite=True)
         vals.append(v)
-        ids.append(i + t * be.rows)
+        ids.append(i + t * be.rows if ex is None else torch.where(i >= 0, i + t * be.rows, i))   # -1 fill entries stay -1
     if not vals:
         return torch.zeros(U.shape[0], 0, dtype=torch.int32, device=be.U.device)
     cv, ci = torch.cat(vals, dim=1), torch.cat(ids, dim=1)
-    if ex is not None:
-        return _ops.merge_lists(cv, ci, min(int(k), cv.shape[1]))[1]   # window values are clamped already; -1 entries go last
-    pos = _ops.topk_stable(cv, min(int(k), cv.shape[1]), clamp_negatives=clamp_negatives)
-    return torch.gather(ci, 1, pos.to(torch.int64))
+    return _ops.merge_windows(cv, ci, min(int(k), cv.shape[1]), fill=ex is not None, return_values=False)[1]
 
 
 def gather_item_embedding(model, n_items, group=None):

@@ -320,8 +320,7 @@ class MatrixFactorization:
     # ------------------------------------------------------------------------------------------
     def predict(self, A=None):
         """:189-201.  All scores [n_users, n_items]; with A also the scores where A == 0 (row-major)."""
-        ep = getattr(self, '_sharded_epoch', None)
-        if ep is not None and ep.world > 1:
+        if self._item_sharded():
             raise NotImplementedError('item-row-sharded fit: this rank holds only its item rows, the dense [n_users, n_items] score '
                                       'matrix is not available; recall_at_k / precision_at_k / retrieve_user_recs rank over the '
                                       'windows (dist.sharded_top_items), dist.gather_item_embedding assembles the table where it fits')
@@ -341,102 +340,68 @@ class MatrixFactorization:
         rows = max(1, min(m, PREDICT_CHUNK_BYTES // (4 * max(n, 1))))
         return [(b, min(b + rows, m)) for b in range(0, m, rows)]
 
+    def _item_sharded(self):
+        """An item-row-sharded fit over several ranks: item_embedding holds only this rank's rows."""
+        ep = getattr(self, '_sharded_epoch', None)
+        return ep is not None and ep.world > 1
+
     def _exclusion(self, exclude):
         """exclude (SparseInteractions, a dense table or an _ops.Exclusion; rows = this model's users) as a device CSR."""
-        ep = getattr(self, '_sharded_epoch', None)
-        n_items = self._n_items_fit if ep is not None and ep.world > 1 else self.item_embedding.shape[0]
+        n_items = self._n_items_fit if self._item_sharded() else self.item_embedding.shape[0]
         return _ops.build_exclusion(exclude, self.user_embedding.shape[0], n_items, device=self.user_embedding.device)
 
     def _top_items(self, k, clamp, users=None, exclude=None):
         """Top-k item ids (int32) for every user, scored block by block: the [m, n] matrix is only
         ever materialised one block of users at a time.  exclude: pairs left out of the ranking (-1 past a user's
         eligible items)."""
-        if exclude is not None:
-            return self._top_items_exclude(k, clamp, users, self._exclusion(exclude))
-        ep = getattr(self, '_sharded_epoch', None)
-        if ep is not None and ep.world > 1:
-            # item-row-sharded fit: item_embedding holds only this rank's rows - rank over the windows (a collective)
-            from .. import dist as tdist
-            top = tdist.sharded_top_items(self, k, clamp, users=users)
-            return top[0] if users is not None else top
-        if users is not None:
-            scores = _ops.predict_gemm(self.user_embedding[users:users + 1], self.item_embedding)
-            return _ops.topk_stable(scores, k, clamp_negatives=clamp)[0]
-        if _ops.fused_topk_supported(self.user_embedding, self.item_embedding, k):
-            return _ops.predict_topk(self.user_embedding, self.item_embedding, k, clamp_negatives=clamp,
-                                     arithmetic=getattr(self, 'predict_arithmetic', None))
-        out = []
-        for b, e in self._user_blocks():
-            scores = _ops.predict_gemm(self.user_embedding[b:e], self.item_embedding)
-            out.append(_ops.topk_stable(scores, k, clamp_negatives=clamp))
-        return torch.cat(out) if len(out) > 1 else out[0]
-
-    def _top_items_exclude(self, k, clamp, users, ex):
-        ep = getattr(self, '_sharded_epoch', None)
-        if ep is not None and ep.world > 1:
+        ex = None if exclude is None else self._exclusion(exclude)
+        if self._item_sharded():
+            # item_embedding holds only this rank's rows - rank over the windows (a collective)
             from .. import dist as tdist
             top = tdist.sharded_top_items(self, k, clamp, users=users, exclude=ex)
             return top[0] if users is not None else top
+
+        def ranked(b, e):   # users [b, e) through their block of scores; the exclusion is written into the block
+            scores = _ops.predict_gemm(self.user_embedding[b:e], self.item_embedding)
+            return _ops.topk_stable(scores, k, clamp_negatives=clamp, exclude=None if ex is None else ex.shifted(b), overwrite=True)
+
         if users is not None:
-            scores = _ops.predict_gemm(self.user_embedding[users:users + 1], self.item_embedding)
-            return _ops.topk_stable(scores, k, clamp_negatives=clamp, exclude=ex.shifted(users), overwrite=True)[0]
+            return ranked(users, users + 1)[0]
         if _ops.fused_topk_supported(self.user_embedding, self.item_embedding, k):
             return _ops.predict_topk(self.user_embedding, self.item_embedding, k, clamp_negatives=clamp,
                                      arithmetic=getattr(self, 'predict_arithmetic', None), exclude=ex)
-        out = []
-        for b, e in self._user_blocks():
-            scores = _ops.predict_gemm(self.user_embedding[b:e], self.item_embedding)
-            out.append(_ops.topk_stable(scores, k, clamp_negatives=clamp, exclude=ex.shifted(b), overwrite=True))
+        out = [ranked(b, e) for b, e in self._user_blocks()]
         return torch.cat(out) if len(out) > 1 else out[0]
 
     def _hits_and_relevant(self, A, k, exclude=None):
         """hits[u] = #top-k items with a non-zero entry in A, relevant[u] = #entries of A > 0
         (:245-254).  A: dense [m, n] tensor, or SparseInteractions (extension for shapes whose dense
-        table does not fit)."""
+        table does not fit).  With exclude the lists may end in -1 (fewer eligible items than k): those slots are never hits."""
         top = self._top_items(k, clamp=True, exclude=exclude)
+        valid = None
         if exclude is not None:
-            return self._hits_and_relevant_padded(A, top)
+            valid = top >= 0
+            top = torch.where(valid, top, torch.zeros_like(top))   # a gatherable id in the fill slots, masked out below
+        top = top.to(torch.int64)
         if isinstance(A, SparseInteractions):
             A = A.to(top.device)
             m, n = A.dense_shape
             nz = A.values != 0
-            # column first, mask second: masked ROW selection of a [nnz, 2] tensor is unreliable beyond ~6e7 rows on this
-            # PyTorch-ROCm build (tools/torch_row_index_probe.py)
+            # column first, mask second (see _ops._decode_table)
             keys = A.indices[:, 0][nz] * n + A.indices[:, 1][nz]
             if keys.numel() > 1 and not bool((keys[1:] >= keys[:-1]).all()):   # row-major input (the reference's format) is sorted already
                 keys = torch.sort(keys)[0]
-            q = torch.arange(m, device=top.device)[:, None] * n + top.to(torch.int64)
-            pos = torch.clamp(torch.searchsorted(keys, q.reshape(-1)), max=max(keys.numel() - 1, 0))
-            found = (keys[pos] == q.reshape(-1)).reshape(q.shape) if keys.numel() else torch.zeros_like(q, dtype=torch.bool)
-            hits = found.sum(dim=1).to(torch.float32)
-            relevant = torch.bincount(A.indices[:, 0][A.values > 0], minlength=m).to(torch.float32)
-            return hits, relevant
-        A = torch.as_tensor(A).to(device=top.device, dtype=torch.float32)
-        res_top_k = gather_matrix_indices(A, top.to(torch.int64))
-        hits = torch.count_nonzero(res_top_k, dim=1).to(torch.float32)
-        relevant = torch.count_nonzero(A > 0.0, dim=1).to(torch.float32)
-        return hits, relevant
-
-    def _hits_and_relevant_padded(self, A, top):
-        """_hits_and_relevant for lists that may end in -1 (fewer eligible items than k): those slots are never hits."""
-        valid = top >= 0
-        top = torch.where(valid, top, torch.zeros_like(top)).to(torch.int64)
-        if isinstance(A, SparseInteractions):
-            A = A.to(top.device)
-            m, n = A.dense_shape
-            nz = A.values != 0
-            keys = torch.sort(A.indices[:, 0][nz] * n + A.indices[:, 1][nz])[0]
             q = (torch.arange(m, device=top.device)[:, None] * n + top).reshape(-1)
             pos = torch.clamp(torch.searchsorted(keys, q), max=max(keys.numel() - 1, 0))
             found = (keys[pos] == q).reshape(top.shape) if keys.numel() else torch.zeros_like(top, dtype=torch.bool)
-            hits = (found & valid).sum(dim=1).to(torch.float32)
             relevant = torch.bincount(A.indices[:, 0][A.values > 0], minlength=m).to(torch.float32)
-            return hits, relevant
-        A = torch.as_tensor(A).to(device=top.device, dtype=torch.float32)
-        res_top_k = gather_matrix_indices(A, top)
-        hits = torch.count_nonzero((res_top_k != 0) & valid, dim=1).to(torch.float32)
-        relevant = torch.count_nonzero(A > 0.0, dim=1).to(torch.float32)
-        return hits, relevant
+        else:
+            A = torch.as_tensor(A).to(device=top.device, dtype=torch.float32)
+            found = gather_matrix_indices(A, top) != 0
+            relevant = torch.count_nonzero(A > 0.0, dim=1).to(torch.float32)
+        if valid is not None:
+            found = found & valid
+        return found.sum(dim=1).to(torch.float32), relevant
 
     def recall_at_k(self, A, k=10, preserve_rows=False, *, exclude=None):
         """:218-269.  Per-user hits@k / #positives; the caller takes the mean.  exclude (extension, LightFM's
@@ -482,8 +447,7 @@ class MatrixFactorization:
     def _dcg_setup(self, A, k, exclude):
         """(graded test table, effective k, exclusion or None, zero gains per user or None) of the sparse DCG path, every argument
         checked before anything is launched."""
-        ep = getattr(self, '_sharded_epoch', None)
-        if ep is not None and ep.world > 1:
+        if self._item_sharded():
             raise NotImplementedError('item-row-sharded fit: this rank holds only its item rows; dcg / idcg / ndcg need every window '
                                       '(dist.gather_item_embedding assembles the table where it fits)')
         k = int(k)
@@ -546,8 +510,7 @@ class MatrixFactorization:
 
     def _rank_pairs(self, A, exclude):
         """(positives' CSR rowptr, cols, int32 ranks, exclusion CSR or None) of item_ranks."""
-        ep = getattr(self, '_sharded_epoch', None)
-        if ep is not None and ep.world > 1:
+        if self._item_sharded():
             raise NotImplementedError('item-row-sharded fit: this rank holds only its item rows; full-catalog ranks need every '
                                       'window (dist.gather_item_embedding assembles the table where it fits)')
         ex = None if exclude is None else self._exclusion(exclude)
@@ -624,8 +587,7 @@ class MatrixFactorization:
         plug-ins are stored as plain data (class name + constructor state), so the file loads with
         ``torch.load(weights_only=True)``; a user-defined plug-in object can only be stored pickled
         (``allow_pickle=True`` here AND in ``load``).  ``include_samples=False`` leaves the [m, S] negative table out."""
-        ep = getattr(self, '_sharded_epoch', None)
-        if ep is not None and ep.world > 1:
+        if self._item_sharded():
             raise ValueError('item-row-sharded model: this rank holds users %s and %d of the item rows only - assemble the tables '
                              'first (dist.gather_user_embedding / gather_item_embedding) or save one file per rank from them'
                              % (self.user_block, int(self.item_rows.numel())))
