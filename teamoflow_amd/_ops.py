@@ -43,6 +43,12 @@ def predict_gemm(user_embedding, item_embedding, out=None):
         raise ValueError(f'embedding widths differ: {r} vs {rb}')
     if out is None:
         out = torch.empty(m, n, dtype=torch.float32, device=A.device)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (m, n)
+              and out.stride(1) == 1 and out.stride(0) >= n):
+        # out.stride(0) is the ldc the kernel writes with: anything else would be written past its rows or as another type
+        raise ValueError(f'out must be a CUDA float32 [{m}, {n}] tensor with unit column stride and a row stride >= {n}, got '
+                         + (f'{out.dtype} {tuple(out.shape)} on {out.device}, strides {tuple(out.stride())}' if torch.is_tensor(out)
+                            else type(out).__name__))
     _lib.check(lib.tmf_predict_gemm_f32(_lib.ptr(A), _lib.ptr(B), _lib.ptr(out), m, n, r, lda, ldb, out.stride(0),
                                         _lib.stream_ptr()), lib)
     return out

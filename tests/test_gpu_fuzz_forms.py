@@ -96,8 +96,15 @@ def test_random_forms_against_the_closed_form(eng, monkeypatch, seed):
     gV = torch.full((n, st.ld), 7.0, device=dev)
     eng.epoch_wmrb(st, adam, n / S, loss, item_epi=_lib.EPI_GRAD, item_out=gV, user_epi=_lib.EPI_GRAD, user_out=gU)
     loss2 = torch.zeros(1, dtype=torch.float64, device=dev)
+    st.U_nxt.fill_(float('nan'))   # what the updated tables hold afterwards - pad columns included - is what this epoch wrote
+    st.V_nxt.fill_(float('nan'))
     eng.epoch_wmrb(st, adam, n / S, loss2)
     torch.cuda.synchronize()
+    # include/tmf.h: the columns [n_components, ld) of a factor table are zero and stay zero - fp32 and bf16 storage, every form
+    assert st.ld >= r and st.U_nxt.shape == (m, st.ld) and st.V_nxt.shape == (n, st.ld), what
+    assert not bool(st.U_nxt[:, r:].any()) and not bool(st.V_nxt[:, r:].any()), what
+    assert not bool(st.U[:, r:].any()) and not bool(st.V[:, r:].any()), what                 # the tables read are left as they were
+    assert bool(torch.isfinite(st.U_nxt.float()).all()) and bool(torch.isfinite(st.V_nxt.float()).all()), what   # every row was written
     U64, V64 = st.U[:, :r].double().cpu().numpy(), st.V[:, :r].double().cpu().numpy()   # the tables as stored (bf16: rounded)
     v64, R64 = val.astype(np.float64), R.astype(np.int64)
     _, _, mean, t = SR.wmrb_epoch(U64, V64, idx, v64, R64, n, S, lr)
@@ -118,6 +125,11 @@ def test_random_forms_against_the_closed_form(eng, monkeypatch, seed):
         assert_step(st.V_nxt[:, :r].cpu().numpy(), V64, t['gV'], lr, rtol=rtol, what=f'V {what}', slack=sl['gV'] + fV)
     # the pad columns of the raw gradients stay what the kernels define them to be: never NaN
     assert torch.isfinite(gU).all() and torch.isfinite(gV).all(), what
+    # What they hold: exact zeros - every form's TMF_EPI_GRAD epilogue stores the whole [rows, ld] row, so the 7.0 the buffers were
+    # filled with is gone from columns [r, ld) as well (seen for r = 24, 100, 160 in both storage types; the other widths have no pad
+    # columns).  A zero pad gradient is what tmf_adam_fresh_rows / tmf_adam_state_rows, which step all ld columns, need to keep the
+    # tables' pad columns zero.
+    assert not bool(gU[:, r:].any()) and not bool(gV[:, r:].any()), what
 
 
 def draw_medium(seed):

@@ -207,9 +207,28 @@ def test_every_rank_geometry_mse_and_wmrb(tm, r):
     V0 = (rng.standard_normal((n, r)) * 0.3).astype(np.float32)
     R = np.stack([rng.choice(n, S_, replace=False) for _ in range(m)])
     lr = 0.01
-    check_one_step(tm, U0, V0, idx, val, (m, n), lr)
+    e, _ = check_one_step(tm, U0, V0, idx, val, (m, n), lr)
     w, t = check_one_step(tm, U0, V0, idx, val, (m, n), lr, 'wmrb', R, n, S_)
     assert rel_err(w._state.wplan.D_in_model_order().cpu().numpy(), t['D']) < 1e-5
+    # include/tmf.h: columns [n_components, ld) of the factor tables are zero and stay zero - the tables a fit leaves behind (the
+    # kernels wrote them into torch.empty storage) and the ones it read, fp32 storage above and bf16 storage below
+    models = [e, w]
+    for loss in ('mse', 'wmrb'):
+        kw = dict(user_weight_graph=tm.Fixed(U0), item_weight_graph=tm.Fixed(V0))
+        if loss == 'wmrb':
+            kw.update(loss_graph=tm.WMRB(), n_users=m, n_items=n, n_samples=S_)
+        b = tm.MF(r, **kw)
+        b.random_ind, b.verbose, b.factor_dtype = torch.as_tensor(R), False, torch.bfloat16
+        b.fit(2, tm.eye(m), tm.eye(n), tm.Sparse(idx, val, (m, n)), lr=lr)
+        assert b._state.dtype is torch.bfloat16 and np.isfinite(b.loss_history_).all()
+        models.append(b)
+    for model in models:
+        st = model._state
+        assert st.ld == tm.lib.padded_ld(r, st.dtype) >= r
+        for W, rows in ((st.U, m), (st.V, n), (st.U_nxt, m), (st.V_nxt, n)):
+            assert W.shape == (rows, st.ld) and W.dtype is st.dtype
+            assert not bool(W[:, r:].any()), (r, st.ld, str(st.dtype))
+        assert model.user_embedding.data_ptr() == st.U.data_ptr() and model.item_embedding.data_ptr() == st.V.data_ptr()
 
 
 @pytest.mark.parametrize('dtype', ['f32', 'bf16'])
