@@ -407,9 +407,7 @@ __device__ __forceinline__ void store_row(const Frag<NV>& f, __bf16* __restrict_
 // Partial rows (slab slots, per-slice layers) are written once and read once by the kernel that sums them: that read carries the
 // non-temporal hint too (combine 1.42 -> 1.30 ms, finish 1.30 -> 1.28 at C4; the same hint on slice offsets or on the hinge
 // kernel's score loads changed nothing, on the item pass's entry lists it cost 2 ms - profiles/r03_c5_experiments.txt item 10).
-#ifndef TMF_NT_FIN
-#define TMF_NT_FIN 1
-#endif
+constexpr bool kNtFin = true;
 template <int G, int NV, typename T, bool NT = false>
 __device__ __forceinline__ void load_row_f32(Frag<NV>& f, const float* __restrict__ B, int64_t row, int g) {
     const float* p = B + row * (int64_t)(4 * G * NV);

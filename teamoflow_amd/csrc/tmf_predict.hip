@@ -447,10 +447,7 @@ constexpr int FBM = 128, FBN = 128, FBK = 32, FLD = FBN + 1, FCAP = 16, FMAXK = 
 constexpr int FCAND_PEND = 0, FCAND_INS = 1, FCAND_MERGE = 2;   // candidate handling of k_predict_topk: pending buffers + rare one-lane merges,
                                                                 // immediate 64-lane insertion, or pending buffers + wave-wide bitonic merges
 constexpr int FPC = 32;   // FCAND_MERGE: pending entries per row
-#ifndef TMF_FPT
-#define TMF_FPT 24
-#endif
-constexpr int FPT = TMF_FPT;   // ... and the fill from which a row is merged after a tile (a 16-column group of the overflow path: FPC / 2)
+constexpr int FPT = 24;   // ... and the fill from which a row is merged after a tile (a 16-column group of the overflow path: FPC / 2)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // MODE 2: K % 4 == 0 and V < 4 GB (buffer loads, constant per-thread offsets), 1: K % 4 == 0 (branch-free), 0: any K

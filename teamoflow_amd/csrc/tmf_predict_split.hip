@@ -321,10 +321,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void k_predict_topk
     // bound of the row's final k-th value.  The scan then restarts at tile 0 with every threshold just below that bound:
     // the rows skip the phase in which nearly every score is a candidate (half of all k (1 + ln(n / k)) insertions of a row
     // fall into its first ~5 tiles) for warm / ntiles (<= 1/64) more MFMA work.
-#ifndef TMF_SPLIT_WARM_MAXK
-#define TMF_SPLIT_WARM_MAXK 32   /* round 4: 24 -> 32 (k = 25: 130.7 -> 134.6 TF, k = 28: 119.6 -> 123.6, k = 32 unchanged; same box) */
-#endif
-    const int warm = (k <= TMF_SPLIT_WARM_MAXK && ntiles >= 256) ? (ntiles / 64 < 128 ? ntiles / 64 : 128) : 0;
+    constexpr int kWarmMaxK = 32;   // round 4: 24 -> 32 (k = 25: 130.7 -> 134.6 TF, k = 28: 119.6 -> 123.6, k = 32 unchanged; same box)
+    const int warm = (k <= kWarmMaxK && ntiles >= 256) ? (ntiles / 64 < 128 ? ntiles / 64 : 128) : 0;
     const int warm_chunks = warm * NCH;
     const int64_t plane = n_pad * LDP;
     auto g_issue = [&](int g, int slot) {   // chunk g -> ring slot `slot` (three LDS-DMA loads per wave)
@@ -553,16 +551,13 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void k_predict_topk
 static int64_t split_rows_pad(int64_t n) { return (n + kSplitRowsPad - 1) / kSplitRowsPad * kSplitRowsPad; }
 static int split_ldp(int r) { return r <= 32 ? 32 : r <= 64 ? 64 : r <= 128 ? 128 : 256; }
 
-#ifndef TMF_SPLIT_LDS_PAD
-#define TMF_SPLIT_LDS_PAD 0   /* timing-only: LDS bytes asked for beyond what the kernel uses (45000: one 4-wave workgroup per CU) */
-#endif
 template <int NJ, int KS, int NCH, int WAVES, bool HALF2, bool EXCL>
 static int launch_predict_topk_split_w(const float* A, const uint16_t* Bp, int64_t m, int64_t n, int64_t n_pad, int K, int64_t lda,
                                        int k, int clamp, int32_t* out_idx, float* out_val, const float* item_scale, const tmf_exclusion& ex,
                                        hipStream_t stream) {
     constexpr int SBM = 32 * WAVES, SRING = split_ring(WAVES, HALF2), NP = HALF2 ? 2 : 3;
     const size_t lds = (size_t)SRING * NP * (32 * NJ) * (32 * KS) + 3 * sizeof(float) * SBM + 8 * (size_t)split_cap(WAVES, k) * SBM +
-                       8 * (size_t)k * SBM + TMF_SPLIT_LDS_PAD;
+                       8 * (size_t)k * SBM;
     if (lds > kSplitMaxLds) {   // never launched: more LDS than a CU has
         set_error("predict_topk_split: %d-wave workgroup at k=%d needs %zu bytes of LDS (a CU has %zu)", WAVES, k, lds, kSplitMaxLds);
         return TMF_E_UNSUPPORTED;

@@ -11,10 +11,7 @@ namespace tmf {
 
 constexpr int kWavesPerBlock = 2;   // independent waves, no barrier; 2 per workgroup measured best (C4 item pass 32.1 ms; 4: 32.5, 8: 36.6; MSE epoch 11.1 vs 11.45)
 constexpr int kUnroll = 4;          // list entries a group keeps in flight
-#ifndef TMF_MSE_UNROLL
-#define TMF_MSE_UNROLL 4
-#endif
-constexpr int kMseUnroll = TMF_MSE_UNROLL;   // the same for k_mse_pass (A/B builds)
+constexpr int kMseUnroll = 4;       // the same for k_mse_pass
 constexpr int64_t kMaxBlocks = ((int64_t)1 << 32) / (64 * kWavesPerBlock) - 1;   // workgroups of one launch: < 2^32 work-items
 
 struct SegView {
@@ -107,23 +104,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_mse_pass(
 // neighbouring lists are served by ONE L2 - changed nothing: 32.8 vs 32.6 ms at C4, profiles/r02_hinge_rewrite.txt.)
 // ---------------------------------------------------------------------------------------------
 constexpr int kWsumTile = 512;  // entries a wave stages in LDS per step (ids + weights: 4 KB per wave)
-#ifndef TMF_WSUM_VARIANT
-#define TMF_WSUM_VARIANT 0   // 1 / 2: timing-only builds that split the item pass's time (tools/build_variant.sh; profiles/r05_item_pass_split.txt)
-#endif
-#ifndef TMF_WSUM_OCC
-#define TMF_WSUM_OCC   // e.g. -DTMF_WSUM_OCC='__attribute__((amdgpu_waves_per_eu(8,8)))' for an occupancy experiment
-#endif
-#ifndef TMF_WSUM_INNER
-// 0 (default): scalar LDS reads and a branch around the load of a zero-weight row; 1: gradu3's form - the four ids / weights of a
-// step in one ds_read_b128 each, a select to a resident row instead of the branch.  Same box, C4 fp32 item pass (two runs each,
-// profiles/r05_item_pass_split.txt): 0 -> 30.40 / 30.40 ms, 1 -> 31.52 / 31.52 ms.  The form with fewer instructions is slower,
-// as the leaner walks of round 4 were: the pass is bound by the rows' way through the texture addresser / L1 (20.4 ms with
-// every row an L1 hit and no weight gather) and by the fabric traffic of the 4-byte weight gathers (+7 ms), not by issue.
-#define TMF_WSUM_INNER 0
-#endif
-#ifndef TMF_WSUM_UNROLL
-#define TMF_WSUM_UNROLL 4    // rows a lane group keeps in flight in k_wsum_pass_pg (A/B builds)
-#endif
+// Inner loop of k_wsum_pass_pg: scalar LDS reads and a branch around the load of a zero-weight row.  gradu3's form - the four ids /
+// weights of a step in one ds_read_b128 each, a select to a resident row instead of the branch - was measured on the same box, C4
+// fp32 item pass (two runs each, profiles/r05_item_pass_split.txt): this form 30.40 / 30.40 ms, gradu3's 31.52 / 31.52 ms.  The
+// form with fewer instructions is slower, as the leaner walks of round 4 were: the pass is bound by the rows' way through the
+// texture addresser / L1 (20.4 ms with every row an L1 hit and no weight gather) and by the fabric traffic of the 4-byte weight
+// gathers (+7 ms), not by issue.  That loop, and the timing-only builds that split the pass's time this way, are in
+// profiles/build_time_variants.patch.
+constexpr int kWsumUnroll = 4;  // rows a lane group keeps in flight in k_wsum_pass_pg
 
 template <int G, int NV, typename T>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void k_wsum_pass(
@@ -193,11 +181,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_wsum_pass(
 // 32.6 ms, C4 bf16 27.8 -> 25.0 ms.  Used for rows of 16 lanes or more (narrower rows would leave each group a tile of
 // a few dozen staged entries); TMF_WSUM_PER_GROUP=0 selects k_wsum_pass for A/B runs.
 template <int G, int NV, typename T>
-__global__ __launch_bounds__(64 * kWavesPerBlock) TMF_WSUM_OCC void k_wsum_pass_pg(
+__global__ __launch_bounds__(64 * kWavesPerBlock) void k_wsum_pass_pg(
     SegView sv, const int32_t* __restrict__ ent_row, const int32_t* __restrict__ ent_w,
     const float* __restrict__ wbuf, const T* __restrict__ Tab, const T* __restrict__ X_old,
     void* __restrict__ X_out, float* __restrict__ slab, int epi, tmf_adam adam) {
-    constexpr int NG = 64 / G, TILE = kWsumTile / NG, kWsumUnroll = TMF_WSUM_UNROLL;
+    constexpr int NG = 64 / G, TILE = kWsumTile / NG;
     __shared__ __attribute__((aligned(16))) int s_ids[kWavesPerBlock][kWsumTile];
     __shared__ __attribute__((aligned(16))) float s_w[kWavesPerBlock][kWsumTile];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -230,22 +218,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) TMF_WSUM_OCC void k_wsum_pass_
     for (int64_t t0 = beg; t0 < end; t0 += TILE) {
         const int cnt = (int)((end - t0 < TILE) ? end - t0 : TILE);
         for (int e = g; e < cnt; e += G) {   // (non-temporal loads of the entry lists were measured: 30.65 -> 32.7 ms; not used)
-#if TMF_WSUM_VARIANT == 1   // timing only: weight derived from the streamed entry, no 4-byte gather
-            ids[e] = ent_row[t0 + e];
-            ws[e] = __int_as_float(0x3f800000 | (ent_w[t0 + e] & 0xffff));
-#elif TMF_WSUM_VARIANT == 2   // timing only: sixteen L1-resident rows, no row gather from the L2s
-            ids[e] = ent_row[t0 + e] & 15;
-            ws[e] = wbuf[ent_w[t0 + e]];
-#elif TMF_WSUM_VARIANT == 3   // timing only: neither gather - streams, LDS, arithmetic and the partial-row stores remain
-            ids[e] = ent_row[t0 + e] & 15;
-            ws[e] = __int_as_float(0x3f800000 | (ent_w[t0 + e] & 0xffff));
-#else
             ids[e] = ent_row[t0 + e];
             ws[e] = wbuf[ent_w[t0 + e]];
-#endif
         }
         wave_lds_sync();
-#if TMF_WSUM_INNER == 0
         for (int e0 = 0; e0 < cnt; e0 += kWsumUnroll) {
             Raw<NV, T> raw[kWsumUnroll];
             float wc[kWsumUnroll];
@@ -267,33 +243,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) TMF_WSUM_OCC void k_wsum_pass_
                 axpy<NV>(acc, wc[t], y);
             }
         }
-#else
-        // the four ids and the four weights of a step in ONE LDS read each (16-byte aligned tile, e0 % 4 == 0; slots past cnt hold
-        // stale values and are never used), the four row loads issued back to back, a zero weight (or a slot past the list) as a
-        // select to the tile's first row - an L1 hit multiplied by 0 - instead of a branch around the load
-        static_assert(TILE % 4 == 0, "vector LDS reads assume four entries per step");
-        const int safe = ids[0];
-        for (int e0 = 0; e0 < cnt; e0 += 4) {
-            const int4 id4 = *reinterpret_cast<const int4*>(ids + e0);
-            const float4 w4 = *reinterpret_cast<const float4*>(ws + e0);
-            const int idv[4] = {id4.x, id4.y, id4.z, id4.w};
-            const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
-            Raw<NV, T> raw[4];
-            float wc[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const bool want = e0 + t < cnt && wv[t] != 0.f;
-                wc[t] = want ? wv[t] : 0.f;
-                load_raw<G, NV>(raw[t], Tab, want ? idv[t] : safe, g);
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                Frag<NV> y;
-                to_frag<NV>(y, raw[t]);
-                axpy<NV>(acc, wc[t], y);
-            }
-        }
-#endif
     }
     if (live) {
         const int slot = sv.seg_slab[seg];
@@ -319,21 +268,10 @@ constexpr int kRows4Tile = 64;
 // K=8 U=8 129.3 (spills)  K=7 U=5 75.7  K=6 U=4 74.9  K=6 U=5 70.6  K=6 U=6 70.5  K=6 U=7 79.4  K=5 U=6 70.4  K=5 U=8 83.0;
 // 4-wave workgroups at 3 per CU (168 VGPRs): K=8 U=6 82.0, K=10 U=6 81.4.  A (user block, row) run is ~9 entries: 6 + 3 instead of
 // 4 + 4 + 1 dependent trips.  Rows of 4 accumulator registers (fp32 r <= 256) keep K = 15, U = 4 (not re-measured).
-#ifndef TMF_ROWS4_UNROLL
-#define TMF_ROWS4_UNROLL 6
-#endif
-constexpr int kRows4Unroll2 = TMF_ROWS4_UNROLL, kRows4Unroll1 = 4;   // rows in flight per lane group: NV >= 2 / NV = 1
-#ifndef TMF_ROWS4_K2
-#define TMF_ROWS4_K2 6
-#endif
-#ifndef TMF_ROWS4_WAVES
-#define TMF_ROWS4_WAVES 8
-#endif
-#ifndef TMF_ROWS4_MINW
-#define TMF_ROWS4_MINW (TMF_ROWS4_WAVES / 2)   // waves per SIMD the register allocation must allow (4: two 8-wave workgroups per CU)
-#endif
-constexpr int kRows4Waves = TMF_ROWS4_WAVES;
-constexpr int kRows4K2 = TMF_ROWS4_K2;           // output rows per lane group when a row takes 8 accumulator registers (NV = 2)
+constexpr int kRows4Unroll2 = 6, kRows4Unroll1 = 4;   // rows in flight per lane group: NV >= 2 / NV = 1
+constexpr int kRows4Waves = 8;
+constexpr int kRows4MinWaves = kRows4Waves / 2;   // waves per SIMD the register allocation must allow (4: two 8-wave workgroups per CU)
+constexpr int kRows4K2 = 6;                       // output rows per lane group when a row takes 8 accumulator registers (NV = 2)
 
 // BALANCED form ("rows5", round 5): the rows a lane group owns are VIRTUAL rows - (output row, part p of P) - listed in (row, part)
 // order, so that a popular item (C4 / config 5: the top item has one list entry per user, the average 1,400) is cut into P parts
@@ -352,7 +290,7 @@ struct VRows {
 };
 
 template <int G, int NV, typename T, int K, int WAVES>
-__global__ __launch_bounds__(64 * WAVES, TMF_ROWS4_MINW) void k_wsum_rows4(
+__global__ __launch_bounds__(64 * WAVES, kRows4MinWaves) void k_wsum_rows4(
     const int64_t* __restrict__ rowptr, int64_t n_rows, int n_blocks, const int32_t* __restrict__ ent_row,
     const int32_t* __restrict__ ent_w, const float* __restrict__ wbuf, const T* __restrict__ Tab, const T* __restrict__ X_old,
     void* __restrict__ X_out, int epi, tmf_adam adam, int64_t row_begin, int64_t row_end, int* __restrict__ sync, int lag,
@@ -390,19 +328,8 @@ __global__ __launch_bounds__(64 * WAVES, TMF_ROWS4_MINW) void k_wsum_rows4(
         for (int c0 = r_beg; c0 < r_end; c0 += kRows4Tile) {
             const int cnt = (r_end - c0 < kRows4Tile) ? r_end - c0 : kRows4Tile;
             for (int e = g; e < cnt; e += G) {
-#if TMF_WSUM_VARIANT == 1   // timing only (see k_wsum_pass_pg): no 4-byte weight gather
-                ids[e] = ent_row[c0 + e];
-                ws[e] = __int_as_float(0x3f800000 | (ent_w[c0 + e] & 0xffff));
-#elif TMF_WSUM_VARIANT == 2   // timing only: sixteen L1-resident rows
-                ids[e] = ent_row[c0 + e] & 15;
-                ws[e] = wbuf[ent_w[c0 + e]];
-#elif TMF_WSUM_VARIANT == 3
-                ids[e] = ent_row[c0 + e] & 15;
-                ws[e] = __int_as_float(0x3f800000 | (ent_w[c0 + e] & 0xffff));
-#else
                 ids[e] = ent_row[c0 + e];
                 ws[e] = wbuf[ent_w[c0 + e]];
-#endif
             }
             wave_lds_sync();
 #pragma unroll
@@ -461,7 +388,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_combine_rows(
     zero<NV>(acc);
     for (int64_t s = beg + grp; s < end; s += NG) {
         Frag<NV> y;
-        load_row_f32<G, NV, T, TMF_NT_FIN>(y, slab, s, g);
+        load_row_f32<G, NV, T, kNtFin>(y, slab, s, g);
         add<NV>(acc, y);
     }
     across_groups_sum<G, NV>(acc);

@@ -20,10 +20,7 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kPosChunk = 512;
 constexpr int kUnrollW = 4;
-#ifndef TMF_G4_UNROLL
-#define TMF_G4_UNROLL 4
-#endif
-constexpr int kG4Unroll = TMF_G4_UNROLL;   // rows in flight per lane group of k_wmrb_gradu4 (4 or 8; A/B builds)
+constexpr int kG4Unroll = 4;   // rows in flight per lane group of k_wmrb_gradu4
 
 __host__ __device__ inline int round4(int x) { return (x + 3) & ~3; }
 
@@ -378,12 +375,8 @@ static int launch_wmrb_user(const int64_t* rowptr, const int32_t* col, const flo
 // (An in-launch variant - scores + hinge in one launch behind an agent-scope ticket - was measured slower and
 // removed; see profiles/r01_sliced_user_pass.txt.)
 // ---------------------------------------------------------------------------------------------
-#ifndef TMF_STREAM_NT
-#define TMF_STREAM_NT 1
-#endif
 // Read-once streams (ids, weights of a (user, slice) range) are loaded with the non-temporal hint, so that they do not displace
 // the slice's V rows in the L2s: same box, C4 fp32, gradU 26.6 -> 25.0 ms, scores 27.9 -> 27.75 (profiles/r03_c5_experiments.txt item 10)
-constexpr bool kStreamNT = TMF_STREAM_NT;
 constexpr int kSliceUsers = 16;   // users per workgroup of the slice kernels (SliceLists::upg)
 // Waves per workgroup of the slice kernels: 4, or 8 when a (user, slice) range is long (C4 fp32: 86 rows).  With 512-byte rows
 // eight waves are 16 lane groups = ONE user per lane group, and the workgroup retires when its users are done.  Same box,
@@ -412,8 +405,8 @@ __device__ __forceinline__ void slice_list(int* ids, float* dst, const int32_t* 
     for (int t0 = beg; t0 < end; t0 += kStageTile) {
         const int cnt = (end - t0 < kStageTile) ? end - t0 : kStageTile;
         for (int e = g; e < cnt; e += G) {
-            ids[e] = kStreamNT ? __builtin_nontemporal_load(list + t0 + e) : list[t0 + e];
-            if (GRADU) dst[e] = kStreamNT ? __builtin_nontemporal_load(wts + t0 + e) : wts[t0 + e];
+            ids[e] = __builtin_nontemporal_load(list + t0 + e);
+            if (GRADU) dst[e] = __builtin_nontemporal_load(wts + t0 + e);
         }
         wave_lds_sync();
         float keep = 0.f;  // scores: lane g keeps the score of entry (e & (G-1)) == g until G of them are complete
@@ -473,7 +466,7 @@ __device__ __forceinline__ void slice_scores_lean(int* ids, const int32_t* __res
     for (int t0 = beg; t0 < end; t0 += kStageTile) {
         const int cnt = (end - t0 < kStageTile) ? end - t0 : kStageTile;
         const int cnt4 = (cnt + 3) & ~3;
-        for (int e = g; e < cnt4; e += G) ids[e] = e < cnt ? (kStreamNT ? __builtin_nontemporal_load(list + t0 + e) : list[t0 + e]) : safe;
+        for (int e = g; e < cnt4; e += G) ids[e] = e < cnt ? __builtin_nontemporal_load(list + t0 + e) : safe;
         wave_lds_sync();
         float keep = 0.f;
         for (int e0 = 0; e0 < cnt4; e0 += 4) {
@@ -811,10 +804,10 @@ __global__ __launch_bounds__(kThreads) void k_wmrb_finish(const float* part, int
     const int64_t u = (int64_t)blockIdx.x * NGB + (threadIdx.x >> 6) * NG + lane / G;
     if (u >= n_users) return;
     Frag<NV> acc;
-    load_row_f32<G, NV, T, TMF_NT_FIN>(acc, part, u, g);
+    load_row_f32<G, NV, T, kNtFin>(acc, part, u, g);
     for (int sl = 1; sl < n_slices; ++sl) {
         Frag<NV> y;
-        load_row_f32<G, NV, T, TMF_NT_FIN>(y, part, sl * n_users + u, g);
+        load_row_f32<G, NV, T, kNtFin>(y, part, sl * n_users + u, g);
         add<NV>(acc, y);
     }
     row_epilogue<G, NV, T>(acc, U_old, U_out, u, g, epi, adam);
@@ -949,6 +942,37 @@ static int slice_waves(const tmf_slice_lists* l, int lanes_per_row) {
     return (l && l->n_slices > 0 && l->n_samples / l->n_slices >= kLongRange && lanes_per_row >= 32) ? 8 : 4;
 }
 
+// The one place that takes (storage type, row geometry, 4 or 8 waves) to an instance of a slice kernel:
+// launch(G, NV, W) is called with the three as integral constants.
+template <typename T, typename F>
+static int dispatch_slice_kernel(const RowGeom& geom, int waves, F&& launch) {
+#define CALLW(G_, NV_, W_) launch(std::integral_constant<int, G_>{}, std::integral_constant<int, NV_>{}, std::integral_constant<int, W_>{})
+#define CALL4(G_, NV_) CALLW(G_, NV_, 4)
+#define CALL8(G_, NV_) CALLW(G_, NV_, 8)
+    if (waves == 8) { TMF_DISPATCH(T, geom, CALL8); } else { TMF_DISPATCH(T, geom, CALL4); }
+#undef CALL4
+#undef CALL8
+#undef CALLW
+    return TMF_OK;
+}
+
+// One launch carries < 2^32 work-items: many slices x many user groups go out in several launches of whole slices
+// (XCD-major: whole rounds of eight).  launch() is called once per piece, with a.sl0 / a.nsl set to it.
+template <typename F>
+static int for_whole_slices(SliceLists& a, int waves, const char* what, F&& launch) {
+    const int unit = a.xcd ? 8 : 1;
+    const int64_t per_unit = a.n_groups * unit * 64 * waves;
+    const int max_units = (int)((((int64_t)1 << 32) - 1) / per_unit);
+    TMF_REQUIRE(max_units >= 1, "%s: %lld user groups exceed one launch", what, (long long)a.n_groups);
+    const int first = a.sl0, last = a.sl0 + a.nsl;
+    for (int s0 = first; s0 < last; s0 += max_units * unit) {
+        a.sl0 = s0;
+        a.nsl = (last - s0 < max_units * unit) ? last - s0 : max_units * unit;
+        if (int rc = launch()) return rc;
+    }
+    return TMF_OK;
+}
+
 template <typename T>
 static int wmrb_scores3_impl(const tmf_slice_lists* lists, const void* U, const void* V, float* sp, float* p,
                              int n_components, void* stream) {
@@ -960,27 +984,13 @@ static int wmrb_scores3_impl(const tmf_slice_lists* lists, const void* U, const 
     if (int rc = check_ids_debug(lists, (hipStream_t)stream)) return rc;
     TMF_REQUIRE(U && V && sp && (p || lists->col == nullptr), "wmrb_scores3: null pointer");
     const size_t lds = slice_lds(geom, waves);
-    // one launch carries < 2^32 work-items: many slices x many user groups go out in several launches of whole slices
-    // (XCD-major: whole rounds of eight)
-    const int unit = a.xcd ? 8 : 1;
-    const int64_t per_unit = a.n_groups * unit * 64 * waves;
-    const int max_units = (int)((((int64_t)1 << 32) - 1) / per_unit);
-    TMF_REQUIRE(max_units >= 1, "wmrb_scores3: %lld user groups exceed one launch", (long long)a.n_groups);
-    const int first = a.sl0, last = a.sl0 + a.nsl;
-    for (int s0 = first; s0 < last; s0 += max_units * unit) {
-        a.sl0 = s0;
-        a.nsl = (last - s0 < max_units * unit) ? last - s0 : max_units * unit;
-#define CALLW(G_, NV_, W_)                                                                                             \
-    hipLaunchKernelGGL((k_wmrb_scores3<G_, NV_, T, W_>), dim3(slice_grid(a)), dim3(64 * W_), lds, \
-                       (hipStream_t)stream, a, (const T*)U, (const T*)V, sp, p)
-#define CALL4(G_, NV_) CALLW(G_, NV_, 4)
-#define CALL8(G_, NV_) CALLW(G_, NV_, 8)
-        if (waves == 8) { TMF_DISPATCH(T, geom, CALL8); } else { TMF_DISPATCH(T, geom, CALL4); }
-#undef CALL4
-#undef CALL8
-#undef CALLW
-    }
-    return check_launch("tmf_wmrb_scores3");
+    const int rc = for_whole_slices(a, waves, "wmrb_scores3", [&] {
+        return dispatch_slice_kernel<T>(geom, waves, [&](auto G_, auto NV_, auto W_) {
+            hipLaunchKernelGGL((k_wmrb_scores3<G_(), NV_(), T, W_()>), dim3(slice_grid(a)), dim3(64 * W_()), lds,
+                               (hipStream_t)stream, a, (const T*)U, (const T*)V, sp, p);
+        });
+    });
+    return rc ? rc : check_launch("tmf_wmrb_scores3");
 }
 
 template <typename T>
@@ -994,56 +1004,25 @@ static int wmrb_gradu3_impl(const tmf_slice_lists* lists, const float* D, const 
     TMF_REQUIRE(D && V && part && (delta || lists->col == nullptr), "wmrb_gradu3: null pointer");   // no interactions at all: no delta either
     const size_t lds = slice_lds(geom, waves);
     TMF_REQUIRE(per_slice_launches >= 0 && per_slice_launches <= 3, "wmrb_gradu3: per_slice_launches=%d", per_slice_launches);
-    if (per_slice_launches == 3) {   // rounds of eight slices, one layer per XCD lane (see k_wmrb_gradu3)
-        TMF_REQUIRE_LAUNCH(a.n_groups * 8, 64 * waves, "wmrb_gradu3 (rounds of eight slices)");
-        for (int sl = a.sl0; sl < a.sl0 + a.nsl; sl += 8) {
-            const int accumulate = (sl == a.sl0) ? 3 : 4;
-#define CALLW(G_, NV_, W_)                                                                                                       \
-    hipLaunchKernelGGL((k_wmrb_gradu3<G_, NV_, T, W_>), dim3((unsigned)(a.n_groups * 8)), dim3(64 * W_), lds, (hipStream_t)stream, a, \
-                       (const T*)V, D, delta, part, sl, accumulate)
-#define CALL4(G_, NV_) CALLW(G_, NV_, 4)
-#define CALL8(G_, NV_) CALLW(G_, NV_, 8)
-            if (waves == 8) { TMF_DISPATCH(T, geom, CALL8); } else { TMF_DISPATCH(T, geom, CALL4); }
-#undef CALL4
-#undef CALL8
-#undef CALLW
-        }
+    const auto launch = [&](unsigned grid, int slice_first, int accumulate) {   // the launch site of all three modes
+        return dispatch_slice_kernel<T>(geom, waves, [&](auto G_, auto NV_, auto W_) {
+            hipLaunchKernelGGL((k_wmrb_gradu3<G_(), NV_(), T, W_()>), dim3(grid), dim3(64 * W_()), lds, (hipStream_t)stream, a,
+                               (const T*)V, D, delta, part, slice_first, accumulate);
+        });
+    };
+    if (per_slice_launches == 0) {   // one launch, or several of whole slices when one would exceed 2^32 work-items
+        if (int rc = for_whole_slices(a, waves, "wmrb_gradu3", [&] { return launch(slice_grid(a), -1, 0); })) return rc;
         return check_launch("tmf_wmrb_gradu3");
     }
-    if (per_slice_launches) {
-        TMF_REQUIRE_LAUNCH(a.n_groups, 64 * waves, "wmrb_gradu3 (one launch per slice)");
-        for (int sl = a.sl0; sl < a.sl0 + a.nsl; ++sl) {
-            const int accumulate = (sl == a.sl0 && per_slice_launches == 1) ? 1 : 2;
-#define CALLW(G_, NV_, W_)                                                                                                   \
-    hipLaunchKernelGGL((k_wmrb_gradu3<G_, NV_, T, W_>), dim3((unsigned)a.n_groups), dim3(64 * W_), lds, (hipStream_t)stream, a, \
-                       (const T*)V, D, delta, part, sl, accumulate)
-#define CALL4(G_, NV_) CALLW(G_, NV_, 4)
-#define CALL8(G_, NV_) CALLW(G_, NV_, 8)
-            if (waves == 8) { TMF_DISPATCH(T, geom, CALL8); } else { TMF_DISPATCH(T, geom, CALL4); }
-#undef CALL4
-#undef CALL8
-#undef CALLW
-        }
-        return check_launch("tmf_wmrb_gradu3");
-    }
-    // several launches of whole slices when one would exceed 2^32 work-items (see wmrb_scores3_impl)
-    const int unit = a.xcd ? 8 : 1;
-    const int64_t per_unit = a.n_groups * unit * 64 * waves;
-    const int max_units = (int)((((int64_t)1 << 32) - 1) / per_unit);
-    TMF_REQUIRE(max_units >= 1, "wmrb_gradu3: %lld user groups exceed one launch", (long long)a.n_groups);
-    const int first = a.sl0, last = a.sl0 + a.nsl;
-    for (int s0 = first; s0 < last; s0 += max_units * unit) {
-        a.sl0 = s0;
-        a.nsl = (last - s0 < max_units * unit) ? last - s0 : max_units * unit;
-#define CALLW(G_, NV_, W_)                                                                                   \
-    hipLaunchKernelGGL((k_wmrb_gradu3<G_, NV_, T, W_>), dim3(slice_grid(a)), dim3(64 * W_), lds, \
-                       (hipStream_t)stream, a, (const T*)V, D, delta, part, -1, 0)
-#define CALL4(G_, NV_) CALLW(G_, NV_, 4)
-#define CALL8(G_, NV_) CALLW(G_, NV_, 8)
-        if (waves == 8) { TMF_DISPATCH(T, geom, CALL8); } else { TMF_DISPATCH(T, geom, CALL4); }
-#undef CALL4
-#undef CALL8
-#undef CALLW
+    // a launch per slice (1: the first one stores, 2: all add), or per round of eight slices, one layer per XCD lane (3; see
+    // k_wmrb_gradu3)
+    const bool rounds = per_slice_launches == 3;
+    const int step = rounds ? 8 : 1;
+    TMF_REQUIRE_LAUNCH(a.n_groups * step, 64 * waves, rounds ? "wmrb_gradu3 (rounds of eight slices)" : "wmrb_gradu3 (one launch per slice)");
+    for (int sl = a.sl0; sl < a.sl0 + a.nsl; sl += step) {
+        const bool head = sl == a.sl0;
+        const int accumulate = rounds ? (head ? 3 : 4) : (head && per_slice_launches == 1) ? 1 : 2;
+        if (int rc = launch((unsigned)(a.n_groups * step), sl, accumulate)) return rc;
     }
     return check_launch("tmf_wmrb_gradu3");
 }
@@ -1073,10 +1052,7 @@ static int wmrb_gradu4_impl(const tmf_slice_lists* lists, const float* D, const 
         set_error("wmrb_gradu4: rows of %d lanes are too narrow for the row-stationary form; use tmf_wmrb_gradu3 + tmf_wmrb_finish", geom.G);
         return TMF_E_UNSUPPORTED;
     }
-#ifndef TMF_G4_K
-#define TMF_G4_K 4
-#endif
-    constexpr int K4 = TMF_G4_K;   // users per lane group (A/B builds)
+    constexpr int K4 = 4;   // users per lane group
     const int cap = geom.G < 16 ? geom.G : 16;
     const size_t lds = (size_t)(64 / geom.G) * W4 * 2 * K4 * 2 * cap * sizeof(int);
     const int64_t per_block = (int64_t)(64 / geom.G) * W4 * K4;
@@ -1335,17 +1311,9 @@ namespace tmf {
 // Config-5 shard, scores ms (profiles/r05_c5_shard.txt item 2): TWO steps of 8 gathers in flight per lane group (110 VGPRs, 4 waves per
 // SIMD): 32 users / 2 waves 55.4 (4 MB slices), 52.7 (6 MB); ONE step in flight (68 VGPRs, 7 waves per SIMD): 32 / 2: 51.0, 32 / 4: 50.0,
 // 32 / 8: 50.1, 64 / 4: 50.2, 64 / 8: 49.6, 16 / 4: 50.6, 128 / 8: 49.4, 128 / 16: 50.5 - more waves beat more rows per wave.
-#ifndef TMF_S6_USERS
-#define TMF_S6_USERS 64
-#endif
-#ifndef TMF_S6_WAVES
-#define TMF_S6_WAVES 8
-#endif
-#ifndef TMF_S6_ROUNDS
-#define TMF_S6_ROUNDS 1
-#endif
-constexpr int kS6Users = TMF_S6_USERS;    // users per chunk (their rows: 32 KB of LDS at 512-byte rows); at most 256 (8-bit local user)
-constexpr int kS6Waves = TMF_S6_WAVES;    // 16 lane groups: a chunk of ~580 entries is ~4.5 steps of 8 for each
+// The two-steps-in-flight tail is in profiles/build_time_variants.patch.
+constexpr int kS6Users = 64;   // users per chunk (their rows: 32 KB of LDS at 512-byte rows); at most 256 (8-bit local user)
+constexpr int kS6Waves = 8;    // 16 lane groups: a chunk of ~580 entries is ~4.5 steps of 8 for each
 
 template <int NV, typename T>
 __global__ __launch_bounds__(64 * kS6Waves) void k_wmrb_scores6(const int32_t* __restrict__ ids, const int32_t* __restrict__ outs,
@@ -1414,43 +1382,16 @@ __global__ __launch_bounds__(64 * kS6Waves) void k_wmrb_scores6(const int32_t* _
         const float sc = Reduce8x32::run(pr, lane);
         if (owner && d.o != kS5Pad) __builtin_nontemporal_store(sc, d.o >= 0 ? sp + d.o : p + ~d.o);
     };
-#if TMF_S6_ROUNDS == 1
     // one step of 8 gathers in flight per lane group: 68 VGPRs, seven waves per SIMD
-    {
-        Raw<NV, T> yA[8];
-        Ids A = fetch(0);
-        for (int i = 0; i < rounds; ++i) {
-            Ids B = fetch(i + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            gather(yA, A);
-            __builtin_amdgcn_sched_barrier(0);
-            finish(yA, A);
-            A = B;
-        }
-        return;
-    }
-#endif
-    // two rounds in flight per lane group, the ids of round i + 2 asked for BEFORE the rows of round i + 1 (as in scores5)
-    Raw<NV, T> yA[8], yB[8];
+    Raw<NV, T> yA[8];
     Ids A = fetch(0);
-    Ids B = fetch(1);
-    gather(yA, A);
-    for (int i = 0; i < rounds; i += 2) {
-        Ids C = fetch(i + 2);
+    for (int i = 0; i < rounds; ++i) {
+        Ids B = fetch(i + 1);
         __builtin_amdgcn_sched_barrier(0);
-        gather(yB, B);
+        gather(yA, A);
         __builtin_amdgcn_sched_barrier(0);
         finish(yA, A);
-        __builtin_amdgcn_sched_barrier(0);
-        if (i + 1 >= rounds) break;
-        Ids Dn = fetch(i + 3);
-        __builtin_amdgcn_sched_barrier(0);
-        gather(yA, C);
-        __builtin_amdgcn_sched_barrier(0);
-        finish(yB, B);
-        __builtin_amdgcn_sched_barrier(0);
-        A = C;
-        B = Dn;
+        A = B;
     }
 }
 

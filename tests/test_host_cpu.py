@@ -361,3 +361,18 @@ def test_32bit_offset_forms_switch_at_4_gb():
         assert last * row_bytes < (1 << 32) <= (last + 1) * row_bytes
         for fn in (lib.tmf_wmrb_scores6_supported, lib.tmf_wmrb_scores5_supported):
             assert fn(r, bf16, last) == 1 and fn(r, bf16, last + 1) == 0 and fn(r, bf16, 9_000_000) == 0, (fn, r)
+
+
+def test_no_preprocessor_conditionals_in_the_kernel_sources():
+    """The product build has ONE form: no #if / #ifdef / #ifndef / #elif in teamoflow_amd/csrc/, so no -D on the build line can
+    select a timing-only variant or an alternative path.  Experiment code lives as patches under profiles/
+    (build_time_variants.patch holds what the sources once carried)."""
+    conditional = re.compile(r'^\s*#\s*(if|ifdef|ifndef|elif)\b')
+    csrc = os.path.join(ROOT, 'teamoflow_amd', 'csrc')
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith(('.hip', '.h')))
+    assert 'tmf_common.h' in sources and 'tmf_train.hip' in sources and 'tmf_wmrb.hip' in sources
+    found = []
+    for name in sources:
+        with open(os.path.join(csrc, name)) as fh:
+            found += [f'{name}:{no}: {line.rstrip()}' for no, line in enumerate(fh, 1) if conditional.match(line)]
+    assert not found, '\n'.join(found)
