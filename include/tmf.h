@@ -129,6 +129,31 @@ int tmf_mse_pass_f32(const tmf_segments* seg, const int32_t* other, const float*
                      const float* X_old, const float* Y_old, float* X_out, float* slab,
                      float* loss_part, int n_components, int epi, tmf_adam adam, void* stream);
 
+/* One epoch of KLDivergenceLoss (loss_graphs.py:91-122 forward - two masks, tf.nn.moments of the stored scores of either class,
+ * 1 - Normal(mu- - mu+, sqrt(v+ + v-)).cdf(0); matrix_factorization.py:158-176 - the serial scores, tape.gradient, Adam)
+ * evaluated sparsely.  Class "+" = entries with val > 0, class "-" = entries with val <= 0 (stored zeros included); a NaN value is
+ * in neither and gets weight 0.  With N_c, mu_c, v_c the count, mean and population variance of p_k = <U[u_k], V[i_k]> over
+ * class c, sigma = sqrt(v+ + v-), z = (mu+ - mu-) / sigma and phi = exp(-z^2 / 2) / sqrt(2 pi):
+ *   loss = erfc(z / sqrt 2) / 2 (one scalar),   d loss / d p_k = a_c + b_c (p_k - mu_c),
+ *   a+ = -phi / (sigma N+),  a- = +phi / (sigma N-),  b_c = phi (mu+ - mu-) / (sigma^3 N_c).
+ * tmf_kl_moments_*: walks the user-side segments (X = U, Y = V, CSR by user) and writes, per segment, part[s][0..5] = N+, N-,
+ *   sum p+, sum p-, sum p^2+, sum p^2- - fp64 sums in a fixed order, no atomics; no table is written.  part: [nseg, 6] fp64,
+ *   16-byte aligned.
+ * tmf_kl_coeffs: one workgroup adds the nseg partials in a fixed order in fp64 and writes the loss into loss_out[0] and
+ *   coef[0..5] = a+, b+, mu+, a-, b-, mu- (fp64, device memory; nothing comes back to the host).  An empty class or sigma = 0
+ *   gives NaN / inf, as the reference's arithmetic does.
+ * tmf_kl_pass_*: the contract of tmf_mse_pass_* with `coef` in place of loss_part and the weight a_c + b_c (p_k - mu_c), p_k
+ *   recomputed from the gathered row, in place of -2 (val - p); padded slots and NaN values weigh 0.  Call once with (X = U,
+ *   Y = V, CSR by user) and once with (X = V, Y = U, CSC by item); both read the PRE-update tables; rows of several segments
+ *   are finished by tmf_combine_rows_*.
+ * Null tables or a bad `epi`: TMF_E_INVALID; nseg == 0: TMF_OK; nothing is launched in either case. */
+int tmf_kl_moments_f32(const tmf_segments* seg, const int32_t* other, const float* val, const float* X_old,
+                       const float* Y_old, double* part, int n_components, void* stream);
+int tmf_kl_coeffs(const double* part, int64_t nseg, double* loss_out, double* coef, void* stream);
+int tmf_kl_pass_f32(const tmf_segments* seg, const int32_t* other, const float* val, const float* X_old,
+                    const float* Y_old, float* X_out, float* slab, const double* coef, int n_components, int epi,
+                    tmf_adam adam, void* stream);
+
 /* Weighted row-gather-sum pass (item side of WMRB, matrix_factorization.py:170-171 through
  * loss_graphs.py:80-88):  g[i] = sum over entries e of row i of  wbuf[ent_w[e]] * T[ent_row[e]]
  * (entries with weight exactly 0 are skipped), then the epilogue writes X_out[i]. */
@@ -355,6 +380,11 @@ int tmf_topk_stable_f32(const float* X, int64_t rows, int64_t cols, int64_t ldx,
 int tmf_mse_pass_bf16(const tmf_segments* seg, const int32_t* other, const float* val,
                       const void* X_old, const void* Y_old, void* X_out, float* slab,
                       float* loss_part, int n_components, int epi, tmf_adam adam, void* stream);
+int tmf_kl_moments_bf16(const tmf_segments* seg, const int32_t* other, const float* val, const void* X_old,
+                        const void* Y_old, double* part, int n_components, void* stream);
+int tmf_kl_pass_bf16(const tmf_segments* seg, const int32_t* other, const float* val, const void* X_old,
+                     const void* Y_old, void* X_out, float* slab, const double* coef, int n_components, int epi,
+                     tmf_adam adam, void* stream);
 int tmf_wsum_pass_bf16(const tmf_segments* seg, const int32_t* ent_row, const int32_t* ent_w,
                        const float* wbuf, const void* T, const void* X_old, void* X_out,
                        float* slab, int n_components, int epi, tmf_adam adam, void* stream);

@@ -5,6 +5,7 @@ streams and the one-off index preparation (sort / bincount / cumsum).
 What replaces what (reference paths under /root/reference/src/teamoflow/mf/):
   epoch_mse   <- matrix_factorization.py:130-176 with MSELoss  (loss_graphs.py:47-52)
   epoch_wmrb  <- matrix_factorization.py:130-176 with WMRBLoss (loss_graphs.py:74-88, utils.py:94-105)
+  epoch_kl    <- matrix_factorization.py:130-176 with KLDivergenceLoss (loss_graphs.py:91-122)
 """
 import ctypes
 import os
@@ -741,8 +742,11 @@ class TrainState:
     ``scratch`` = a dict shared by such states: the per-step buffers are allocated once at the largest size any of them needs
     (``share_scratch``) instead of once per state."""
 
-    def __init__(self, U0, V0, plan, n_components, wplan=None, dtype=torch.float32, V_tables=None, scratch=None):
+    def __init__(self, U0, V0, plan, n_components, wplan=None, dtype=torch.float32, V_tables=None, scratch=None, kl=False):
         dev = plan.col_u.device
+        if kl:   # epoch_kl: the per-segment fp64 moments of the user side and the six coefficients tmf_kl_coeffs derives from them
+            self.kl_part = torch.zeros(max(plan.seg_u.nseg, 1), 6, dtype=torch.float64, device=dev)
+            self.kl_coef = torch.zeros(6, dtype=torch.float64, device=dev)
         self.r = int(n_components)
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError('factor tables are stored as float32 or bfloat16')
@@ -895,6 +899,33 @@ def epoch_mse(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=No
                                     _lib.ptr(st.U), _lib.ptr(V_out), _lib.ptr(st.slab), None, r, item_epi, adam, s), lib)
     if prof:
         prof.stop('mse_item_pass')
+    _row_pass_finish(lib, p.seg_i, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
+
+
+def epoch_kl(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM, user_out=None):
+    """One KLDivergenceLoss epoch (st built with kl=True): moments of the stored scores -> loss and coefficients -> user pass ->
+    item pass; everything reads the pre-update tables and nothing comes back to the host.
+    loss_out: 1-element fp64 device tensor receiving the epoch's loss (a scalar).  item_epi / user_epi as in epoch_mse."""
+    lib, p, r = _lib.get(), st.plan, st.r
+    s = _lib.stream_ptr()
+
+    def timed(name, rc):
+        if prof:
+            prof.start(name)
+        _lib.check(rc(), lib)
+        if prof:
+            prof.stop(name)
+    kl_pass = getattr(lib, 'tmf_kl_pass' + st.sfx)
+    timed('kl_moments', lambda: getattr(lib, 'tmf_kl_moments' + st.sfx)(
+        p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(st.kl_part), r, s))
+    timed('kl_coeffs', lambda: lib.tmf_kl_coeffs(_lib.ptr(st.kl_part), p.seg_u.nseg, _lib.ptr(loss_out), _lib.ptr(st.kl_coef), s))
+    U_out = st.U_nxt if user_out is None else user_out
+    timed('kl_user_pass', lambda: kl_pass(p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U), _lib.ptr(st.V),
+                                          _lib.ptr(U_out), _lib.ptr(st.slab), _lib.ptr(st.kl_coef), r, user_epi, adam, s))
+    _row_pass_finish(lib, p.seg_u, st.slab, st.U, U_out, r, user_epi, adam, s, st.sfx)
+    V_out = st.V_nxt if item_out is None else item_out
+    timed('kl_item_pass', lambda: kl_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(st.V), _lib.ptr(st.U),
+                                          _lib.ptr(V_out), _lib.ptr(st.slab), _lib.ptr(st.kl_coef), r, item_epi, adam, s))
     _row_pass_finish(lib, p.seg_i, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
 
 

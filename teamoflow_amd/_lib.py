@@ -77,6 +77,11 @@ _BASE_SIGNATURES = {
     'tmf_wmrb_entry_lists_workspace_bytes': (_SZ, [_L, _I32, _I32]),
     'tmf_wmrb_entry_lists': (_I, [_P, _P, _P, _L, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _SZ, _P]),
     'tmf_mse_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
+    'tmf_kl_moments_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _I, _P]),
+    'tmf_kl_moments_bf16': (_I, [_SEG, _P, _P, _P, _P, _P, _I, _P]),
+    'tmf_kl_coeffs': (_I, [_P, _L, _P, _P, _P]),
+    'tmf_kl_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
+    'tmf_kl_pass_bf16': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
     'tmf_wsum_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
     'tmf_wsum_rows4_rows_per_group': (_I, [_I, _I]),
     'tmf_wsum_rows4_workspace_bytes': (_SZ, [_I32, _I32, _I32]),

@@ -1,4 +1,4 @@
-// Row passes of one training epoch: MSE gather->dot->loss->gradient->Adam, the weighted
+// Row passes of one training epoch: MSE gather->dot->loss->gradient->Adam, the KL moments / coefficients / gradient, the weighted
 // gather-sum used by the WMRB item side, the combine of multi-segment rows, the standalone
 // fresh-Adam row update and the deterministic loss sum.  See include/tmf.h for the contracts
 // and DESIGN.md for the bytes each kernel moves.
@@ -94,6 +94,159 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_mse_pass(
         if (slot < 0) row_epilogue<G, NV, T>(acc, X_old, X_out, row, g, epi, adam);
         else store_row_f32<G, NV, T>(acc, slab, slot, g);
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// KL passes (KLDivergenceLoss).  The loss depends on the stored scores p_k only through the count, sum and sum of squares
+// of p over the class a_k > 0 and over the class a_k <= 0 (a NaN value is in neither), and d loss / d p_k is affine in p_k,
+// so an epoch is the walk of k_mse_pass three times: MOMENTS = true sums the six moments of every segment in fp64 and writes
+// no table; after k_kl_coeffs has turned their total into the loss and six coefficients, MOMENTS = false recomputes p_k from
+// the row it gathers anyway and accumulates the gradient row with the weight a_c + b_c (p_k - mu_c) in place of -2 (a_k - p_k).
+// ---------------------------------------------------------------------------------------------
+constexpr int kKlMoments = 6;   // per segment: N+, N-, sum p+, sum p-, sum p^2+, sum p^2-
+
+template <int G, int NV, typename T, bool MOMENTS>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void k_kl_pass(
+    SegView sv, const int32_t* __restrict__ other, const float* __restrict__ val,
+    const T* __restrict__ X_old, const T* __restrict__ Y_old, void* __restrict__ X_out,
+    float* __restrict__ slab, double* __restrict__ part, const double* __restrict__ coef, int epi, tmf_adam adam) {
+    constexpr int NG = 64 / G;
+    const int lane = threadIdx.x & 63;
+    const int64_t seg = sv.seg0 + (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (seg >= sv.nseg) return;
+    const int g = lane & (G - 1), grp = lane / G;
+    const int lrow = sv.seg_row[seg];
+    const int row = sv.row_mod > 0 ? lrow % sv.row_mod : lrow;
+    const int64_t rbeg = sv.rowptr[lrow], rend = sv.rowptr[lrow + 1];
+    const int64_t beg = rbeg + (int64_t)sv.seg_chunk[seg] * sv.chunk;
+    const int64_t end = (beg + sv.chunk < rend) ? beg + sv.chunk : rend;
+
+    Frag<NV> x, acc;
+    load_row<G, NV>(x, X_old, row, g);
+    zero<NV>(acc);
+    double mom[kKlMoments] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double a_pos = 0.0, b_pos = 0.0, mu_pos = 0.0, a_neg = 0.0, b_neg = 0.0, mu_neg = 0.0;
+    if constexpr (!MOMENTS) {
+        a_pos = coef[0]; b_pos = coef[1]; mu_pos = coef[2];
+        a_neg = coef[3]; b_neg = coef[4]; mu_neg = coef[5];
+    }
+
+    for (int64_t k0 = beg + grp; k0 < end; k0 += (int64_t)NG * kMseUnroll) {
+        Raw<NV, T> raw[kMseUnroll];
+        float a[kMseUnroll];
+        int j[kMseUnroll];
+        bool ok[kMseUnroll];
+#pragma unroll
+        for (int t = 0; t < kMseUnroll; ++t) {   // ids and values first, index clamped into the segment (k_mse_pass)
+            const int64_t k = k0 + (int64_t)t * NG;
+            ok[t] = k < end;
+            const int64_t kc = ok[t] ? k : end - 1;
+            j[t] = other[kc];
+            a[t] = val[kc];
+        }
+#pragma unroll
+        for (int t = 0; t < kMseUnroll; ++t) load_raw<G, NV>(raw[t], Y_old, j[t], g);
+#pragma unroll
+        for (int t = 0; t < kMseUnroll; ++t) {
+            Frag<NV> y;
+            to_frag<NV>(y, raw[t]);
+            const double p = (double)group_allsum<G>(dot_partial<NV>(x, y));
+            const bool pos = ok[t] && a[t] > 0.f, neg = ok[t] && a[t] <= 0.f;   // padded slots and NaN values: neither
+            if constexpr (MOMENTS) {
+                mom[0] += pos ? 1.0 : 0.0;
+                mom[1] += neg ? 1.0 : 0.0;
+                mom[2] += pos ? p : 0.0;
+                mom[3] += neg ? p : 0.0;
+                mom[4] += pos ? p * p : 0.0;   // an fp32 score squared is exact in fp64
+                mom[5] += neg ? p * p : 0.0;
+            } else {
+                const double w = pos ? a_pos + b_pos * (p - mu_pos) : a_neg + b_neg * (p - mu_neg);
+                axpy<NV>(acc, (pos || neg) ? (float)w : 0.f, y);
+            }
+        }
+    }
+    if constexpr (MOMENTS) {
+        // every lane of a group carries the same sums: add the groups in the fixed butterfly order, lane 0 writes the slot
+#pragma unroll
+        for (int c = 0; c < kKlMoments; ++c) {
+#pragma unroll
+            for (int off = 32; off >= G; off >>= 1) mom[c] += __shfl_xor(mom[c], off, 64);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < kKlMoments; ++c) part[seg * kKlMoments + c] = mom[c];
+        }
+    } else {
+        across_groups_sum<G, NV>(acc);
+        if (grp == 0) {
+            const int slot = sv.seg_slab[seg];
+            if (slot < 0) row_epilogue<G, NV, T>(acc, X_old, X_out, row, g, epi, adam);
+            else store_row_f32<G, NV, T>(acc, slab, slot, g);
+        }
+    }
+}
+
+// One workgroup: the per-segment moments summed in a fixed order in fp64 (a strided share per thread, a fixed butterfly over
+// the wave, then the 16 waves in order), then by thread 0
+//   mu_c = S_c / N_c,  v_c = Q_c / N_c - mu_c^2,  sigma = sqrt(v+ + v-),  z = (mu+ - mu-) / sigma,  loss = erfc(z / sqrt 2) / 2,
+//   phi = exp(-z^2 / 2) / sqrt(2 pi),  a+- = -+phi / (sigma N+-),  b+- = phi (mu+ - mu-) / (sigma^3 N+-).
+// An empty class or sigma = 0 is left to the arithmetic (NaN / inf), as in the reference.
+__global__ __launch_bounds__(1024) void k_kl_coeffs(const double* __restrict__ part, int64_t nseg, double* __restrict__ loss_out,
+                                                    double* __restrict__ coef) {
+    __shared__ double sh[16][kKlMoments];
+    // `part` read as 3 nseg pairs of 16 bytes, thread t taking pairs t, t + 1024, ..: every load of a wave is one contiguous KB
+    // (a segment per thread would be a 48-byte stride: 1.45 ms for the 48 MB of C4).  Pair e holds moments 2 (e % 3) and
+    // 2 (e % 3) + 1, and 1024 % 3 == 1, so step j of thread t meets pair (t + j) % 3: six steps per round, accumulator j % 3.
+    const double2* p2 = reinterpret_cast<const double2*>(part);
+    const int64_t n2 = 3 * nseg;
+    double2 acc[3] = {make_double2(0.0, 0.0), make_double2(0.0, 0.0), make_double2(0.0, 0.0)};
+    for (int64_t e0 = threadIdx.x; e0 < n2; e0 += 6 * 1024) {
+        double2 v[6];
+#pragma unroll
+        for (int u = 0; u < 6; ++u) {
+            const int64_t e = e0 + (int64_t)u * 1024;
+            v[u] = (e < n2) ? p2[e] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int u = 0; u < 6; ++u) {
+            acc[u % 3].x += v[u].x;
+            acc[u % 3].y += v[u].y;
+        }
+    }
+    const int rot = threadIdx.x % 3;   // acc[a] holds pair (t + a) % 3: pair c sits in acc[(c - t) mod 3]
+    const double2 m0 = rot == 0 ? acc[0] : rot == 1 ? acc[2] : acc[1];
+    const double2 m1 = rot == 0 ? acc[1] : rot == 1 ? acc[0] : acc[2];
+    const double2 m2 = rot == 0 ? acc[2] : rot == 1 ? acc[1] : acc[0];
+    double s[kKlMoments] = {m0.x, m0.y, m1.x, m1.y, m2.x, m2.y};
+#pragma unroll
+    for (int c = 0; c < kKlMoments; ++c) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) s[c] += __shfl_xor(s[c], off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < kKlMoments; ++c) sh[threadIdx.x >> 6][c] = s[c];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double t[kKlMoments];
+#pragma unroll
+    for (int c = 0; c < kKlMoments; ++c) {
+        t[c] = sh[0][c];
+        for (int w = 1; w < 16; ++w) t[c] += sh[w][c];
+    }
+    const double n_pos = t[0], n_neg = t[1];
+    const double mu_pos = t[2] / n_pos, mu_neg = t[3] / n_neg;
+    const double v_pos = t[4] / n_pos - mu_pos * mu_pos, v_neg = t[5] / n_neg - mu_neg * mu_neg;
+    const double sigma = sqrt(v_pos + v_neg), d = mu_pos - mu_neg, z = d / sigma;
+    const double phi = exp(-0.5 * z * z) * 0.3989422804014326779;   // 1 / sqrt(2 pi)
+    loss_out[0] = 0.5 * erfc(z * 0.7071067811865475244);
+    coef[0] = -phi / (sigma * n_pos);
+    coef[1] = phi * d / (sigma * sigma * sigma * n_pos);
+    coef[2] = mu_pos;
+    coef[3] = phi / (sigma * n_neg);
+    coef[4] = phi * d / (sigma * sigma * sigma * n_neg);
+    coef[5] = mu_neg;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -523,6 +676,65 @@ static int mse_pass_impl(const tmf_segments* seg, const int32_t* other, const fl
 #undef CALL
     }
     return check_launch("tmf_mse_pass");
+}
+
+// MOMENTS: the moments pass (writes `part`, no table); else the gradient pass with the coefficients of tmf_kl_coeffs
+template <typename T, bool MOMENTS>
+static int kl_pass_impl(const tmf_segments* seg, const int32_t* other, const float* val, const void* X_old, const void* Y_old,
+                        void* X_out, float* slab, double* part, const double* coef, int n_components, int epi, tmf_adam adam,
+                        void* stream) {
+    const char* what = MOMENTS ? "tmf_kl_moments" : "tmf_kl_pass";
+    if (int rc = check_segments(seg)) return rc;
+    if (seg->nseg == 0) return TMF_OK;
+    TMF_REQUIRE(X_old && Y_old && (MOMENTS || X_out), "%s: null table", what);
+    TMF_REQUIRE(other && val, "%s: null entry list", what);
+    if (MOMENTS) {
+        TMF_REQUIRE(part && reinterpret_cast<uintptr_t>(part) % 16 == 0, "%s: part is null or not 16-byte aligned", what);
+    } else {
+        TMF_REQUIRE(coef, "%s: coef is null", what);
+        TMF_REQUIRE(epi == TMF_EPI_ADAM || epi == TMF_EPI_GRAD, "%s: bad epilogue %d", what, epi);
+    }
+    const RowGeom geom = row_geom_of<T>(n_components);
+    SegView sv = view(seg);
+    for (sv.seg0 = 0; sv.seg0 < seg->nseg; sv.seg0 += kMaxBlocks * kWavesPerBlock) {   // pieces of < 2^32 work-items
+        const int64_t want = (seg->nseg - sv.seg0 + kWavesPerBlock - 1) / kWavesPerBlock;
+        const unsigned blocks = (unsigned)(want < kMaxBlocks ? want : kMaxBlocks);
+#define CALL(G_, NV_)                                                                                                      \
+    hipLaunchKernelGGL((k_kl_pass<G_, NV_, T, MOMENTS>), dim3(blocks), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, sv, \
+                       other, val, (const T*)X_old, (const T*)Y_old, X_out, slab, part, coef, epi, adam)
+        TMF_DISPATCH(T, geom, CALL);
+#undef CALL
+    }
+    return check_launch(what);
+}
+
+extern "C" int tmf_kl_moments_f32(const tmf_segments* seg, const int32_t* other, const float* val, const float* X_old,
+                                  const float* Y_old, double* part, int n_components, void* stream) {
+    return kl_pass_impl<float, true>(seg, other, val, X_old, Y_old, nullptr, nullptr, part, nullptr, n_components, TMF_EPI_GRAD,
+                                     tmf_adam{}, stream);
+}
+extern "C" int tmf_kl_moments_bf16(const tmf_segments* seg, const int32_t* other, const float* val, const void* X_old,
+                                   const void* Y_old, double* part, int n_components, void* stream) {
+    return kl_pass_impl<__bf16, true>(seg, other, val, X_old, Y_old, nullptr, nullptr, part, nullptr, n_components, TMF_EPI_GRAD,
+                                      tmf_adam{}, stream);
+}
+extern "C" int tmf_kl_coeffs(const double* part, int64_t nseg, double* loss_out, double* coef, void* stream) {
+    TMF_REQUIRE(nseg >= 0, "tmf_kl_coeffs: nseg=%lld", (long long)nseg);
+    if (nseg == 0) return TMF_OK;
+    TMF_REQUIRE(part && reinterpret_cast<uintptr_t>(part) % 16 == 0 && loss_out && coef,
+                "tmf_kl_coeffs: null pointer, or part not 16-byte aligned");
+    hipLaunchKernelGGL(k_kl_coeffs, dim3(1), dim3(1024), 0, (hipStream_t)stream, part, nseg, loss_out, coef);
+    return check_launch("tmf_kl_coeffs");
+}
+extern "C" int tmf_kl_pass_f32(const tmf_segments* seg, const int32_t* other, const float* val, const float* X_old,
+                               const float* Y_old, float* X_out, float* slab, const double* coef, int n_components, int epi,
+                               tmf_adam adam, void* stream) {
+    return kl_pass_impl<float, false>(seg, other, val, X_old, Y_old, X_out, slab, nullptr, coef, n_components, epi, adam, stream);
+}
+extern "C" int tmf_kl_pass_bf16(const tmf_segments* seg, const int32_t* other, const float* val, const void* X_old,
+                                const void* Y_old, void* X_out, float* slab, const double* coef, int n_components, int epi,
+                                tmf_adam adam, void* stream) {
+    return kl_pass_impl<__bf16, false>(seg, other, val, X_old, Y_old, X_out, slab, nullptr, coef, n_components, epi, adam, stream);
 }
 
 template <typename T>

@@ -1,6 +1,6 @@
 """Loss graphs (plug-in interface of /root/reference/src/teamoflow/mf/loss_graphs.py).
 
-``MSELoss`` and ``WMRBLoss`` with ``LinearEmbedding`` over indicator features are recognised by
+``MSELoss``, ``WMRBLoss`` and ``KLDivergenceLoss`` with ``LinearEmbedding`` over indicator features are recognised by
 ``MatrixFactorization.fit`` (same isinstance dispatch as matrix_factorization.py:152-162) and run as
 fused HIP kernels; ``get_loss`` below is the generic differentiable definition used when the model is
 built from other plug-ins (dense features, custom embeddings), always called by keyword like

@@ -2,11 +2,12 @@
 /root/reference/src/teamoflow/mf/matrix_factorization.py:23-475, computed sparsely on MI355X.
 
 Dispatch (same isinstance test the reference uses at :115,:136-162): a model made of
-``LinearEmbedding`` x indicator features x (``MSELoss`` | ``WMRBLoss``) trains on the HIP engine
-(``_engine.py`` -> libtmf.so) and needs a GPU - there is no CPU fallback for it.  Any other
-combination of plug-ins (dense features, biased / ReLU embeddings, KL loss, user subclasses) trains
+``LinearEmbedding`` x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss``) trains on the
+HIP engine (``_engine.py`` -> libtmf.so); for the first two it needs a GPU - there is no CPU fallback for them.
+Any other combination of plug-ins (dense features, biased / ReLU embeddings, user subclasses) trains
 through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins'
-own ``get_repr`` / ``get_loss``.
+own ``get_repr`` / ``get_loss`` - and so does KL without a GPU, with ``batch_users`` / ``shard_items`` /
+``data_parallel`` set, or on a table with an empty class.
 """
 import os
 import timeit
@@ -107,8 +108,18 @@ class MatrixFactorization:
     # ------------------------------------------------------------------------------------------
     def _on_fast_path(self, user_features, item_features):
         return (type(self.user_repr_graph) is LinearEmbedding and type(self.item_repr_graph) is LinearEmbedding
-                and type(self.loss_graph) in (MSELoss, WMRBLoss)
+                and type(self.loss_graph) in (MSELoss, WMRBLoss, KLDivergenceLoss)
                 and is_indicator(user_features) and is_indicator(item_features))
+
+    def _data_parallel_active(self):
+        return bool(self.data_parallel and torch.distributed.is_available() and torch.distributed.is_initialized()
+                    and torch.distributed.get_world_size() > 1 or (self.data_parallel == 'force'))
+
+    def _kl_engine_allowed(self):
+        """KLDivergenceLoss has no CPU, mini-batch, item-sharded or data-parallel form on the engine (its moments are global):
+        those settings, which the generic path ignores for KL, keep the generic path."""
+        return (torch.cuda.is_available() and not getattr(self, 'batch_users', 0) and not getattr(self, 'shard_items', 0)
+                and not self._data_parallel_active())
 
     def fit(self, epochs, user_features, item_features, tf_interactions, lr=1e-2):
         """matrix_factorization.py:96-187.  Re-initialises the weights on every call, runs ``epochs``
@@ -125,16 +136,19 @@ class MatrixFactorization:
         else:
             V = self.item_weight_graph.initialize_weights(self.item_aux_dim, self.n_components)
         interactions = _as_interactions(tf_interactions)
-        if self._on_fast_path(user_features, item_features):
-            self._fit_sparse(epochs, n_users, n_items, interactions, lr, U, V)
-        else:
-            self._fit_generic(epochs, user_features, item_features, interactions, lr, U, V)
+        kl = type(self.loss_graph) is KLDivergenceLoss
+        if self._on_fast_path(user_features, item_features) and (not kl or self._kl_engine_allowed()):
+            if self._fit_sparse(epochs, n_users, n_items, interactions, lr, U, V):
+                return
+        self._fit_generic(epochs, user_features, item_features, interactions, lr, U, V)
 
     def _report(self, epoch, loss, seconds):
         if self.verbose and (epoch + 1) % 25 == 0:
             print(f'Epoch {epoch + 1} Complete | Loss {loss} | Runtime {seconds:.5} s')
 
     def _fit_sparse(self, epochs, n_users, n_items, interactions, lr, U0, V0):
+        """Trains on the HIP engine and returns True; False (nothing trained) for a KLDivergenceLoss table with an empty class,
+        which fit() hands to the generic path."""
         _lib.get()  # fail loudly here when the HIP engine cannot run
         self._sharded_epoch = None
         dev = default_device()
@@ -142,6 +156,7 @@ class MatrixFactorization:
         if interactions.device != dev:
             interactions = interactions.to(dev)
         wmrb = isinstance(self.loss_graph, WMRBLoss)
+        kl = type(self.loss_graph) is KLDivergenceLoss
         if wmrb and self.random_ind is None:
             raise SampleTableMissing('WMRBLoss needs generate_sample=True (random_ind is None)')
         if getattr(self, 'batch_users', 0):
@@ -149,19 +164,20 @@ class MatrixFactorization:
                 raise ValueError('batch_users cannot be combined with shard_items / data_parallel')
             from .. import _minibatch
             _minibatch.fit_minibatch(self, epochs, n_users, n_items, interactions, lr, U0, V0, self.batch_users)
-            return
+            return True
         if getattr(self, 'shard_items', 0):
             from .. import dist as tdist
             tdist.fit_item_sharded(self, epochs, n_users, n_items, interactions, lr, U0, V0, windows_per_rank=int(self.shard_items))
-            return
-        if self.data_parallel and torch.distributed.is_available() and torch.distributed.is_initialized() \
-                and torch.distributed.get_world_size() > 1 or (self.data_parallel == 'force'):
+            return True
+        if self._data_parallel_active():
             from .. import dist as tdist
             tdist.fit_data_parallel(self, epochs, n_users, n_items, interactions, lr, U0, V0)
-            return
+            return True
         ld = _lib.padded_ld(self.n_components, self.factor_dtype)
         plan = _engine.InteractionPlan(interactions.indices, interactions.values, n_users, n_items,
                                        user_chunks=1 if wmrb else _engine.mse_user_chunks(), csc=not wmrb)
+        if kl and (plan.n_pos == 0 or int((plan.val_u <= 0).sum()) == 0):
+            return False   # an empty class: no moments to take (the reference's arithmetic gives NaN; the generic path keeps that)
         wplan, c = None, 0.0
         if wmrb:
             if self.random_ind is None:
@@ -173,10 +189,10 @@ class MatrixFactorization:
                 raise IndexError('random_ind holds item ids outside [0, n_items)')
             c = self.n_items / self.n_samples  # constructor ints, true division (:167)
             wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype)
-        st = _engine.TrainState(U0, V0, plan, self.n_components, wplan, dtype=self.factor_dtype)
+        st = _engine.TrainState(U0, V0, plan, self.n_components, wplan, dtype=self.factor_dtype, kl=kl)
         adam = _engine.adam_constants(lr)
         loss_sums = torch.zeros(max(epochs, 1), dtype=torch.float64, device=dev)
-        denom = plan.n_pos if wmrb else plan.nnz
+        denom = plan.n_pos if wmrb else 1 if kl else plan.nnz   # KL: the loss is one scalar, its mean is itself
         self.loss_history_ = []
         if self.optimizer not in ('fresh_adam', 'adam'):
             raise ValueError(f"optimizer={self.optimizer!r}: 'fresh_adam' (the reference's behaviour) or 'adam'")
@@ -193,6 +209,8 @@ class MatrixFactorization:
                 a = lib.tmf_adam_step(float(lr), epoch + 1)
                 if wmrb:
                     _engine.epoch_wmrb(st, a, c, out, _lib.EPI_GRAD, gV, None, _lib.EPI_GRAD, gU)
+                elif kl:
+                    _engine.epoch_kl(st, a, out, _lib.EPI_GRAD, gV, None, _lib.EPI_GRAD, gU)
                 else:
                     _engine.epoch_mse(st, a, out, _lib.EPI_GRAD, gV, None, _lib.EPI_GRAD, gU)
                 for W, G, M, V2 in ((st.U, gU, mom[0], mom[1]), (st.V, gV, mom[2], mom[3])):
@@ -201,6 +219,8 @@ class MatrixFactorization:
                 return
             if wmrb:
                 _engine.epoch_wmrb(st, adam, c, out)
+            elif kl:
+                _engine.epoch_kl(st, adam, out)
             else:
                 _engine.epoch_mse(st, adam, out)
             st.swap()
@@ -252,6 +272,7 @@ class MatrixFactorization:
         self.item_embedding = st.V[:, :r]
         self.user_trainable = [self.user_embedding]
         self.item_trainable = [self.item_embedding]
+        return True
 
     def _fit_generic(self, epochs, user_features, item_features, interactions, lr, U, V):
         """The reference's dense loop (:128-187) over arbitrary plug-ins, differentiated by autograd."""

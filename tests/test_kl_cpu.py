@@ -1,0 +1,138 @@
+"""CPU side of the sparse KLDivergenceLoss path (no GPU): the C ABI of the five tmf_kl_* entry points (declared, bound, built,
+argument checks that fail before anything is launched) and the closed form the kernels evaluate, stated in NumPy and pinned
+to the dense fp64 oracle."""
+import ctypes
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT, rel_err
+
+KL_NAMES = ('tmf_kl_moments_f32', 'tmf_kl_moments_bf16', 'tmf_kl_coeffs', 'tmf_kl_pass_f32', 'tmf_kl_pass_bf16')
+
+
+def kl_moments(p, val):
+    """(N+, N-, mu+, mu-, v+, v-) of the stored scores p: class + = val > 0, class - = val <= 0, population variances."""
+    p, val = np.asarray(p, np.float64), np.asarray(val, np.float64)
+    pos, neg = p[val > 0], p[val <= 0]
+    return pos.size, neg.size, pos.mean(), neg.mean(), pos.var(), neg.var()
+
+
+def kl_closed_form(U, V, idx, val):
+    """Loss and gradients of one KL epoch from the closed form the engine uses, in fp64:
+    z = (mu+ - mu-) / sigma, loss = erfc(z / sqrt 2) / 2, d loss / d p_k = a_c + b_c (p_k - mu_c)
+    -> (loss, gU, gV, w [nnz])."""
+    U, V, val = np.asarray(U, np.float64), np.asarray(V, np.float64), np.asarray(val, np.float64)
+    u, i = idx[:, 0], idx[:, 1]
+    p = np.einsum('kr,kr->k', U[u], V[i])
+    n_pos, n_neg, mu_pos, mu_neg, v_pos, v_neg = kl_moments(p, val)
+    sigma = math.sqrt(v_pos + v_neg)
+    d = mu_pos - mu_neg
+    z = d / sigma
+    phi = math.exp(-0.5 * z * z) / math.sqrt(2.0 * math.pi)
+    w = np.zeros_like(p)
+    pos, neg = val > 0, val <= 0
+    w[pos] = -phi / (sigma * n_pos) + phi * d / (sigma ** 3 * n_pos) * (p[pos] - mu_pos)
+    w[neg] = +phi / (sigma * n_neg) + phi * d / (sigma ** 3 * n_neg) * (p[neg] - mu_neg)
+    gU, gV = np.zeros_like(U), np.zeros_like(V)
+    np.add.at(gU, u, w[:, None] * V[i])
+    np.add.at(gV, i, w[:, None] * U[u])
+    return 0.5 * math.erfc(z / math.sqrt(2.0)), gU, gV, w
+
+
+def kl_problem(seed, m=33, n=47, r=5):
+    """The generic problem of the KL tests: 30 % of the pairs stored, values in [-5, 5] (stored zeros occur), tables ~ N(0, 0.3^2)."""
+    rng = np.random.default_rng(seed)
+    mask = rng.random((m, n)) < 0.3
+    A = rng.integers(-5, 6, (m, n))
+    idx = np.argwhere(mask)
+    val = A[mask].astype(np.float32)
+    U0 = (rng.standard_normal((m, r)) * 0.3).astype(np.float32)
+    V0 = (rng.standard_normal((n, r)) * 0.3).astype(np.float32)
+    return idx, val, U0, V0
+
+
+def kl_oracle(U0, V0, idx, val, epochs, lr):
+    from oracle import dense_ref as D
+    m, n = U0.shape[0], V0.shape[0]
+    return D.fit_dense_plugins(U0, V0, idx, val, 'kl', epochs, lr, np.eye(m), np.eye(n), dtype=torch.float64)
+
+
+@pytest.mark.parametrize('seed', range(4))
+def test_closed_form_is_the_dense_oracle(seed):
+    idx, val, U0, V0 = kl_problem(seed, r=(5, 12, 24, 128)[seed])
+    assert (val == 0).any() and (val > 0).any() and (val < 0).any()
+    ref = kl_oracle(U0, V0, idx, val, 1, 0.05)
+    loss, gU, gV, _ = kl_closed_form(U0, V0, idx, val)
+    assert abs(loss - ref['loss'][0]) <= 1e-12 * abs(ref['loss'][0])
+    assert 0.3 < loss < 0.7          # a relative tolerance on the first loss means something
+    assert rel_err(gU, ref['first_grads'][0][0]) < 1e-12
+    assert rel_err(gV, ref['first_grads'][1][0]) < 1e-12
+
+
+def test_entry_points_are_declared_bound_and_built():
+    from teamoflow_amd import _lib
+    header = open(os.path.join(ROOT, 'include', 'tmf.h')).read()
+    declared = set(re.findall(r'\b(tmf_[a-z0-9_]+)\s*\(', header))
+    lib = _lib.load_library()
+    for name in KL_NAMES:
+        assert name in declared and name in _lib.SIGNATURES and hasattr(lib, name), name
+    assert lib.tmf_version() == _lib.MIN_LIB_VERSION
+
+
+def test_argument_checks_fail_before_any_launch():
+    """No GPU here: a call that got as far as a launch would fail differently (or crash); these return first."""
+    from teamoflow_amd import _lib
+    lib = _lib.load_library()
+    adam = lib.tmf_adam_fresh(0.05)
+    i64, i32 = (ctypes.c_int64 * 2)(0, 1), (ctypes.c_int32 * 1)(0)
+    slab = (ctypes.c_int32 * 1)(-1)
+    host = (ctypes.c_double * 8)()              # stands for any non-null table / list / buffer: never dereferenced
+    H = ctypes.cast(host, ctypes.c_void_p)
+
+    def seg(nseg):
+        return ctypes.byref(_lib.Segments(ctypes.addressof(i64), ctypes.addressof(i32), ctypes.addressof(i32), ctypes.addressof(slab),
+                                          nseg, 1024, 0))
+
+    def failed(rc, word):
+        return rc != 0 and word in lib.tmf_last_error().decode()
+
+    for sfx in ('_f32', '_bf16'):
+        moments, kl_pass = getattr(lib, 'tmf_kl_moments' + sfx), getattr(lib, 'tmf_kl_pass' + sfx)
+        assert moments(seg(0), None, None, None, None, None, 24, None) == 0                       # nothing to do
+        assert kl_pass(seg(0), None, None, None, None, None, None, None, 24, 7, adam, None) == 0
+        assert failed(moments(seg(1), H, H, None, H, H, 24, None), 'null table')
+        assert failed(moments(seg(1), H, H, H, None, H, 24, None), 'null table')
+        assert failed(moments(seg(1), H, H, H, H, None, 24, None), 'part')
+        assert failed(kl_pass(seg(1), H, H, None, H, H, H, H, 24, _lib.EPI_ADAM, adam, None), 'null table')
+        assert failed(kl_pass(seg(1), H, H, H, None, H, H, H, 24, _lib.EPI_ADAM, adam, None), 'null table')
+        assert failed(kl_pass(seg(1), H, H, H, H, None, H, H, 24, _lib.EPI_GRAD, adam, None), 'null table')
+        assert failed(kl_pass(seg(1), H, H, H, H, H, H, None, 24, _lib.EPI_ADAM, adam, None), 'coef')
+        assert failed(kl_pass(seg(1), H, H, H, H, H, H, H, 24, 2, adam, None), 'bad epilogue 2')
+        assert failed(kl_pass(None, H, H, H, H, H, H, H, 24, _lib.EPI_ADAM, adam, None), 'segments')
+    assert lib.tmf_kl_coeffs(None, 0, None, None, None) == 0
+    assert failed(lib.tmf_kl_coeffs(None, 5, H, H, None), 'tmf_kl_coeffs')
+    assert failed(lib.tmf_kl_coeffs(H, 5, None, H, None), 'tmf_kl_coeffs')
+    assert failed(lib.tmf_kl_coeffs(H, -1, H, H, None), 'nseg')
+
+
+def test_dispatch_without_a_gpu_stays_generic(monkeypatch):
+    """KL over indicator features is a fast-path model, but without a GPU (or with a mini-batch / sharded / data-parallel setting,
+    which the generic path ignores for KL) it keeps the generic loop."""
+    from teamoflow_amd.mf.loss_graphs import KLDivergenceLoss
+    from teamoflow_amd.mf.matrix_factorization import MatrixFactorization
+    from teamoflow_amd.mf.sparse import eye
+    model = MatrixFactorization(4, loss_graph=KLDivergenceLoss())
+    assert model._on_fast_path(eye(6), eye(7))
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
+    assert not model._kl_engine_allowed()
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: True)
+    assert model._kl_engine_allowed()
+    for name, value in (('batch_users', 8), ('shard_items', 2), ('data_parallel', 'force')):
+        other = MatrixFactorization(4, loss_graph=KLDivergenceLoss())
+        setattr(other, name, value)
+        assert not other._kl_engine_allowed(), name
