@@ -12,7 +12,8 @@ are 0.5 .. 5.0 in half steps.  From there on every call is the reference's:
 
     python examples/movielens_shape.py [100k | 1m | n_users n_items n_ratings] [--components 5] [--epochs 100] [--biased]
 
-`--biased` also trains the reference's third model (BiasedLinearEmbedding, :81-86), which takes the generic autograd path.
+`--biased` also trains the reference's third model (BiasedLinearEmbedding on both sides, :81-86); its identity features are
+indicators, so on a GPU it trains on the sparse HIP engine like the other two (the generic autograd path without one).
 """
 import argparse
 import os

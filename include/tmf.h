@@ -339,6 +339,31 @@ int tmf_wmrb_finish_bf16(const float* part, int32_t n_slices, int32_t n_users, c
 int tmf_adam_fresh_rows_f32(float* W, const float* G, int64_t n_rows, int n_components,
                             tmf_adam adam, void* stream);
 
+/* BiasedLinearEmbedding over indicator features (embedding_graphs.py:41-58): the effective table is E = W + 1 b^T with a
+ * trainable [1, r] bias b.  The passes read E and, under TMF_EPI_GRAD, write G = dL/dE = dL/dW [n_rows, ld]; dL/db is the column
+ * sum of G, and W, b take the same fresh-Adam step (matrix_factorization.py:173-176).  fp32 tables only.  Per epoch and side:
+ * the pass with TMF_EPI_GRAD, tmf_bias_colsum_f32 (colsum = NULL), tmf_bias_adam_f32, tmf_adam_bias_rows_f32.
+ *
+ *   tmf_bias_colsum_part_rows  rows P of the workspace `part` [P, ld] fp64 for a table of n_rows rows (>= 1; 0 for n_rows < 0).
+ *   tmf_bias_colsum_f32        part[p][c] = sum of G[i][c] over the p-th block of rows (a fixed partition, fp64 accumulators, no
+ *                              atomics).  With colsum != NULL also colsum[c] = sum_p part[p][c] for c < n_components and 0 for the
+ *                              padding columns, [ld] fp64, summed in a fixed order: bit-identical from run to run.  The padding
+ *                              columns of G may hold anything.  n_rows = 0 gives zeros.  part_rows must be what
+ *                              tmf_bias_colsum_part_rows returns for n_rows.
+ *   tmf_bias_adam_f32          g_b[c] = fp32(sum_p part[p][c]) (the same fixed order, rounded once), stored in g_out [ld] when it is
+ *                              not NULL, and b[c] = fresh-Adam(b[c], g_b[c]) in place for c < n_components; the padding columns
+ *                              of b and g_out are written as zeros.  b: [ld] fp32.
+ *   tmf_adam_bias_rows_f32     one sweep over every row: W[i] = fresh-Adam(W[i], G[i]) in place (the arithmetic of
+ *                              tmf_adam_fresh_rows_f32), then E[i] = W[i] + b_new.  Columns >= n_components of W and E are written
+ *                              as zeros whatever W, G and b_new hold there.  W, G, E: [n_rows, ld], 16-byte aligned, W != E. */
+int64_t tmf_bias_colsum_part_rows(int64_t n_rows);
+int tmf_bias_colsum_f32(const float* G, int64_t n_rows, int n_components, double* part, int64_t part_rows, double* colsum,
+                        void* stream);
+int tmf_bias_adam_f32(const double* part, int64_t part_rows, float* b, float* g_out, int n_components, tmf_adam adam,
+                      void* stream);
+int tmf_adam_bias_rows_f32(float* W, const float* G, const float* b_new, float* E, int64_t n_rows, int n_components,
+                           tmf_adam adam, void* stream);
+
 /* OPT-IN EXTENSION, not the reference's optimiser (which is rebuilt every epoch, matrix_factorization.py:176): Keras
  * Adam with persistent moments.  tmf_adam_step gives the scalars of iteration `step` (1-based; step 1 == tmf_adam_fresh),
  * tmf_adam_state_rows_f32 applies one step in place to a whole [n_rows, ld] table from its raw gradient G (the

@@ -742,7 +742,8 @@ class TrainState:
     ``scratch`` = a dict shared by such states: the per-step buffers are allocated once at the largest size any of them needs
     (``share_scratch``) instead of once per state."""
 
-    def __init__(self, U0, V0, plan, n_components, wplan=None, dtype=torch.float32, V_tables=None, scratch=None, kl=False):
+    def __init__(self, U0, V0, plan, n_components, wplan=None, dtype=torch.float32, V_tables=None, scratch=None, kl=False,
+                 user_bias=None, item_bias=None):
         dev = plan.col_u.device
         if kl:   # epoch_kl: the per-segment fp64 moments of the user side and the six coefficients tmf_kl_coeffs derives from them
             self.kl_part = torch.zeros(max(plan.seg_u.nseg, 1), 6, dtype=torch.float64, device=dev)
@@ -753,13 +754,18 @@ class TrainState:
         self.dtype = dtype
         self.sfx = '_bf16' if dtype is torch.bfloat16 else '_f32'
         self.ld = _lib.padded_ld(self.r, dtype)
+        if (user_bias is not None or item_bias is not None) and (dtype is not torch.float32 or V_tables is not None):
+            raise ValueError('a biased side needs float32 factor tables of its own')
+        # a biased side (BiasSide): U / V is its effective table E = W + b, rebuilt in place every epoch - no second buffer
         self.U = self._pad(U0, dev)
-        self.U_nxt = torch.empty_like(self.U)
+        self.bias_u = None if user_bias is None else BiasSide(self.U, user_bias, self.r)
+        self.U_nxt = torch.empty_like(self.U) if user_bias is None else None
         if V_tables is None:
             self.V = self._pad(V0, dev)
-            self.V_nxt = torch.empty_like(self.V)
+            self.V_nxt = torch.empty_like(self.V) if item_bias is None else None
         else:
             self.V, self.V_nxt = V_tables
+        self.bias_v = None if item_bias is None else BiasSide(self.V, item_bias, self.r)
         self.plan, self.wplan = plan, wplan
         need = dict(slab=max(plan.seg_u.n_slab, plan.seg_i.n_slab if plan.seg_i else 0,
                              wplan.seg_e.n_slab if wplan is not None and wplan.seg_e is not None else 0,
@@ -829,8 +835,70 @@ class TrainState:
         return out
 
     def swap(self):
-        self.U, self.U_nxt = self.U_nxt, self.U
-        self.V, self.V_nxt = self.V_nxt, self.V
+        if self.bias_u is None:
+            self.U, self.U_nxt = self.U_nxt, self.U
+        if self.bias_v is None:
+            self.V, self.V_nxt = self.V_nxt, self.V
+
+
+class BiasSide:
+    """One BiasedLinearEmbedding side over indicator features (embedding_graphs.py:41-58): the raw weights W [rows, ld] - kept as
+    a table of their own, the reference computes fl(W + b) afresh every epoch -, the bias b [ld] (zeros beyond r), the gradient
+    table G the passes fill under TMF_EPI_GRAD, g_b [ld] (the last bias gradient) and the fp64 partial column sums.  ``E`` is the
+    TrainState table of the side: it holds the padded W0 on entry and W0 + b0 afterwards."""
+
+    def __init__(self, E, b0, r):
+        lib = _lib.get()
+        rows, ld = E.shape
+        b0 = torch.as_tensor(b0).detach().to(device=E.device, dtype=torch.float32).reshape(-1)
+        if b0.numel() != r:
+            raise ValueError(f'linear bias of {b0.numel()} elements for n_components={r}')
+        self.r = int(r)
+        self.W = E.clone()
+        self.b = torch.zeros(ld, dtype=torch.float32, device=E.device)
+        self.b[:r] = b0
+        E[:, :r] += self.b[:r]
+        self.g_b = torch.zeros(ld, dtype=torch.float32, device=E.device)
+        self.G = torch.empty_like(E)
+        self.part_rows = int(lib.tmf_bias_colsum_part_rows(rows))
+        self.part = torch.empty(self.part_rows, ld, dtype=torch.float64, device=E.device)
+
+
+def bias_update(side, E, adam, prof=None, tag=''):
+    """The step of one biased side from its gradient table side.G (filled by this epoch's pass): column sums -> bias step -> row
+    update, which also rebuilds E = W + b in place.  Stream-ordered, nothing allocated, no host scalars: graph-capturable.
+    tag: prefix of the three span names under ``prof`` (KernelTimer)."""
+    lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
+    rows = E.shape[0]
+
+    def timed(name, rc):
+        if prof:
+            prof.start(name)
+        _lib.check(rc(), lib)
+        if prof:
+            prof.stop(name)
+    timed(tag + 'bias_colsum', lambda: lib.tmf_bias_colsum_f32(P(side.G), rows, side.r, P(side.part), side.part_rows, None, s))
+    timed(tag + 'bias_adam', lambda: lib.tmf_bias_adam_f32(P(side.part), side.part_rows, P(side.b), P(side.g_b), side.r, adam, s))
+    timed(tag + 'adam_bias_rows', lambda: lib.tmf_adam_bias_rows_f32(P(side.W), P(side.G), P(side.b), P(E), rows, side.r, adam, s))
+
+
+def epoch_biased(st, adam, loss_out, loss='mse', c=0.0, prof=None):
+    """One epoch of a state with at least one biased side: the loss's own epoch on the effective tables, a biased side emitting
+    its raw gradient (TMF_EPI_GRAD) where an unbiased one keeps the fused fresh-Adam epilogue into its second buffer; then the
+    bias and row updates of the biased sides (both passes have read the pre-update tables by then) and the swap of the others."""
+    ue, uo = (_lib.EPI_GRAD, st.bias_u.G) if st.bias_u is not None else (_lib.EPI_ADAM, None)
+    ie, io = (_lib.EPI_GRAD, st.bias_v.G) if st.bias_v is not None else (_lib.EPI_ADAM, None)
+    if loss == 'wmrb':
+        epoch_wmrb(st, adam, c, loss_out, ie, io, prof, ue, uo)
+    elif loss == 'kl':
+        epoch_kl(st, adam, loss_out, ie, io, prof, ue, uo)
+    else:
+        epoch_mse(st, adam, loss_out, ie, io, prof, ue, uo)
+    if st.bias_u is not None:
+        bias_update(st.bias_u, st.U, adam, prof, 'user_')
+    if st.bias_v is not None:
+        bias_update(st.bias_v, st.V, adam, prof, 'item_')
+    st.swap()
 
 
 def share_scratch(scratch, dev):

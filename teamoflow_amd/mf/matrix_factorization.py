@@ -2,12 +2,13 @@
 /root/reference/src/teamoflow/mf/matrix_factorization.py:23-475, computed sparsely on MI355X.
 
 Dispatch (same isinstance test the reference uses at :115,:136-162): a model made of
-``LinearEmbedding`` x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss``) trains on the
-HIP engine (``_engine.py`` -> libtmf.so); for the first two it needs a GPU - there is no CPU fallback for them.
-Any other combination of plug-ins (dense features, biased / ReLU embeddings, user subclasses) trains
+(``LinearEmbedding`` | ``BiasedLinearEmbedding``) x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss``)
+trains on the HIP engine (``_engine.py`` -> libtmf.so); for unbiased MSE / WMRB it needs a GPU - there is no CPU fallback for them.
+Any other combination of plug-ins (dense features, ReLU embeddings, user subclasses) trains
 through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins'
 own ``get_repr`` / ``get_loss`` - and so does KL without a GPU, with ``batch_users`` / ``shard_items`` /
-``data_parallel`` set, or on a table with an empty class.
+``data_parallel`` set, or on a table with an empty class, and a biased side without a GPU, with those settings, with bf16 factor
+storage or with ``optimizer='adam'``.
 """
 import os
 import timeit
@@ -107,9 +108,18 @@ class MatrixFactorization:
     # training
     # ------------------------------------------------------------------------------------------
     def _on_fast_path(self, user_features, item_features):
-        return (type(self.user_repr_graph) is LinearEmbedding and type(self.item_repr_graph) is LinearEmbedding
+        kinds = (type(self.user_repr_graph), type(self.item_repr_graph))
+        if not (all(k in (LinearEmbedding, BiasedLinearEmbedding) for k in kinds)
                 and type(self.loss_graph) in (MSELoss, WMRBLoss, KLDivergenceLoss)
-                and is_indicator(user_features) and is_indicator(item_features))
+                and is_indicator(user_features) and is_indicator(item_features)):
+            return False
+        return BiasedLinearEmbedding not in kinds or self._biased_engine_allowed()
+
+    def _biased_engine_allowed(self):
+        """A BiasedLinearEmbedding side trains on the engine as float32 tables with the reference's fresh-Adam step, full-batch on
+        one GPU; anything else keeps the generic path, as before."""
+        return (torch.cuda.is_available() and self.factor_dtype is torch.float32 and self.optimizer == 'fresh_adam'
+                and not getattr(self, 'batch_users', 0) and not getattr(self, 'shard_items', 0) and not self._data_parallel_active())
 
     def _data_parallel_active(self):
         return bool(self.data_parallel and torch.distributed.is_available() and torch.distributed.is_initialized()
@@ -189,7 +199,14 @@ class MatrixFactorization:
                 raise IndexError('random_ind holds item ids outside [0, n_items)')
             c = self.n_items / self.n_samples  # constructor ints, true division (:167)
             wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype)
-        st = _engine.TrainState(U0, V0, plan, self.n_components, wplan, dtype=self.factor_dtype, kl=kl)
+        r = self.n_components
+        # a biased side starts from the bias an earlier fit left on the model, as in the reference (:139-146), else from zeros
+        bias0 = [None, None]
+        for i, (graph, kept) in enumerate(((self.user_repr_graph, self.user_linear_bias), (self.item_repr_graph, self.item_linear_bias))):
+            if type(graph) is BiasedLinearEmbedding:
+                bias0[i] = torch.zeros(r) if kept is None else kept
+        biased = bias0[0] is not None or bias0[1] is not None
+        st = _engine.TrainState(U0, V0, plan, r, wplan, dtype=self.factor_dtype, kl=kl, user_bias=bias0[0], item_bias=bias0[1])
         adam = _engine.adam_constants(lr)
         loss_sums = torch.zeros(max(epochs, 1), dtype=torch.float64, device=dev)
         denom = plan.n_pos if wmrb else 1 if kl else plan.nnz   # KL: the loss is one scalar, its mean is itself
@@ -216,6 +233,9 @@ class MatrixFactorization:
                 for W, G, M, V2 in ((st.U, gU, mom[0], mom[1]), (st.V, gV, mom[2], mom[3])):
                     _lib.check(lib.tmf_adam_state_rows_f32(_lib.ptr(W), _lib.ptr(G), _lib.ptr(M), _lib.ptr(V2), W.shape[0],
                                                            self.n_components, a, _lib.stream_ptr()), lib)
+                return
+            if biased:
+                _engine.epoch_biased(st, adam, out, 'wmrb' if wmrb else 'kl' if kl else 'mse', c)
                 return
             if wmrb:
                 _engine.epoch_wmrb(st, adam, c, out)
@@ -267,11 +287,18 @@ class MatrixFactorization:
         sums = loss_sums[:epochs].cpu().numpy()
         self.loss_history_ = (sums / denom if denom else np.full(epochs, np.nan)).tolist()
         self._state = st
-        r = self.n_components
         self.user_embedding = st.U[:, :r]
         self.item_embedding = st.V[:, :r]
         self.user_trainable = [self.user_embedding]
         self.item_trainable = [self.item_embedding]
+        # a biased side leaves what _fit_generic leaves: [weights, bias], the [1, r] bias kept on the model - a leaf that requires
+        # grad, because a later generic fit differentiates with respect to it
+        if st.bias_u is not None:
+            self.user_linear_bias = st.bias_u.b[:r].clone().view(1, r).requires_grad_(True)
+            self.user_trainable = [st.bias_u.W[:, :r], self.user_linear_bias]
+        if st.bias_v is not None:
+            self.item_linear_bias = st.bias_v.b[:r].clone().view(1, r).requires_grad_(True)
+            self.item_trainable = [st.bias_v.W[:, :r], self.item_linear_bias]
         return True
 
     def _fit_generic(self, epochs, user_features, item_features, interactions, lr, U, V):
