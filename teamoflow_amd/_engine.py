@@ -20,6 +20,11 @@ DEFAULT_CHUNK = 1024  # list entries per segment (heavy rows are cut into severa
 PART_BUDGET = int(os.environ.get('TMF_PART_BUDGET', 8 << 30))
 
 
+def row_bytes(n_components, dtype=torch.float32):
+    """Bytes of one factor-table row as stored (padded to the row geometry, _lib.padded_ld)."""
+    return _lib.padded_ld(n_components, dtype) * (2 if dtype is torch.bfloat16 else 4)
+
+
 def _excl_cumsum(x):
     out = torch.zeros(x.numel() + 1, dtype=torch.int64, device=x.device)
     torch.cumsum(x, 0, out=out[1:])
@@ -62,15 +67,8 @@ class SegmentTable:
     tmf_combine_rows."""
 
     def __init__(self, rowptr, chunk=DEFAULT_CHUNK, out_row=None, n_out=None, row_mod=0):
-        dev = rowptr.device
         rows = rowptr.numel() - 1
-        lens = rowptr[1:] - rowptr[:-1]
-        nch = torch.clamp((lens + (chunk - 1)) // chunk, min=1)
-        nseg = int(nch.sum())
-        seg_first = _excl_cumsum(nch)
-        ar = torch.arange(rows, device=dev)
-        seg_row = torch.repeat_interleave(ar, nch, output_size=nseg)
-        seg_chunk = torch.arange(nseg, device=dev) - seg_first[seg_row]
+        nch, seg_row, seg_chunk = self._cut(rowptr[1:] - rowptr[:-1], chunk)
         if out_row is None:
             multi = nch > 1
             slab_beg = _excl_cumsum(nch * multi)
@@ -79,15 +77,30 @@ class SegmentTable:
             self.n_slab = int(slab_beg[-1])
             self.long_slab_beg = torch.cat([slab_beg[long_rows], slab_beg[-1:]]).contiguous()
         else:
-            seg_out = out_row[seg_row]
-            order = torch.sort(seg_out, stable=True)[1]  # table-row-major, list order kept inside a row
-            seg_slab = torch.empty(nseg, dtype=torch.int64, device=dev)
-            seg_slab[order] = torch.arange(nseg, device=dev)
-            long_rows = torch.arange(n_out, device=dev)
-            self.n_slab = nseg
-            self.long_slab_beg = _excl_cumsum(torch.bincount(seg_out, minlength=n_out))
-        self.rows, self.chunk, self.nseg, self.row_mod = rows, int(chunk), nseg, int(row_mod)
-        self.rowptr = rowptr.contiguous()
+            seg_slab, long_rows = self._slots_by_out_row(out_row[seg_row], n_out)
+        self._set(rows, chunk, row_mod, rowptr.contiguous(), seg_row, seg_chunk, seg_slab, long_rows)
+
+    @staticmethod
+    def _cut(lens, chunk):
+        """(segments per row, row of every segment, its chunk index): rows of ``lens`` entries cut into segments of <= chunk."""
+        nch = torch.clamp((lens + (chunk - 1)) // chunk, min=1)
+        nseg = int(nch.sum())
+        seg_row = torch.repeat_interleave(torch.arange(lens.numel(), device=lens.device), nch, output_size=nseg)
+        return nch, seg_row, torch.arange(nseg, device=lens.device) - _excl_cumsum(nch)[seg_row]
+
+    def _slots_by_out_row(self, seg_out, n_out):
+        """Every segment a slab slot, numbered output-row-major with the list order kept inside a row; all n_out rows are
+        'long'.  seg_out: output row of every segment.  -> (seg_slab, long_rows); sets n_slab and long_slab_beg."""
+        nseg = seg_out.numel()
+        seg_slab = torch.empty(nseg, dtype=torch.int64, device=seg_out.device)
+        seg_slab[torch.sort(seg_out, stable=True)[1]] = torch.arange(nseg, device=seg_out.device)
+        self.n_slab = nseg
+        self.long_slab_beg = _excl_cumsum(torch.bincount(seg_out, minlength=n_out))
+        return seg_slab, torch.arange(n_out, device=seg_out.device)
+
+    def _set(self, rows, chunk, row_mod, rowptr, seg_row, seg_chunk, seg_slab, long_rows):
+        self.rows, self.chunk, self.nseg, self.row_mod = int(rows), int(chunk), int(seg_row.numel()), int(row_mod)
+        self.rowptr = rowptr
         self.seg_row = seg_row.to(torch.int32)
         self.seg_chunk = seg_chunk.to(torch.int32)
         self.seg_slab = seg_slab.to(torch.int32)
@@ -101,27 +114,9 @@ class SegmentTable:
         ``out_row[i]`` in [0, n_out) is the output row the partial sums of list row ``rows[i]`` belong to.  One window of
         an item-row-sharded pass: the lists of the window's items, output rows relative to the window."""
         self = cls.__new__(cls)
-        dev = rowptr.device
-        lens = rowptr[rows + 1] - rowptr[rows]
-        nch = torch.clamp((lens + (chunk - 1)) // chunk, min=1)
-        nseg = int(nch.sum())
-        seg_first = _excl_cumsum(nch)
-        sel = torch.repeat_interleave(torch.arange(rows.numel(), device=dev), nch, output_size=nseg)
-        seg_chunk = torch.arange(nseg, device=dev) - seg_first[sel]
-        seg_out = out_row[sel]
-        order = torch.sort(seg_out, stable=True)[1]
-        seg_slab = torch.empty(nseg, dtype=torch.int64, device=dev)
-        seg_slab[order] = torch.arange(nseg, device=dev)
-        self.n_slab = nseg
-        self.long_slab_beg = _excl_cumsum(torch.bincount(seg_out, minlength=n_out))
-        self.rows, self.chunk, self.nseg, self.row_mod = int(rows.numel()), int(chunk), nseg, 0
-        self.rowptr = rowptr
-        self.seg_row = rows[sel].to(torch.int32)
-        self.seg_chunk = seg_chunk.to(torch.int32)
-        self.seg_slab = seg_slab.to(torch.int32)
-        self.long_rows = torch.arange(n_out, device=dev, dtype=torch.int32)
-        self.n_long = int(n_out)
-        self._c = None
+        _, sel, seg_chunk = cls._cut(rowptr[rows + 1] - rowptr[rows], chunk)
+        seg_slab, long_rows = self._slots_by_out_row(out_row[sel], n_out)
+        self._set(rows.numel(), chunk, 0, rowptr, rows[sel], seg_chunk, seg_slab, long_rows)
         return self
 
     def cstruct(self):
@@ -206,8 +201,6 @@ def _slab_budget():
         return int(env)
     total = torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory if torch.cuda.is_available() else 32 << 30
     return int(min(64 << 30, total // 4))
-
-
 
 
 def default_user_chunks(n_users, ld, target_bytes=3 << 20, n_items=None):
@@ -306,10 +299,9 @@ def rows4_wanted(n_components, dtype=torch.float32, plan=None, R=None, n_users=N
         n_items = plan.n_items if n_items is None else n_items
     if not n_users or not n_items:
         return False
-    ld = _lib.padded_ld(n_components, dtype)
-    row_bytes = ld * (2 if dtype is torch.bfloat16 else 4)
-    blocks_wanted = -(-int(n_users) * row_bytes // ROWS5_BLOCK_BYTES)          # user blocks of ~4 MB of rows as stored
-    blocks_slab_allows = max(1, _slab_budget() // (int(n_items) * ld * 4))     # one fp32 partial row per (block, item)
+    blocks_wanted = -(-int(n_users) * row_bytes(n_components, dtype) // ROWS5_BLOCK_BYTES)   # user blocks of ~4 MB of rows as stored
+    # one fp32 partial row per (block, item)
+    blocks_slab_allows = max(1, _slab_budget() // (int(n_items) * _lib.padded_ld(n_components, dtype) * 4))
     return blocks_wanted > 2 * blocks_slab_allows
 
 
@@ -322,8 +314,7 @@ def rows5_user_chunks(n_users, n_components, dtype=torch.float32):
     env = os.environ.get('TMF_USER_CHUNKS')
     if env:
         return max(1, int(env))
-    row_bytes = _lib.padded_ld(n_components, dtype) * (2 if dtype is torch.bfloat16 else 4)
-    return int(min(max(1, -(-int(n_users) * row_bytes // ROWS5_BLOCK_BYTES)), 256))
+    return int(min(max(1, -(-int(n_users) * row_bytes(n_components, dtype) // ROWS5_BLOCK_BYTES)), 256))
 
 
 class VirtualRows:
@@ -481,7 +472,7 @@ class WmrbPlan:
         self.hinge_order = hinge_user_order(plan.rowptr_u)
         self.D = self.wbuf[nnz:].view(m, S)
         self._lists = None
-        self.s5 = None   # Scores5Plan, built by the TrainState that wants the row-stationary scores kernel (scores5_wanted)
+        self.s5 = self.s6 = None   # Scores5Plan / Scores6Plan, built by the TrainState that wants that scores kernel (scores5_wanted, scores6_wanted)
 
     def lists(self, plan):
         """tmf_slice_lists of the sliced pass (kept alive with the plan)."""
@@ -528,14 +519,13 @@ def wmrb_plan_for(plan, R, n_components, dtype=torch.float32, n_items=None):
     n_items: the catalog size for the slice geometry when the plan's table is padded (multi-GPU: rows padded to the world size)."""
     m = plan.n_users
     n = plan.n_items if n_items is None else n_items
-    bf16 = dtype is torch.bfloat16
-    ld_store = _lib.padded_ld(n_components, dtype)
-    ns, sliced = choose_wmrb_user_pass(m, n, ld_store, int(R.shape[1]), plan.n_pos, n_components, elem_size=2 if bf16 else 4)
+    ns, sliced = choose_wmrb_user_pass(m, n, _lib.padded_ld(n_components, dtype), int(R.shape[1]), plan.n_pos, n_components,
+                                       elem_size=2 if dtype is torch.bfloat16 else 4)
     # short visits (config-5 shard): the row-stationary gradU with its own slice size, unless the environment decides
     # (TMF_ROW_STATIONARY = 0 | 1, TMF_ITEM_SLICES)
     rs = row_stationary_wanted(m, n, int(R.shape[1]), plan.nnz, n_components, dtype, sliced)
     if rs and not os.environ.get('TMF_ITEM_SLICES'):
-        ns = int(max(1, -(-n * ld_store * (2 if bf16 else 4) // GRADU4_SLICE_BYTES)))
+        ns = int(max(1, -(-n * row_bytes(n_components, dtype) // GRADU4_SLICE_BYTES)))
     rows4 = rows4_wanted(n_components, dtype, plan, R)
     C = rows5_user_chunks(m, n_components, dtype) if rows4 else default_user_chunks(m, _lib.padded_ld(n_components), n_items=plan.n_items)
     return WmrbPlan(plan, R, user_chunks=C, item_slices=ns, n_components=n_components, sliced=sliced, rows4=rows4)
@@ -563,8 +553,7 @@ def short_visits(n_users, n_items, n_samples, nnz, n_components, dtype=torch.flo
     (+ the user's interactions in the slice): 9 at the config-5 shard (1M items x 512 bytes), 88 at C4.  Short visits are what
     tmf_wmrb_scores3 / gradu3 pay their per-visit round trips, their row of U and their partial row for; such shapes take the flat
     streams (tmf_wmrb_scores6) and the row-stationary gradU (tmf_wmrb_gradu4) instead."""
-    row_bytes = _lib.padded_ld(n_components, dtype) * (2 if dtype is torch.bfloat16 else 4)
-    table = n_items * row_bytes
+    table = n_items * row_bytes(n_components, dtype)
     if table < 8 * VISIT_SLICE_BYTES:   # short because the catalog is cut fine, not because a user has few negatives (tiny S)
         return False
     return (n_samples + nnz / max(n_users, 1)) * VISIT_SLICE_BYTES / table <= SCORES6_MAX_VISIT
@@ -579,40 +568,32 @@ SCORES6_MAX_VISIT = 24          # rows of a (user, 4 MB slice) visit up to which
 SCORES6_DEFAULT = True          # config-5 shard: 55.4 ms against 59.5 for scores3, fabric traffic 183 GB against 446 (profiles/r05_c5_shard.txt)
 
 
-class Scores6Plan:
-    """Entry stream of tmf_wmrb_scores6 (include/tmf.h), built once per fit from the sliced plan: every (user, item) pair whose
-    score the epoch needs - interaction k of the CSR (score -> p[k]) and negative (u, pos) of the item-sorted table (score ->
-    sp[u, pos]) - keyed by chunk = slice * n_groups + user group and put in that order by ONE stable radix sort: inside a chunk
-    the interactions come first, then the negatives, each by user and item (so the scores of a user's visit are neighbours in the
-    stream AND in sp / p).  Every chunk is padded to whole steps of 8 entries with its last id and the PAD place."""
+class _ScoreStreams:
+    """What Scores5Plan and Scores6Plan share: ONE stable radix sort (stable_order) puts every (user, item) pair whose score the epoch
+    needs - interaction k of the CSR (score -> p[k], place ~k) and negative (u, pos) of the item-sorted table (score -> sp[u, pos],
+    place u * S + pos) - in key order; inside a key the interactions come first, then the negatives, each by user and item.  An id
+    packs (user % users_per_owner) << 24 | item.  A stream = keys_per_stream consecutive keys, padded to whole steps of 8 entries
+    with its last id (a valid user, a resident row) and the PAD place."""
 
     PAD = -2 ** 31
 
-    def __init__(self, plan, wplan, n_components, dtype=torch.float32, slice_bytes=None):
-        lib = _lib.load_library()   # the builder itself needs no GPU (tests/test_host_cpu.py runs it on CPU tensors)
-        dev = plan.col_u.device
-        self.key = (int(n_components), dtype)
-        UG = int(lib.tmf_wmrb_scores6_users_per_group())
+    def _build(self, plan, wplan, users_per_owner, key_of, n_keys, keys_per_stream=1):
+        """key_of(owner = user // users_per_owner, item) -> int32 key in [0, n_keys).  Sets ids, outs, n_entries, n_padded;
+        -> (first padded entry of every stream, first sorted entry of every key)."""
+        dev, i32, UO = plan.col_u.device, torch.int32, users_per_owner
         m, S = wplan.R.shape
-        nnz, n = plan.nnz, plan.n_items
+        nnz = plan.nnz
         E = nnz + m * S
-        self.n_groups = ng = -(-m // UG)
-        row_bytes = _lib.padded_ld(n_components, dtype) * (2 if dtype is torch.bfloat16 else 4)
-        slice_bytes = int(os.environ.get('TMF_S6_SLICE_BYTES', slice_bytes or SCORES6_SLICE_BYTES))
-        ns = int(min(max(1, -(-n * row_bytes // slice_bytes)), max(1, (2 ** 31 - 1) // max(ng, 1))))
-        width = -(-n // ns)
-        self.n_slices = ns = -(-n // width)
-        i32 = torch.int32
         uo = plan.user_of                                                  # int32 [nnz]
         rows = torch.arange(m, device=dev, dtype=i32)
         keys = torch.empty(E, dtype=i32, device=dev)
-        keys[:nnz] = (plan.col_u // width) * ng + uo // UG
-        keys[nnz:].view(m, S).copy_((wplan.R // width) * ng + (rows // UG)[:, None])
-        perm, rowptr = stable_order(keys, ns * ng)
+        keys[:nnz] = key_of(uo // UO, plan.col_u)
+        keys[nnz:].view(m, S).copy_(key_of((rows // UO)[:, None], wplan.R))
+        perm, rowptr = stable_order(keys, n_keys)
         del keys
         packed = torch.empty(E, dtype=i32, device=dev)
-        packed[:nnz] = ((uo % UG) << 24) | plan.col_u
-        packed[nnz:].view(m, S).copy_(((rows % UG) << 24)[:, None] | wplan.R)
+        packed[:nnz] = ((uo % UO) << 24) | plan.col_u
+        packed[nnz:].view(m, S).copy_(((rows % UO) << 24)[:, None] | wplan.R)
         ids_sorted = packed[perm]
         del packed
         outs = torch.empty(E, dtype=i32, device=dev)
@@ -620,7 +601,8 @@ class Scores6Plan:
         outs[nnz:] = torch.arange(m * S, device=dev, dtype=i32)            # u * S + pos: to sp[u, pos]
         outs_sorted = outs[perm]
         del outs, perm
-        cnt = rowptr[1:] - rowptr[:-1]
+        ptr = rowptr[::keys_per_stream].contiguous()
+        cnt = ptr[1:] - ptr[:-1]
         ptr8 = _excl_cumsum((cnt + 7) // 8 * 8)
         E8 = int(ptr8[-1])
         self.ids = torch.empty(E8 + 8, dtype=i32, device=dev)
@@ -629,15 +611,33 @@ class Scores6Plan:
         step = 1 << 27
         for q0 in range(0, E8, step):
             q = torch.arange(q0, min(q0 + step, E8), device=dev, dtype=torch.int64)
-            ch = torch.searchsorted(ptr8, q, right=True) - 1
-            r = q - ptr8[ch]
-            c = cnt[ch]
-            src = rowptr[ch] + torch.minimum(r, c - 1)
+            st = torch.searchsorted(ptr8, q, right=True) - 1
+            r = q - ptr8[st]
+            c = cnt[st]
+            src = ptr[st] + torch.minimum(r, c - 1)
             self.ids[q0:q0 + q.numel()] = ids_sorted[src]
             self.outs[q0:q0 + q.numel()] = torch.where(r < c, outs_sorted[src], torch.full_like(src, self.PAD).to(i32))
-            del q, ch, r, c, src
-        self.chunk_ptr = ptr8
+            del q, st, r, c, src
         self.n_entries, self.n_padded = E, E8
+        return ptr8, rowptr
+
+
+class Scores6Plan(_ScoreStreams):
+    """Entry stream of tmf_wmrb_scores6 (include/tmf.h), built once per fit from the sliced plan (_ScoreStreams): keyed by chunk =
+    slice * n_groups + user group, so the scores of a user's visit are neighbours in the stream AND in sp / p; every chunk is a
+    stream of its own."""
+
+    def __init__(self, plan, wplan, n_components, dtype=torch.float32, slice_bytes=None):
+        lib = _lib.load_library()   # the builder itself needs no GPU (tests/test_host_cpu.py runs it on CPU tensors)
+        self.key = (int(n_components), dtype)
+        UG = int(lib.tmf_wmrb_scores6_users_per_group())
+        n = plan.n_items
+        self.n_groups = ng = -(-wplan.R.shape[0] // UG)
+        slice_bytes = int(os.environ.get('TMF_S6_SLICE_BYTES', slice_bytes or SCORES6_SLICE_BYTES))
+        ns = int(min(max(1, -(-n * row_bytes(n_components, dtype) // slice_bytes)), max(1, (2 ** 31 - 1) // max(ng, 1))))
+        width = -(-n // ns)
+        self.n_slices = ns = -(-n // width)
+        self.chunk_ptr, _ = self._build(plan, wplan, UG, lambda grp, item: (item // width) * ng + grp, ns * ng)
 
 
 def scores5_wanted(plan, wplan, n_components, dtype=torch.float32):
@@ -654,67 +654,25 @@ def scores5_wanted(plan, wplan, n_components, dtype=torch.float32):
     return bool(_lib.load_library().tmf_wmrb_scores5_supported(int(n_components), int(dtype is torch.bfloat16), int(plan.n_items)))
 
 
-class Scores5Plan:
-    """Entry streams of tmf_wmrb_scores5 (include/tmf.h), built once per fit from the sliced plan: every (user, item) pair whose
-    score the epoch needs - interaction k of the CSR (score -> p[k]) and negative (u, pos) of the item-sorted table (score ->
-    sp[u, pos]) - keyed by (workgroup = u // 256, slice = item // width) and put in that order by ONE stable radix sort
-    (stable_order): inside a (workgroup, slice) chunk the interactions come first, then the negatives, each by user and item.
+class Scores5Plan(_ScoreStreams):
+    """Entry streams of tmf_wmrb_scores5 (include/tmf.h), built once per fit from the sliced plan (_ScoreStreams): keyed by
+    (workgroup = u // 256, slice = item // width); a workgroup's slices together are its stream.
     The slices only order the stream (the kernel never sees them), so they are fine: ~512 KB of V rows each."""
 
-    PAD = -2 ** 31
-
     def __init__(self, plan, wplan, n_components, dtype=torch.float32, slice_bytes=None):
-        lib = _lib.get()
+        lib = _lib.load_library()   # like Scores6Plan: the builder itself needs no GPU
         dev = plan.col_u.device
         self.key = (int(n_components), dtype)   # what the streams were built for (the slice width follows the row bytes)
         UB = int(lib.tmf_wmrb_scores5_users_per_workgroup())
-        m, S = wplan.R.shape
-        nnz, n = plan.nnz, plan.n_items
-        E = nnz + m * S
-        self.n_wg = n_wg = -(-m // UB)
-        row_bytes = _lib.padded_ld(n_components, dtype) * (2 if dtype is torch.bfloat16 else 4)
+        n = plan.n_items
+        self.n_wg = n_wg = -(-wplan.R.shape[0] // UB)
         slice_bytes = int(os.environ.get('TMF_S5_SLICE_BYTES', slice_bytes or (512 << 10)))
-        ns = int(min(max(1, -(-n * row_bytes // slice_bytes)), 4096, max(1, (2 ** 31 - 1) // max(n_wg, 1))))
+        ns = int(min(max(1, -(-n * row_bytes(n_components, dtype) // slice_bytes)), 4096, max(1, (2 ** 31 - 1) // max(n_wg, 1))))
         width = -(-n // ns)
         self.n_slices = ns
         i32 = torch.int32
-        uo = plan.user_of                                                  # int32 [nnz]
-        rows = torch.arange(m, device=dev, dtype=i32)
-        keys = torch.empty(E, dtype=i32, device=dev)
-        keys[:nnz] = (uo // UB) * ns + plan.col_u // width
-        keys[nnz:].view(m, S).copy_(((rows // UB) * ns)[:, None] + wplan.R // width)
-        perm, rowptr = stable_order(keys, n_wg * ns)
-        del keys
-        packed = torch.empty(E, dtype=i32, device=dev)
-        packed[:nnz] = ((uo % UB) << 24) | plan.col_u
-        packed[nnz:].view(m, S).copy_(((rows % UB) << 24)[:, None] | wplan.R)
-        ids_sorted = packed[perm]
-        del packed
-        outs = torch.empty(E, dtype=i32, device=dev)
-        outs[:nnz] = -1 - torch.arange(nnz, device=dev, dtype=i32)         # ~k: the score of interaction k goes to p[k]
-        outs[nnz:] = torch.arange(m * S, device=dev, dtype=i32)            # u * S + pos: to sp[u, pos]
-        outs_sorted = outs[perm]
-        del outs, perm
-        # every workgroup's stream padded to whole steps of 8 with its last entry's id (a valid user, a resident row) and PAD
-        wg_ptr = rowptr[::ns].contiguous()                                  # [n_wg + 1]
-        cnt = wg_ptr[1:] - wg_ptr[:-1]
-        wg_ptr8 = _excl_cumsum((cnt + 7) // 8 * 8)
-        E8 = int(wg_ptr8[-1])
-        self.ids = torch.empty(E8 + 8, dtype=i32, device=dev)
-        self.outs = torch.full((E8 + 8,), self.PAD, dtype=i32, device=dev)
-        self.ids[E8:] = 0
-        step = 1 << 27
-        for q0 in range(0, E8, step):
-            q = torch.arange(q0, min(q0 + step, E8), device=dev, dtype=torch.int64)
-            wg = torch.searchsorted(wg_ptr8, q, right=True) - 1
-            r = q - wg_ptr8[wg]
-            c = cnt[wg]
-            src = wg_ptr[wg] + torch.minimum(r, c - 1)
-            self.ids[q0:q0 + q.numel()] = ids_sorted[src]
-            self.outs[q0:q0 + q.numel()] = torch.where(r < c, outs_sorted[src], torch.full_like(src, self.PAD).to(i32))
-            del q, wg, r, c, src
-        self.wg_ptr = wg_ptr8
-        self.n_entries, self.n_padded = E, E8
+        self.wg_ptr, rowptr = self._build(plan, wplan, UB, lambda wg, item: wg * ns + item // width, n_wg * ns, keys_per_stream=ns)
+        wg_ptr8, wg_ptr = self.wg_ptr, rowptr[::ns]                         # [n_wg + 1] first padded / sorted entry of every workgroup
         # pacing: the workgroups of a launch meet every `pace_every` slices (tmf.h: window w may start when the peers have
         # completed window w - lag - 1; lag 0 = a barrier per window) and run freely in between - equal work per slice keeps them
         # within a slice or two of each other over such a stretch, a rendezvous per slice would cost more than a slice takes.
@@ -769,7 +727,7 @@ class TrainState:
         self.plan, self.wplan = plan, wplan
         need = dict(slab=max(plan.seg_u.n_slab, plan.seg_i.n_slab if plan.seg_i else 0,
                              wplan.seg_e.n_slab if wplan is not None and wplan.seg_e is not None else 0,
-                             wplan.vrows.n_slab if wplan is not None and getattr(wplan, 'vrows', None) is not None else 0, 1) * self.ld,
+                             wplan.vrows.n_slab if wplan is not None and wplan.vrows is not None else 0, 1) * self.ld,
                     loss_part=max(plan.seg_u.nseg, plan.n_users, 1))
         self.row_stationary = False
         if wplan is not None and wplan.sliced:
@@ -789,14 +747,13 @@ class TrainState:
             else:
                 self.part_layers, self.gradu_launches = 1, 1           # a launch per slice
             need.update(sp=m * S, pk=max(plan.nnz, 1), part=self.part_layers * max(m, 1) * self.ld)
-            wplan.s6 = getattr(wplan, 's6', None)
             if scores6_wanted(plan, wplan, self.r, dtype):
                 if wplan.s6 is None or wplan.s6.key != (self.r, dtype):
                     wplan.s6 = Scores6Plan(plan, wplan, self.r, dtype)
             else:
                 wplan.s6 = None
             if wplan.seg_e is not None and scores5_wanted(plan, wplan, self.r, dtype):
-                if getattr(wplan, 's5', None) is None or wplan.s5.key != (self.r, dtype):
+                if wplan.s5 is None or wplan.s5.key != (self.r, dtype):
                     wplan.s5 = Scores5Plan(plan, wplan, self.r, dtype)
             else:
                 wplan.s5 = None
@@ -870,16 +827,9 @@ def bias_update(side, E, adam, prof=None, tag=''):
     tag: prefix of the three span names under ``prof`` (KernelTimer)."""
     lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
     rows = E.shape[0]
-
-    def timed(name, rc):
-        if prof:
-            prof.start(name)
-        _lib.check(rc(), lib)
-        if prof:
-            prof.stop(name)
-    timed(tag + 'bias_colsum', lambda: lib.tmf_bias_colsum_f32(P(side.G), rows, side.r, P(side.part), side.part_rows, None, s))
-    timed(tag + 'bias_adam', lambda: lib.tmf_bias_adam_f32(P(side.part), side.part_rows, P(side.b), P(side.g_b), side.r, adam, s))
-    timed(tag + 'adam_bias_rows', lambda: lib.tmf_adam_bias_rows_f32(P(side.W), P(side.G), P(side.b), P(E), rows, side.r, adam, s))
+    _timed(prof, tag + 'bias_colsum', lambda: lib.tmf_bias_colsum_f32(P(side.G), rows, side.r, P(side.part), side.part_rows, None, s))
+    _timed(prof, tag + 'bias_adam', lambda: lib.tmf_bias_adam_f32(P(side.part), side.part_rows, P(side.b), P(side.g_b), side.r, adam, s))
+    _timed(prof, tag + 'adam_bias_rows', lambda: lib.tmf_adam_bias_rows_f32(P(side.W), P(side.G), P(side.b), P(E), rows, side.r, adam, s))
 
 
 def epoch_biased(st, adam, loss_out, loss='mse', c=0.0, prof=None):
@@ -888,12 +838,7 @@ def epoch_biased(st, adam, loss_out, loss='mse', c=0.0, prof=None):
     bias and row updates of the biased sides (both passes have read the pre-update tables by then) and the swap of the others."""
     ue, uo = (_lib.EPI_GRAD, st.bias_u.G) if st.bias_u is not None else (_lib.EPI_ADAM, None)
     ie, io = (_lib.EPI_GRAD, st.bias_v.G) if st.bias_v is not None else (_lib.EPI_ADAM, None)
-    if loss == 'wmrb':
-        epoch_wmrb(st, adam, c, loss_out, ie, io, prof, ue, uo)
-    elif loss == 'kl':
-        epoch_kl(st, adam, loss_out, ie, io, prof, ue, uo)
-    else:
-        epoch_mse(st, adam, loss_out, ie, io, prof, ue, uo)
+    run_epoch(st, adam, loss_out, loss, c, ie, io, prof, ue, uo)
     if st.bias_u is not None:
         bias_update(st.bias_u, st.U, adam, prof, 'user_')
     if st.bias_v is not None:
@@ -936,6 +881,30 @@ class KernelTimer:
         return sum(v) / len(v) if v else float('nan')
 
 
+def _timed(prof, name, call):
+    """call() as the span ``name`` of ``prof`` (a KernelTimer, or None).  A launch returns its code, which is checked here; a
+    sequence of launches that checks its own returns None."""
+    if prof:
+        prof.start(name)
+    rc = call()
+    if rc is not None:
+        _lib.check(rc)
+    if prof:
+        prof.stop(name)
+
+
+def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM,
+              user_out=None):
+    """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'kl' or 'mse' - on the state's tables: the ONE place that maps a
+    loss to its epoch.  The other arguments as in epoch_mse."""
+    if loss == 'wmrb':
+        epoch_wmrb(st, adam, c, loss_out, item_epi, item_out, prof, user_epi, user_out)
+    elif loss == 'kl':
+        epoch_kl(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
+    else:
+        epoch_mse(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
+
+
 def _row_pass_finish(lib, seg, slab, X_old, X_out, r, epi, adam, stream, sfx='_f32'):
     if seg.n_long:
         _lib.check(getattr(lib, 'tmf_combine_rows' + sfx)(_lib.ptr(seg.long_rows), _lib.ptr(seg.long_slab_beg), seg.n_long,
@@ -950,23 +919,14 @@ def epoch_mse(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=No
     lib, p, r = _lib.get(), st.plan, st.r
     s = _lib.stream_ptr()
     U_out = st.U_nxt if user_out is None else user_out
-    if prof:
-        prof.start('mse_user_pass')
     mse_pass = getattr(lib, 'tmf_mse_pass' + st.sfx)
-    _lib.check(mse_pass(p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U),
-                                    _lib.ptr(st.V), _lib.ptr(U_out), _lib.ptr(st.slab), _lib.ptr(st.loss_part),
-                                    r, user_epi, adam, s), lib)
-    if prof:
-        prof.stop('mse_user_pass')
+    _timed(prof, 'mse_user_pass', lambda: mse_pass(p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U), _lib.ptr(st.V),
+                                                   _lib.ptr(U_out), _lib.ptr(st.slab), _lib.ptr(st.loss_part), r, user_epi, adam, s))
     _row_pass_finish(lib, p.seg_u, st.slab, st.U, U_out, r, user_epi, adam, s, st.sfx)
     _lib.check(lib.tmf_sum_f32(_lib.ptr(st.loss_part), p.seg_u.nseg, _lib.ptr(loss_out), s), lib)
     V_out = st.V_nxt if item_out is None else item_out
-    if prof:
-        prof.start('mse_item_pass')
-    _lib.check(mse_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(st.V),
-                                    _lib.ptr(st.U), _lib.ptr(V_out), _lib.ptr(st.slab), None, r, item_epi, adam, s), lib)
-    if prof:
-        prof.stop('mse_item_pass')
+    _timed(prof, 'mse_item_pass', lambda: mse_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(st.V), _lib.ptr(st.U),
+                                                   _lib.ptr(V_out), _lib.ptr(st.slab), None, r, item_epi, adam, s))
     _row_pass_finish(lib, p.seg_i, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
 
 
@@ -976,23 +936,16 @@ def epoch_kl(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=Non
     loss_out: 1-element fp64 device tensor receiving the epoch's loss (a scalar).  item_epi / user_epi as in epoch_mse."""
     lib, p, r = _lib.get(), st.plan, st.r
     s = _lib.stream_ptr()
-
-    def timed(name, rc):
-        if prof:
-            prof.start(name)
-        _lib.check(rc(), lib)
-        if prof:
-            prof.stop(name)
     kl_pass = getattr(lib, 'tmf_kl_pass' + st.sfx)
-    timed('kl_moments', lambda: getattr(lib, 'tmf_kl_moments' + st.sfx)(
+    _timed(prof, 'kl_moments', lambda: getattr(lib, 'tmf_kl_moments' + st.sfx)(
         p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(st.kl_part), r, s))
-    timed('kl_coeffs', lambda: lib.tmf_kl_coeffs(_lib.ptr(st.kl_part), p.seg_u.nseg, _lib.ptr(loss_out), _lib.ptr(st.kl_coef), s))
+    _timed(prof, 'kl_coeffs', lambda: lib.tmf_kl_coeffs(_lib.ptr(st.kl_part), p.seg_u.nseg, _lib.ptr(loss_out), _lib.ptr(st.kl_coef), s))
     U_out = st.U_nxt if user_out is None else user_out
-    timed('kl_user_pass', lambda: kl_pass(p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U), _lib.ptr(st.V),
+    _timed(prof, 'kl_user_pass', lambda: kl_pass(p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U), _lib.ptr(st.V),
                                           _lib.ptr(U_out), _lib.ptr(st.slab), _lib.ptr(st.kl_coef), r, user_epi, adam, s))
     _row_pass_finish(lib, p.seg_u, st.slab, st.U, U_out, r, user_epi, adam, s, st.sfx)
     V_out = st.V_nxt if item_out is None else item_out
-    timed('kl_item_pass', lambda: kl_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(st.V), _lib.ptr(st.U),
+    _timed(prof, 'kl_item_pass', lambda: kl_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(st.V), _lib.ptr(st.U),
                                           _lib.ptr(V_out), _lib.ptr(st.slab), _lib.ptr(st.kl_coef), r, item_epi, adam, s))
     _row_pass_finish(lib, p.seg_i, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
 
@@ -1004,41 +957,34 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
     m, S, ns = p.n_users, w.S, w.n_slices
     s = _lib.stream_ptr()
     lists = w.lists(p)
-
-    def timed(name, rc_fn):
-        if prof:
-            prof.start(name)
-        _lib.check(rc_fn(), lib)
-        if prof:
-            prof.stop(name)
-    s5, s6 = getattr(w, 's5', None), getattr(w, 's6', None)
+    s5, s6 = w.s5, w.s6
     if s6 is not None:
         # flat streams on the slice-major grid: one workgroup per (slice, group of 32 users) chunk, the group's rows in LDS
-        timed('wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores6' + st.sfx)(
+        _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores6' + st.sfx)(
             _lib.ptr(s6.ids), _lib.ptr(s6.outs), _lib.ptr(s6.chunk_ptr), s6.n_groups, i32(s6.n_slices), m, p.n_items, _lib.ptr(st.U),
             _lib.ptr(st.V), _lib.ptr(st.sp), _lib.ptr(st.pk), r, s))
     elif s5 is not None:
         # row-stationary scores: workgroups own 256 users (rows in LDS) and walk one flat stream of (user, item) pairs
-        timed('wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores5' + st.sfx)(
+        _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores5' + st.sfx)(
             _lib.ptr(s5.ids), _lib.ptr(s5.outs), _lib.ptr(s5.wg_ptr), s5.n_wg, m, p.n_items, _lib.ptr(st.U), _lib.ptr(st.V),
             _lib.ptr(st.sp), _lib.ptr(st.pk), r, s5.wgs_per_launch, _lib.ptr(s5.wstart) if s5.paced else None, i32(s5.n_windows),
             s5.lag, _lib.ptr(s5.sync) if s5.paced else None, s5.sync.numel() * 4, s))
     else:
-        timed('wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores3' + st.sfx)(lists, _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(st.sp),
+        _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores3' + st.sfx)(lists, _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(st.sp),
                                                                                 _lib.ptr(st.pk), r, s))
-    timed('wmrb_hinge', lambda: lib.tmf_wmrb_hinge2_ordered(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk), _lib.ptr(st.sp),
+    _timed(prof, 'wmrb_hinge', lambda: lib.tmf_wmrb_hinge2_ordered(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk), _lib.ptr(st.sp),
                                                             i32(m), i32(S), c, _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part),
                                                             _lib.ptr(w.hinge_order), s))
     if st.row_stationary:
         # gradU + finish in one row-stationary kernel (lane groups own users and walk the slices; no partial rows)
-        timed('wmrb_gradu', lambda: getattr(lib, 'tmf_wmrb_gradu4' + st.sfx)(
+        _timed(prof, 'wmrb_gradu', lambda: getattr(lib, 'tmf_wmrb_gradu4' + st.sfx)(
             lists, _lib.ptr(w.D), _lib.ptr(w.delta), _lib.ptr(st.V), _lib.ptr(st.U), _lib.ptr(st.U_nxt if U_out is None else U_out),
             r, user_epi, adam, i32(st.users_per_launch), _lib.ptr(st.g4_sync), st.g4_sync.numel() * 4, s))
         return
-    timed('wmrb_gradu', lambda: getattr(lib, 'tmf_wmrb_gradu3' + st.sfx)(
+    _timed(prof, 'wmrb_gradu', lambda: getattr(lib, 'tmf_wmrb_gradu3' + st.sfx)(
         lists, _lib.ptr(w.D), _lib.ptr(w.delta), _lib.ptr(st.V), _lib.ptr(st.part),
         st.gradu_launches, r, s))
-    timed('wmrb_finish', lambda: getattr(lib, 'tmf_wmrb_finish' + st.sfx)(_lib.ptr(st.part), i32(st.part_layers), i32(m),
+    _timed(prof, 'wmrb_finish', lambda: getattr(lib, 'tmf_wmrb_finish' + st.sfx)(_lib.ptr(st.part), i32(st.part_layers), i32(m),
                                                                           _lib.ptr(st.U), _lib.ptr(st.U_nxt if U_out is None else U_out),
                                                                           r, user_epi, adam, s))
 
@@ -1047,61 +993,34 @@ def epoch_wmrb(st, adam, c, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, pro
     """One WMRB epoch.  loss_out receives sum over positives of log(1 + M_k).  item_epi / user_epi as in epoch_mse."""
     lib, p, w, r = _lib.get(), st.plan, st.wplan, st.r
     s = _lib.stream_ptr()
-    if prof:
-        prof.start('wmrb_user_pass')
     if w.sliced:
-        _wmrb_user_pass_sliced(lib, st, adam, c, prof, user_epi, user_out)
+        _timed(prof, 'wmrb_user_pass', lambda: _wmrb_user_pass_sliced(lib, st, adam, c, prof, user_epi, user_out))
     else:
-        _lib.check(getattr(lib, 'tmf_wmrb_user_pass' + st.sfx)(_lib.ptr(p.rowptr_u), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(w.R),
-                                              p.n_users, w.S, c, _lib.ptr(st.U), _lib.ptr(st.V),
-                                              _lib.ptr(st.U_nxt if user_out is None else user_out),
-                                              _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part), None,
-                                              r, user_epi, adam, s), lib)
-    if prof:
-        prof.stop('wmrb_user_pass')
+        _timed(prof, 'wmrb_user_pass', lambda: getattr(lib, 'tmf_wmrb_user_pass' + st.sfx)(
+            _lib.ptr(p.rowptr_u), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(w.R), p.n_users, w.S, c, _lib.ptr(st.U), _lib.ptr(st.V),
+            _lib.ptr(st.U_nxt if user_out is None else user_out), _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part), None,
+            r, user_epi, adam, s))
     _lib.check(lib.tmf_sum_f32(_lib.ptr(st.loss_part), p.n_users, _lib.ptr(loss_out), s), lib)
     V_out = st.V_nxt if item_out is None else item_out
-    if w.rows4:
+    i32, v = ctypes.c_int32, w.vrows
+    if not w.rows4:
+        _timed(prof, 'wmrb_item_pass', lambda: getattr(lib, 'tmf_wsum_pass' + st.sfx)(
+            w.seg_e.cstruct(), _lib.ptr(w.ent_row), _lib.ptr(w.ent_w), _lib.ptr(w.wbuf), _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(V_out),
+            _lib.ptr(st.slab), r, item_epi, adam, s))
+        _timed(prof, 'wmrb_combine', lambda: _row_pass_finish(lib, w.seg_e, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx))
+    elif v is not None:
         # row-stationary item pass: lane groups own (virtual) rows and walk the user blocks; no slab but for the parts of cut rows
-        if prof:
-            prof.start('wmrb_item_pass')
-        i32 = ctypes.c_int32
-        if w.vrows is not None:
-            v = w.vrows
-            _lib.check(getattr(lib, 'tmf_wsum_rows5' + st.sfx)(_lib.ptr(w.rowptr_e), i32(p.n_items), i32(w.user_chunks), _lib.ptr(w.ent_row),
-                                                               _lib.ptr(w.ent_w), _lib.ptr(w.wbuf), _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(V_out),
-                                                               _lib.ptr(st.slab), _lib.ptr(v.item), _lib.ptr(v.part), _lib.ptr(v.nparts),
-                                                               _lib.ptr(v.slot), i32(v.n_vrows), r, item_epi, adam, i32(st.rows4_per_launch),
-                                                               _lib.ptr(st.rows4_sync), st.rows4_sync.numel() * 4, s), lib)
-        else:
-            _lib.check(getattr(lib, 'tmf_wsum_rows4' + st.sfx)(_lib.ptr(w.rowptr_e), i32(p.n_items), i32(w.user_chunks),
-                                                               _lib.ptr(w.ent_row), _lib.ptr(w.ent_w), _lib.ptr(w.wbuf), _lib.ptr(st.U),
-                                                               _lib.ptr(st.V), _lib.ptr(V_out), r, item_epi, adam,
-                                                               i32(st.rows4_per_launch), _lib.ptr(st.rows4_sync),
-                                                               st.rows4_sync.numel() * 4, s), lib)
-        if prof:
-            prof.stop('wmrb_item_pass')
-        if w.vrows is not None and w.vrows.n_long:
-            if prof:
-                prof.start('wmrb_combine')
-            v = w.vrows
-            _lib.check(getattr(lib, 'tmf_combine_rows' + st.sfx)(_lib.ptr(v.long_rows), _lib.ptr(v.long_slab_beg), v.n_long, _lib.ptr(st.slab),
-                                                                 _lib.ptr(st.V), _lib.ptr(V_out), r, item_epi, adam, s), lib)
-            if prof:
-                prof.stop('wmrb_combine')
-        return
-    if prof:
-        prof.start('wmrb_item_pass')
-    _lib.check(getattr(lib, 'tmf_wsum_pass' + st.sfx)(w.seg_e.cstruct(), _lib.ptr(w.ent_row), _lib.ptr(w.ent_w), _lib.ptr(w.wbuf),
-                                     _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(V_out), _lib.ptr(st.slab), r, item_epi,
-                                     adam, s), lib)
-    if prof:
-        prof.stop('wmrb_item_pass')
-    if prof:
-        prof.start('wmrb_combine')
-    _row_pass_finish(lib, w.seg_e, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
-    if prof:
-        prof.stop('wmrb_combine')
+        _timed(prof, 'wmrb_item_pass', lambda: getattr(lib, 'tmf_wsum_rows5' + st.sfx)(
+            _lib.ptr(w.rowptr_e), i32(p.n_items), i32(w.user_chunks), _lib.ptr(w.ent_row), _lib.ptr(w.ent_w), _lib.ptr(w.wbuf), _lib.ptr(st.U),
+            _lib.ptr(st.V), _lib.ptr(V_out), _lib.ptr(st.slab), _lib.ptr(v.item), _lib.ptr(v.part), _lib.ptr(v.nparts), _lib.ptr(v.slot),
+            i32(v.n_vrows), r, item_epi, adam, i32(st.rows4_per_launch), _lib.ptr(st.rows4_sync), st.rows4_sync.numel() * 4, s))
+        if v.n_long:   # the cut rows: their parts' slab slots summed in part order (VirtualRows has a SegmentTable's long-row fields)
+            _timed(prof, 'wmrb_combine', lambda: _row_pass_finish(lib, v, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx))
+    else:
+        _timed(prof, 'wmrb_item_pass', lambda: getattr(lib, 'tmf_wsum_rows4' + st.sfx)(
+            _lib.ptr(w.rowptr_e), i32(p.n_items), i32(w.user_chunks), _lib.ptr(w.ent_row), _lib.ptr(w.ent_w), _lib.ptr(w.wbuf), _lib.ptr(st.U),
+            _lib.ptr(st.V), _lib.ptr(V_out), r, item_epi, adam, i32(st.rows4_per_launch), _lib.ptr(st.rows4_sync),
+            st.rows4_sync.numel() * 4, s))
 
 
 def adam_constants(lr):

@@ -64,10 +64,7 @@ def fit_minibatch(model, epochs, n_users, n_items, interactions, lr, U0, V0, bat
     for epoch in range(epochs):
         for i, st in enumerate(states):
             st.V, st.V_nxt = tables
-            if wmrb:
-                _engine.epoch_wmrb(st, adam, c, sums[epoch, i:i + 1])
-            else:
-                _engine.epoch_mse(st, adam, sums[epoch, i:i + 1])
+            _engine.run_epoch(st, adam, sums[epoch, i:i + 1], 'wmrb' if wmrb else 'mse', c)
             st.U, st.U_nxt = st.U_nxt, st.U
             tables.reverse()                      # the item table this batch wrote is the one the next batch reads
         if model.verbose and (epoch + 1) % 25 == 0:

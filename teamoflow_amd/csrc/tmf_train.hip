@@ -26,6 +26,26 @@ struct SegView {
     int xcd_run;      // k_wsum_pass_pg: consecutive workgroups per XCD run (0 = plain block order)
 };
 
+struct SegRange { int row; int64_t beg, end; };   // the table row a segment's list belongs to, and its entries
+__device__ __forceinline__ SegRange seg_range(const SegView& sv, int64_t seg) {
+    const int lrow = sv.seg_row[seg];
+    const int row = sv.row_mod > 0 ? lrow % sv.row_mod : lrow;
+    const int64_t rbeg = sv.rowptr[lrow], rend = sv.rowptr[lrow + 1];
+    const int64_t beg = rbeg + (int64_t)sv.seg_chunk[seg] * sv.chunk;
+    return SegRange{row, beg, (beg + sv.chunk < rend) ? beg + sv.chunk : rend};
+}
+
+// The end of a segment: its slab slot when the row is cut into several (k_combine_rows), else the epilogue at once.  adam by
+// reference: a copy made here moves the kernels' loads of adam and epi, 2 - 5 instructions more in every instance.
+template <int G, int NV, typename T>
+__device__ __forceinline__ void finish_segment(const SegView& sv, int64_t seg, const Frag<NV>& acc, const T* __restrict__ X_old,
+                                               void* __restrict__ X_out, float* __restrict__ slab, int row, int g, int epi,
+                                               const tmf_adam& adam) {
+    const int slot = sv.seg_slab[seg];
+    if (slot < 0) row_epilogue<G, NV, T>(acc, X_old, X_out, row, g, epi, adam);
+    else store_row_f32<G, NV, T>(acc, slab, slot, g);
+}
+
 // ---------------------------------------------------------------------------------------------
 // MSE pass.  One wave per segment; 64/G groups of G lanes each take every (64/G)-th entry of the
 // segment, kUnroll entries in flight per group.  p_k is reduced over the group with xor shuffles,
@@ -41,11 +61,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_mse_pass(
     const int64_t seg = sv.seg0 + (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     if (seg >= sv.nseg) return;
     const int g = lane & (G - 1), grp = lane / G;
-    const int lrow = sv.seg_row[seg];
-    const int row = sv.row_mod > 0 ? lrow % sv.row_mod : lrow;  // table row this list belongs to
-    const int64_t rbeg = sv.rowptr[lrow], rend = sv.rowptr[lrow + 1];
-    const int64_t beg = rbeg + (int64_t)sv.seg_chunk[seg] * sv.chunk;
-    const int64_t end = (beg + sv.chunk < rend) ? beg + sv.chunk : rend;
+    const auto [row, beg, end] = seg_range(sv, seg);
 
     Frag<NV> x, acc;
     load_row<G, NV>(x, X_old, row, g);
@@ -89,11 +105,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_mse_pass(
         for (int off = 32; off >= 1; off >>= 1) l += __shfl_xor(l, off, 64);
         if (lane == 0) loss_part[seg] = l;
     }
-    if (grp == 0) {
-        const int slot = sv.seg_slab[seg];
-        if (slot < 0) row_epilogue<G, NV, T>(acc, X_old, X_out, row, g, epi, adam);
-        else store_row_f32<G, NV, T>(acc, slab, slot, g);
-    }
+    if (grp == 0) finish_segment<G, NV, T>(sv, seg, acc, X_old, X_out, slab, row, g, epi, adam);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -102,6 +114,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_mse_pass(
 // so an epoch is the walk of k_mse_pass three times: MOMENTS = true sums the six moments of every segment in fp64 and writes
 // no table; after k_kl_coeffs has turned their total into the loss and six coefficients, MOMENTS = false recomputes p_k from
 // the row it gathers anyway and accumulates the gradient row with the weight a_c + b_c (p_k - mu_c) in place of -2 (a_k - p_k).
+// The loop below is a COPY of k_mse_pass's on purpose (shared: seg_range, finish_segment).  One walk_scores<G, NV, T>(.., f) with
+// the per-entry step as a lambda (captured by reference or by value) leaves the MSE instances unchanged but moves the six
+// coefficients of every MOMENTS = false instance from SGPRs to VGPRs: G=16 NV=1 fp32 62 -> 77 VGPRs, G=64 NV=4 fp32 92 -> 119,
+// G=64 NV=4 bf16 118 -> 124, 13 to 38 more instructions each, several across a waves-per-SIMD step - not measured on the GPU.
 // ---------------------------------------------------------------------------------------------
 constexpr int kKlMoments = 6;   // per segment: N+, N-, sum p+, sum p-, sum p^2+, sum p^2-
 
@@ -115,11 +131,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_kl_pass(
     const int64_t seg = sv.seg0 + (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     if (seg >= sv.nseg) return;
     const int g = lane & (G - 1), grp = lane / G;
-    const int lrow = sv.seg_row[seg];
-    const int row = sv.row_mod > 0 ? lrow % sv.row_mod : lrow;
-    const int64_t rbeg = sv.rowptr[lrow], rend = sv.rowptr[lrow + 1];
-    const int64_t beg = rbeg + (int64_t)sv.seg_chunk[seg] * sv.chunk;
-    const int64_t end = (beg + sv.chunk < rend) ? beg + sv.chunk : rend;
+    const auto [row, beg, end] = seg_range(sv, seg);
 
     Frag<NV> x, acc;
     load_row<G, NV>(x, X_old, row, g);
@@ -178,11 +190,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_kl_pass(
         }
     } else {
         across_groups_sum<G, NV>(acc);
-        if (grp == 0) {
-            const int slot = sv.seg_slab[seg];
-            if (slot < 0) row_epilogue<G, NV, T>(acc, X_old, X_out, row, g, epi, adam);
-            else store_row_f32<G, NV, T>(acc, slab, slot, g);
-        }
+        if (grp == 0) finish_segment<G, NV, T>(sv, seg, acc, X_old, X_out, slab, row, g, epi, adam);
     }
 }
 
@@ -322,11 +330,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_wsum_pass(
         }
     }
     across_groups_sum<G, NV>(acc);
-    if (grp == 0) {
-        const int slot = sv.seg_slab[seg];
-        if (slot < 0) row_epilogue<G, NV, T>(acc, X_old, X_out, row, g, epi, adam);
-        else store_row_f32<G, NV, T>(acc, slab, slot, g);
-    }
+    if (grp == 0) finish_segment<G, NV, T>(sv, seg, acc, X_old, X_out, slab, row, g, epi, adam);
 }
 
 // One lane GROUP per segment instead of one wave: the 64/G groups of a wave walk 64/G different segments (two 69-entry lists
@@ -397,11 +401,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_wsum_pass_pg(
             }
         }
     }
-    if (live) {
-        const int slot = sv.seg_slab[seg];
-        if (slot < 0) row_epilogue<G, NV, T>(acc, X_old, X_out, row, g, epi, adam);
-        else store_row_f32<G, NV, T>(acc, slab, slot, g);
-    }
+    if (live) finish_segment<G, NV, T>(sv, seg, acc, X_old, X_out, slab, row, g, epi, adam);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -643,6 +643,15 @@ static inline SegView view(const tmf_segments* s) {
     return SegView{s->rowptr, s->seg_row, s->seg_chunk, s->seg_slab, s->nseg, s->chunk, s->row_mod, 0, 0};
 }
 
+// A launch carries < 2^32 work-items (tmf::launch_fits): the segments go out in pieces of kMaxBlocks workgroups, sv.seg0 first
+template <typename F>
+static void for_segment_pieces(SegView& sv, int64_t segs_per_block, F&& launch) {
+    for (sv.seg0 = 0; sv.seg0 < sv.nseg; sv.seg0 += kMaxBlocks * segs_per_block) {
+        const int64_t want = (sv.nseg - sv.seg0 + segs_per_block - 1) / segs_per_block;
+        launch((unsigned)(want < kMaxBlocks ? want : kMaxBlocks));
+    }
+}
+
 static int check_segments(const tmf_segments* s) {
     TMF_REQUIRE(s != nullptr, "segments is null");
     TMF_REQUIRE(s->nseg >= 0 && s->chunk > 0, "segments: nseg=%lld chunk=%d", (long long)s->nseg, s->chunk);
@@ -664,17 +673,13 @@ static int mse_pass_impl(const tmf_segments* seg, const int32_t* other, const fl
     TMF_REQUIRE(epi == TMF_EPI_ADAM || epi == TMF_EPI_GRAD, "mse_pass: bad epilogue %d", epi);
     const RowGeom geom = row_geom_of<T>(n_components);
     SegView sv = view(seg);
-    // a launch carries < 2^32 work-items (tmf::launch_fits): the segment list goes out in pieces of kMaxBlocks workgroups
-    for (sv.seg0 = 0; sv.seg0 < seg->nseg; sv.seg0 += kMaxBlocks * kWavesPerBlock) {
-        const int64_t left = seg->nseg - sv.seg0;
-        const int64_t want = (left + kWavesPerBlock - 1) / kWavesPerBlock;
-        const unsigned blocks = (unsigned)(want < kMaxBlocks ? want : kMaxBlocks);
-#define CALL(G_, NV_)                                                                                          \
-    hipLaunchKernelGGL((k_mse_pass<G_, NV_, T>), dim3(blocks), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, \
-                       sv, other, val, (const T*)X_old, (const T*)Y_old, X_out, slab, loss_part, epi, adam)
-        TMF_DISPATCH(T, geom, CALL);
+#define CALL(G_, NV_) \
+    for_segment_pieces(sv, kWavesPerBlock, [&](unsigned blocks) { \
+        hipLaunchKernelGGL((k_mse_pass<G_, NV_, T>), dim3(blocks), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, \
+                           sv, other, val, (const T*)X_old, (const T*)Y_old, X_out, slab, loss_part, epi, adam); \
+    })
+    TMF_DISPATCH(T, geom, CALL);
 #undef CALL
-    }
     return check_launch("tmf_mse_pass");
 }
 
@@ -696,15 +701,13 @@ static int kl_pass_impl(const tmf_segments* seg, const int32_t* other, const flo
     }
     const RowGeom geom = row_geom_of<T>(n_components);
     SegView sv = view(seg);
-    for (sv.seg0 = 0; sv.seg0 < seg->nseg; sv.seg0 += kMaxBlocks * kWavesPerBlock) {   // pieces of < 2^32 work-items
-        const int64_t want = (seg->nseg - sv.seg0 + kWavesPerBlock - 1) / kWavesPerBlock;
-        const unsigned blocks = (unsigned)(want < kMaxBlocks ? want : kMaxBlocks);
-#define CALL(G_, NV_)                                                                                                      \
-    hipLaunchKernelGGL((k_kl_pass<G_, NV_, T, MOMENTS>), dim3(blocks), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, sv, \
-                       other, val, (const T*)X_old, (const T*)Y_old, X_out, slab, part, coef, epi, adam)
-        TMF_DISPATCH(T, geom, CALL);
+#define CALL(G_, NV_) \
+    for_segment_pieces(sv, kWavesPerBlock, [&](unsigned blocks) { \
+        hipLaunchKernelGGL((k_kl_pass<G_, NV_, T, MOMENTS>), dim3(blocks), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, \
+                           sv, other, val, (const T*)X_old, (const T*)Y_old, X_out, slab, part, coef, epi, adam); \
+    })
+    TMF_DISPATCH(T, geom, CALL);
 #undef CALL
-    }
     return check_launch(what);
 }
 
@@ -759,27 +762,23 @@ static int wsum_pass_impl(const tmf_segments* seg, const int32_t* ent_row, const
             // 1024: 30.9, 2048: 31.4, 8192: 32.0 (profiles/r03_c5_experiments.txt item 8).  TMF_WSUM_XCD_RUN overrides (A/B runs).
             sv.xcd_run = (seg->nseg / per_block >= 4 * 8 * 512) ? 512 : 0;
             if (const char* xr = getenv("TMF_WSUM_XCD_RUN")) sv.xcd_run = atoi(xr);
-            for (sv.seg0 = 0; sv.seg0 < seg->nseg; sv.seg0 += kMaxBlocks * per_block) {   // pieces of < 2^32 work-items
-                const int64_t want = (seg->nseg - sv.seg0 + per_block - 1) / per_block;
-                const unsigned pblocks = (unsigned)(want < kMaxBlocks ? want : kMaxBlocks);
-#define CALLPG(G_, NV_)                                                                                               \
-    hipLaunchKernelGGL((k_wsum_pass_pg<G_, NV_, T>), dim3(pblocks), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, \
-                       sv, ent_row, ent_w, wbuf, (const T*)Tab, (const T*)X_old, X_out, slab, epi, adam)
-                TMF_DISPATCH(T, geom, CALLPG);
+#define CALLPG(G_, NV_) \
+    for_segment_pieces(sv, per_block, [&](unsigned blocks) { \
+        hipLaunchKernelGGL((k_wsum_pass_pg<G_, NV_, T>), dim3(blocks), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, \
+                           sv, ent_row, ent_w, wbuf, (const T*)Tab, (const T*)X_old, X_out, slab, epi, adam); \
+    })
+            TMF_DISPATCH(T, geom, CALLPG);
 #undef CALLPG
-            }
             return check_launch("tmf_wsum_pass (per group)");
         }
     }
-    for (sv.seg0 = 0; sv.seg0 < seg->nseg; sv.seg0 += kMaxBlocks * kWavesPerBlock) {   // pieces of < 2^32 work-items
-        const int64_t want = (seg->nseg - sv.seg0 + kWavesPerBlock - 1) / kWavesPerBlock;
-        const unsigned blocks = (unsigned)(want < kMaxBlocks ? want : kMaxBlocks);
-#define CALL(G_, NV_)                                                                                           \
-    hipLaunchKernelGGL((k_wsum_pass<G_, NV_, T>), dim3(blocks), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, \
-                       sv, ent_row, ent_w, wbuf, (const T*)Tab, (const T*)X_old, X_out, slab, epi, adam)
-        TMF_DISPATCH(T, geom, CALL);
+#define CALL(G_, NV_) \
+    for_segment_pieces(sv, kWavesPerBlock, [&](unsigned blocks) { \
+        hipLaunchKernelGGL((k_wsum_pass<G_, NV_, T>), dim3(blocks), dim3(64 * kWavesPerBlock), 0, (hipStream_t)stream, \
+                           sv, ent_row, ent_w, wbuf, (const T*)Tab, (const T*)X_old, X_out, slab, epi, adam); \
+    })
+    TMF_DISPATCH(T, geom, CALL);
 #undef CALL
-    }
     return check_launch("tmf_wsum_pass");
 }
 

@@ -57,10 +57,7 @@ class HipBackend:
 
     def local_passes(self):
         """U block updated into st.U_nxt; raw item gradient of this rank's users into self.gV."""
-        if self.loss == 'wmrb':
-            _engine.epoch_wmrb(self.st, self.adam, self.c, self.loss_out, _lib.EPI_GRAD, self.gV, self.prof)
-        else:
-            _engine.epoch_mse(self.st, self.adam, self.loss_out, _lib.EPI_GRAD, self.gV, self.prof)
+        _engine.run_epoch(self.st, self.adam, self.loss_out, self.loss, self.c, _lib.EPI_GRAD, self.gV, self.prof)
         return self.gV, self.loss_out
 
     def adam_rows(self, W_rows, G_rows):

@@ -165,9 +165,8 @@ class MatrixFactorization:
         t_plan = timeit.default_timer()
         if interactions.device != dev:
             interactions = interactions.to(dev)
-        wmrb = isinstance(self.loss_graph, WMRBLoss)
-        kl = type(self.loss_graph) is KLDivergenceLoss
-        if wmrb and self.random_ind is None:
+        loss = 'wmrb' if isinstance(self.loss_graph, WMRBLoss) else 'kl' if type(self.loss_graph) is KLDivergenceLoss else 'mse'
+        if loss == 'wmrb' and self.random_ind is None:
             raise SampleTableMissing('WMRBLoss needs generate_sample=True (random_ind is None)')
         if getattr(self, 'batch_users', 0):
             if getattr(self, 'shard_items', 0) or self.data_parallel:
@@ -175,23 +174,39 @@ class MatrixFactorization:
             from .. import _minibatch
             _minibatch.fit_minibatch(self, epochs, n_users, n_items, interactions, lr, U0, V0, self.batch_users)
             return True
-        if getattr(self, 'shard_items', 0):
+        if getattr(self, 'shard_items', 0) or self._data_parallel_active():
             from .. import dist as tdist
-            tdist.fit_item_sharded(self, epochs, n_users, n_items, interactions, lr, U0, V0, windows_per_rank=int(self.shard_items))
+            if getattr(self, 'shard_items', 0):
+                tdist.fit_item_sharded(self, epochs, n_users, n_items, interactions, lr, U0, V0, windows_per_rank=int(self.shard_items))
+            else:
+                tdist.fit_data_parallel(self, epochs, n_users, n_items, interactions, lr, U0, V0)
             return True
-        if self._data_parallel_active():
-            from .. import dist as tdist
-            tdist.fit_data_parallel(self, epochs, n_users, n_items, interactions, lr, U0, V0)
-            return True
-        ld = _lib.padded_ld(self.n_components, self.factor_dtype)
+        st, c = self._sparse_state(loss, n_users, n_items, interactions, U0, V0, dev)
+        if st is None:
+            return False   # an empty class: no moments to take (the reference's arithmetic gives NaN; the generic path keeps that)
+        denom = st.plan.n_pos if loss == 'wmrb' else 1 if loss == 'kl' else st.plan.nnz   # KL: the loss is one scalar, its mean is itself
+        self.loss_history_ = []
+        step = self._sparse_step(st, loss, c, lr)
+        # Launch-bound problems (a few hundred microseconds of kernels per epoch): capture an even number of
+        # epochs into one hipGraph and replay it - the per-launch host cost disappears from the loop.
+        work = st.plan.nnz + (st.plan.n_users * st.wplan.S if loss == 'wmrb' else 0)
+        G = min(epochs - epochs % 2, GRAPH_EPOCHS)
+        use_graph = G >= 4 and work <= GRAPH_MAX_WORK and os.environ.get('TMF_NO_GRAPH') is None and self.optimizer != 'adam'
+        sums = self._run_epochs(step, epochs, G if use_graph else 0, denom, dev, t_plan).cpu().numpy()
+        self.loss_history_ = (sums / denom if denom else np.full(epochs, np.nan)).tolist()
+        self._publish_sparse(st)
+        return True
+
+    def _sparse_state(self, loss, n_users, n_items, interactions, U0, V0, dev):
+        """(TrainState, c) of a single-GPU full-batch fit: the interaction plan, for WMRB the checked negative table, its plan and
+        c = n_items / n_samples, and the starting bias of a BiasedLinearEmbedding side.  (None, 0.0) for KL with an empty class."""
+        wmrb, kl = loss == 'wmrb', loss == 'kl'
         plan = _engine.InteractionPlan(interactions.indices, interactions.values, n_users, n_items,
                                        user_chunks=1 if wmrb else _engine.mse_user_chunks(), csc=not wmrb)
         if kl and (plan.n_pos == 0 or int((plan.val_u <= 0).sum()) == 0):
-            return False   # an empty class: no moments to take (the reference's arithmetic gives NaN; the generic path keeps that)
+            return None, 0.0
         wplan, c = None, 0.0
         if wmrb:
-            if self.random_ind is None:
-                raise SampleTableMissing('WMRBLoss needs generate_sample=True (random_ind is None)')
             R = torch.as_tensor(self.random_ind).to(device=dev, dtype=torch.int32).contiguous()
             if R.dim() != 2 or R.shape[0] != n_users:
                 raise ValueError(f'random_ind has shape {tuple(R.shape)}, expected [{n_users}, n_samples]')
@@ -201,65 +216,50 @@ class MatrixFactorization:
             wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype)
         r = self.n_components
         # a biased side starts from the bias an earlier fit left on the model, as in the reference (:139-146), else from zeros
-        bias0 = [None, None]
-        for i, (graph, kept) in enumerate(((self.user_repr_graph, self.user_linear_bias), (self.item_repr_graph, self.item_linear_bias))):
-            if type(graph) is BiasedLinearEmbedding:
-                bias0[i] = torch.zeros(r) if kept is None else kept
-        biased = bias0[0] is not None or bias0[1] is not None
-        st = _engine.TrainState(U0, V0, plan, r, wplan, dtype=self.factor_dtype, kl=kl, user_bias=bias0[0], item_bias=bias0[1])
+        bias0 = [None if type(graph) is not BiasedLinearEmbedding else torch.zeros(r) if kept is None else kept
+                 for graph, kept in ((self.user_repr_graph, self.user_linear_bias), (self.item_repr_graph, self.item_linear_bias))]
+        return _engine.TrainState(U0, V0, plan, r, wplan, dtype=self.factor_dtype, kl=kl, user_bias=bias0[0], item_bias=bias0[1]), c
+
+    def _sparse_step(self, st, loss, c, lr):
+        """step(epoch, out): one epoch, its loss sum into ``out``, by the reference's fresh Adam or by optimizer='adam' (kept moments)."""
         adam = _engine.adam_constants(lr)
-        loss_sums = torch.zeros(max(epochs, 1), dtype=torch.float64, device=dev)
-        denom = plan.n_pos if wmrb else 1 if kl else plan.nnz   # KL: the loss is one scalar, its mean is itself
-        self.loss_history_ = []
         if self.optimizer not in ('fresh_adam', 'adam'):
             raise ValueError(f"optimizer={self.optimizer!r}: 'fresh_adam' (the reference's behaviour) or 'adam'")
-        persistent = self.optimizer == 'adam'
-        if persistent:
-            if self.factor_dtype is not torch.float32:
-                raise ValueError("optimizer='adam' (persistent moments) needs float32 factor tables")
-            lib = _lib.get()
-            gU, gV = torch.empty_like(st.U), torch.empty_like(st.V)
-            mom = [torch.zeros_like(st.U), torch.zeros_like(st.U), torch.zeros_like(st.V), torch.zeros_like(st.V)]
+        if self.optimizer == 'fresh_adam':
+            if st.bias_u is not None or st.bias_v is not None:
+                return lambda epoch, out: _engine.epoch_biased(st, adam, out, loss, c)
 
-        def run_epoch(epoch, out):
-            if persistent:  # raw gradients of both sides from the pre-update tables, then one Adam step with state, in place
-                a = lib.tmf_adam_step(float(lr), epoch + 1)
-                if wmrb:
-                    _engine.epoch_wmrb(st, a, c, out, _lib.EPI_GRAD, gV, None, _lib.EPI_GRAD, gU)
-                elif kl:
-                    _engine.epoch_kl(st, a, out, _lib.EPI_GRAD, gV, None, _lib.EPI_GRAD, gU)
-                else:
-                    _engine.epoch_mse(st, a, out, _lib.EPI_GRAD, gV, None, _lib.EPI_GRAD, gU)
-                for W, G, M, V2 in ((st.U, gU, mom[0], mom[1]), (st.V, gV, mom[2], mom[3])):
-                    _lib.check(lib.tmf_adam_state_rows_f32(_lib.ptr(W), _lib.ptr(G), _lib.ptr(M), _lib.ptr(V2), W.shape[0],
-                                                           self.n_components, a, _lib.stream_ptr()), lib)
-                return
-            if biased:
-                _engine.epoch_biased(st, adam, out, 'wmrb' if wmrb else 'kl' if kl else 'mse', c)
-                return
-            if wmrb:
-                _engine.epoch_wmrb(st, adam, c, out)
-            elif kl:
-                _engine.epoch_kl(st, adam, out)
-            else:
-                _engine.epoch_mse(st, adam, out)
-            st.swap()
+            def fresh(epoch, out):
+                _engine.run_epoch(st, adam, out, loss, c)
+                st.swap()
+            return fresh
+        if self.factor_dtype is not torch.float32:
+            raise ValueError("optimizer='adam' (persistent moments) needs float32 factor tables")
+        lib = _lib.get()
+        gU, gV = torch.empty_like(st.U), torch.empty_like(st.V)
+        sides = [(W, G, torch.zeros_like(W), torch.zeros_like(W)) for W, G in ((st.U, gU), (st.V, gV))]   # table, gradient, m, v
 
-        # Launch-bound problems (a few hundred microseconds of kernels per epoch): capture an even number of
-        # epochs into one hipGraph and replay it - the per-launch host cost disappears from the loop.
-        work = plan.nnz + (plan.n_users * wplan.S if wmrb else 0)
-        G = min(epochs - epochs % 2, GRAPH_EPOCHS)
-        use_graph = G >= 4 and work <= GRAPH_MAX_WORK and os.environ.get('TMF_NO_GRAPH') is None and not persistent
+        def persistent(epoch, out):   # raw gradients of both sides from the pre-update tables, then one Adam step with state, in place
+            a = lib.tmf_adam_step(float(lr), epoch + 1)
+            _engine.run_epoch(st, a, out, loss, c, _lib.EPI_GRAD, gV, None, _lib.EPI_GRAD, gU)
+            for W, G, M, V2 in sides:
+                _lib.check(lib.tmf_adam_state_rows_f32(_lib.ptr(W), _lib.ptr(G), _lib.ptr(M), _lib.ptr(V2), W.shape[0],
+                                                       self.n_components, a, _lib.stream_ptr()), lib)
+        return persistent
+
+    def _run_epochs(self, step, epochs, G, denom, dev, t_plan):
+        """step(epoch, out) for every epoch (G > 0: replays of one hipGraph of G epochs, then the rest), reports and timings.  -> loss sums."""
+        loss_sums = torch.zeros(max(epochs, 1), dtype=torch.float64, device=dev)
         torch.cuda.synchronize(dev)
         t0 = timeit.default_timer()
         self.plan_seconds_ = t0 - t_plan  # extension: index structures + table set-up of this fit (once, not per epoch)
         done = 0
-        if use_graph:
+        if G:
             block = torch.zeros(G, dtype=torch.float64, device=dev)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 for e in range(G):
-                    run_epoch(e, block[e:e + 1])
+                    step(e, block[e:e + 1])
             # capture only records; the tables are still the initial ones (G is even: buffers line up again)
             t_prev = timeit.default_timer() - t0
             while done + G <= epochs:
@@ -278,28 +278,27 @@ class MatrixFactorization:
                     if t_now is not None:
                         t_prev = t_now
         for epoch in range(done, epochs):
-            run_epoch(epoch, loss_sums[epoch:epoch + 1])
+            step(epoch, loss_sums[epoch:epoch + 1])
             if self.verbose and (epoch + 1) % 25 == 0:
                 loss = float(loss_sums[epoch]) / denom if denom else float('nan')  # syncs
                 self._report(epoch, loss, timeit.default_timer() - t0)
         torch.cuda.synchronize(dev)
         self.fit_seconds_ = timeit.default_timer() - t0
-        sums = loss_sums[:epochs].cpu().numpy()
-        self.loss_history_ = (sums / denom if denom else np.full(epochs, np.nan)).tolist()
+        return loss_sums[:epochs]
+
+    def _publish_sparse(self, st):
+        """What a fit leaves on the model: the tables, and for a biased side what _fit_generic leaves - [weights, bias], the [1, r]
+        bias kept on the model, a leaf that requires grad because a later generic fit differentiates with respect to it."""
+        r = self.n_components
         self._state = st
-        self.user_embedding = st.U[:, :r]
-        self.item_embedding = st.V[:, :r]
-        self.user_trainable = [self.user_embedding]
-        self.item_trainable = [self.item_embedding]
-        # a biased side leaves what _fit_generic leaves: [weights, bias], the [1, r] bias kept on the model - a leaf that requires
-        # grad, because a later generic fit differentiates with respect to it
+        self.user_embedding, self.item_embedding = st.U[:, :r], st.V[:, :r]
+        self.user_trainable, self.item_trainable = [self.user_embedding], [self.item_embedding]
         if st.bias_u is not None:
             self.user_linear_bias = st.bias_u.b[:r].clone().view(1, r).requires_grad_(True)
             self.user_trainable = [st.bias_u.W[:, :r], self.user_linear_bias]
         if st.bias_v is not None:
             self.item_linear_bias = st.bias_v.b[:r].clone().view(1, r).requires_grad_(True)
             self.item_trainable = [st.bias_v.W[:, :r], self.item_linear_bias]
-        return True
 
     def _fit_generic(self, epochs, user_features, item_features, interactions, lr, U, V):
         """The reference's dense loop (:128-187) over arbitrary plug-ins, differentiated by autograd."""

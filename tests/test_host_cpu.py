@@ -376,3 +376,76 @@ def test_no_preprocessor_conditionals_in_the_kernel_sources():
         with open(os.path.join(csrc, name)) as fh:
             found += [f'{name}:{no}: {line.rstrip()}' for no, line in enumerate(fh, 1) if conditional.match(line)]
     assert not found, '\n'.join(found)
+
+
+def test_segment_table_of_rows_equals_the_out_row_table():
+    """SegmentTable.of_rows over ALL list rows in order is the table SegmentTable(..., out_row=..) builds: both number the slab slots
+    with one function.  Rows of 0, 1, chunk, chunk + 1 and 3 chunk entries, 2 user blocks over 5 items (list row = block * 5 + item)."""
+    from teamoflow_amd._engine import SegmentTable, _excl_cumsum
+    chunk, n_out = 4, 5
+    lens = torch.tensor([0, 1, chunk, chunk + 1, 3 * chunk, 3 * chunk, chunk + 1, chunk, 1, 0])
+    rowptr = _excl_cumsum(lens)
+    out_row = torch.arange(lens.numel()) % n_out
+    a = SegmentTable(rowptr, chunk, out_row=out_row, n_out=n_out)
+    b = SegmentTable.of_rows(rowptr, torch.arange(lens.numel()), out_row, n_out, chunk=chunk)
+    assert a.nseg == b.nseg == a.n_slab == b.n_slab == 16                      # 1 + 1 + 1 + 2 + 3 segments per block
+    for name in ('seg_row', 'seg_chunk', 'seg_slab', 'long_slab_beg'):
+        x, y = getattr(a, name), getattr(b, name)
+        assert x.dtype == y.dtype and torch.equal(x, y), name
+    assert a.long_slab_beg.tolist() == [0, 4, 7, 9, 12, 16]    # slots output-row-major: items of 1 + 3, 1 + 2, 1 + 1, 2 + 1, 3 + 1 segments
+    assert sorted(a.seg_slab.tolist()) == list(range(16))
+
+
+@pytest.mark.parametrize('m', [70, 600])   # one workgroup of 256 users; three of them
+def test_scores5_entry_streams_on_the_host(m, monkeypatch):
+    """_engine.Scores5Plan (the streams tmf_wmrb_scores5 walks), built on CPU tensors - what test_scores6_entry_streams_on_the_host
+    asserts for Scores6Plan: every interaction and every negative appears exactly once among the non-PAD entries, in the stream of
+    its workgroup, with the right packed id and place; inside a workgroup by slice, then interactions before negatives, each by user
+    and item; every workgroup's stream is a whole number of steps of 8 and its pads repeat the stream's last id."""
+    from teamoflow_amd import _engine as E, _lib
+    monkeypatch.setenv('TMF_S5_PACE_EVERY', '2')
+    for name in ('TMF_S5_SLICE_BYTES', 'TMF_S5_PACE', 'TMF_S5_WGS'):
+        monkeypatch.delenv(name, raising=False)
+    g = torch.Generator().manual_seed(5)
+    n, r, S = 900, 128, 8
+    key = torch.unique(torch.randint(0, m, (2500,), generator=g) * n + torch.randint(0, n, (2500,), generator=g))
+    idx = torch.stack([key // n, key % n], 1)
+    val = torch.randint(-1, 6, (key.numel(),), generator=g).float()
+    R = torch.stack([torch.randperm(n, generator=g)[:S] for _ in range(m)]).to(torch.int32)
+    plan = E.InteractionPlan(idx, val, m, n)
+    wplan = E.WmrbPlan(plan, R, item_slices=3, n_components=r, sliced=True)
+    s5 = E.Scores5Plan(plan, wplan, r, torch.float32, slice_bytes=100 * 512)      # slices of 100 items: 9 of them
+    UB = _lib.load_library().tmf_wmrb_scores5_users_per_workgroup()
+    n_wg, ns = s5.n_wg, s5.n_slices
+    assert n_wg == -(-m // UB) and ns == 9 and s5.wg_ptr.numel() == n_wg + 1 and s5.key == (r, torch.float32)
+    width = -(-n // ns)
+    ptr, ids, outs = s5.wg_ptr.tolist(), s5.ids.tolist(), s5.outs.tolist()
+    assert ptr[0] == 0 and all(p % 8 == 0 for p in ptr) and ptr[-1] == s5.n_padded and len(ids) == len(outs) == s5.n_padded + 8
+    assert s5.n_entries == plan.nnz + m * S and all(o == E.Scores5Plan.PAD for o in outs[s5.n_padded:])
+    Rs, user_of, col = wplan.R.tolist(), plan.user_of.tolist(), plan.col_u.tolist()
+    seen_neg, seen_pos = set(), set()
+    for wg in range(n_wg):
+        real = [(ids[e], outs[e]) for e in range(ptr[wg], ptr[wg + 1]) if outs[e] != E.Scores5Plan.PAD]
+        pads = [e for e in range(ptr[wg], ptr[wg + 1]) if outs[e] == E.Scores5Plan.PAD]
+        assert real and len(pads) < 8 and all(e >= ptr[wg] + len(real) for e in pads)   # padding sits behind the workgroup's entries
+        assert all(ids[e] == real[-1][0] for e in pads)                                  # ... and repeats the stream's last id
+        order = []
+        for pid, out in real:
+            u, item = wg * UB + ((pid >> 24) & 0xff), pid & 0xffffff
+            assert u < m and item < n
+            if out >= 0:
+                assert Rs[out // S][out % S] == item and out // S == u and out not in seen_neg
+                seen_neg.add(out)
+            else:
+                k = ~out
+                assert user_of[k] == u and col[k] == item and k not in seen_pos
+                seen_pos.add(k)
+            order.append((item // width, int(out >= 0), u, item))
+        assert order == sorted(order)                   # by slice; inside one the interactions, then the negatives; each by user and item
+    assert len(seen_neg) == m * S and len(seen_pos) == plan.nnz
+    # pacing windows (every 2 slices): window 0 is empty, the starts are steps of 8 in stream order, the last one the stream's length
+    ws = s5.wstart.tolist()
+    assert s5.paced and s5.n_windows == 6 and s5.sync.numel() >= 1
+    for wg in range(n_wg):
+        assert len(ws[wg]) == s5.n_windows + 1 and ws[wg][0] == ws[wg][1] == 0 and ws[wg] == sorted(ws[wg])
+        assert ws[wg][-1] == (ptr[wg + 1] - ptr[wg]) // 8
