@@ -472,6 +472,44 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// Stage-time compaction of a weighted entry list (gradU's slice lists, the item pass's entry lists).  One round: every lane of a
+// group of G lanes brings one (id, w) - lanes past the end of the list bring w = 0 - and the entries with w != 0 are appended to
+// ids[] / ws[] at n, n + 1, ... in lane order; n grows by their number.  The place of a lane's entry is the number of non-zero
+// weights on the lanes below it in its group: one ballot and two popcounts, no scan.  All G lanes of a group call it together
+// (groups of a wave may make different numbers of rounds: lanes that are not there vote 0).  -0.f and +0.f are dropped alike; a
+// NaN weight is kept.
+// The gather loops take STEP entries per step, so the list is kept padded to whole steps: the lane that appends a round's last
+// entry also fills the rest of that entry's step with pads, which the next round's entries overwrite (a wave's LDS writes land in
+// program order).  A pad has weight 0 and the id of that last entry: a row the step loads anyway (so it is resident) and whose
+// weight is not 0 - the row of a dropped entry never reaches an accumulator, not even multiplied by 0.  The buffers hold
+// staged_steps(n): their capacity is a multiple of STEP.
+template <int G, int STEP>
+__device__ __forceinline__ void stage_nonzero(int* ids, float* ws, int& n, int id, float w, int g) {
+    const bool nz = w != 0.f;
+    uint64_t b = __builtin_amdgcn_ballot_w64(nz);
+    if constexpr (G < 64) b = (b >> (threadIdx.x & 63 & ~(G - 1))) & ((1ull << G) - 1);
+    if (nz) {
+        const int at = n + __popcll(b & ((1ull << g) - 1));
+        ids[at] = id;
+        ws[at] = w;
+        if ((b >> g) == 1) {   // the last entry kept so far
+#pragma unroll
+            for (int k = 1; k < STEP; ++k) {
+                if ((at & (STEP - 1)) + k < STEP) {
+                    ids[at + k] = id;
+                    ws[at + k] = 0.f;
+                }
+            }
+        }
+    }
+    n += __popcll(b);
+}
+
+template <int STEP>
+__device__ __forceinline__ int staged_steps(int n) {   // entries the gather loop walks: n and its pads
+    return (n + STEP - 1) / STEP * STEP;
+}
+
 // v of lane `idx` of this lane group (ds_bpermute: every lane of the wave has to execute it)
 template <int G>
 __device__ __forceinline__ int group_read(int v, int idx) {

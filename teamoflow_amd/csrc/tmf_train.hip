@@ -265,14 +265,15 @@ __global__ __launch_bounds__(1024) void k_kl_coeffs(const double* __restrict__ p
 // neighbouring lists are served by ONE L2 - changed nothing: 32.8 vs 32.6 ms at C4, profiles/r02_hinge_rewrite.txt.)
 // ---------------------------------------------------------------------------------------------
 constexpr int kWsumTile = 512;  // entries a wave stages in LDS per step (ids + weights: 4 KB per wave)
-// Inner loop of k_wsum_pass_pg: scalar LDS reads and a branch around the load of a zero-weight row.  gradu3's form - the four ids /
-// weights of a step in one ds_read_b128 each, a select to a resident row instead of the branch - was measured on the same box, C4
-// fp32 item pass (two runs each, profiles/r05_item_pass_split.txt): this form 30.40 / 30.40 ms, gradu3's 31.52 / 31.52 ms.  The
-// form with fewer instructions is slower, as the leaner walks of round 4 were: the pass is bound by the rows' way through the
-// texture addresser / L1 (20.4 ms with every row an L1 hit and no weight gather) and by the fabric traffic of the 4-byte weight
-// gathers (+7 ms), not by issue.  That loop, and the timing-only builds that split the pass's time this way, are in
-// profiles/build_time_variants.patch.
+// Entries whose gathered weight is 0 (an inactive hinge term, a positive without an active sample; -0.f counts) are dropped while
+// the tile is staged (stage_nonzero, tmf_common.h): the inner loops have no branch and no select, every row they load is one the sum
+// needs.  A lane group still adds its entries in list order to one running fp32 sum, so for finite tables no bit changes: an
+// accumulator starts at +0 and acc + (0 * row) = acc + (+-0) = acc.  The weight gather wbuf[ent_w[e]] stays in the staging loop - it
+// decides what is kept.  The pass is bound by the rows' way through the texture addresser / L1 (20.4 ms at C4 fp32 with every row an
+// L1 hit and no weight gather) and by the fabric traffic of the 4-byte weight gathers (+7 ms), not by issue
+// (profiles/r05_item_pass_split.txt; the timing-only builds that split the time this way are in profiles/build_time_variants.patch).
 constexpr int kWsumUnroll = 4;  // rows a lane group keeps in flight in k_wsum_pass_pg
+constexpr int kWsumRounds = 4;  // rounds of G entries a lane group stages together in k_wsum_pass_pg
 
 template <int G, int NV, typename T>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void k_wsum_pass(
@@ -293,33 +294,58 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_wsum_pass(
     int* ids = s_ids[wave];
     float* ws = s_w[wave];
 
+    // Lane group `grp` takes entries grp, grp + NG, ... of the tile (class grp), in that order, whether or not others are dropped:
+    // the entries are compacted class by class, class c into its own SUB slots of the tile buffers.  Lane l stages entries of
+    // class l % NG (64 % NG == 0), so a class is the same set of lanes in every round.
+    constexpr int SUB = kWsumTile / NG;
+    constexpr uint64_t kClass0 = NG == 64 ? 1ull : ~0ull / ((1ull << (NG & 63)) - 1);   // lanes 0, NG, 2 NG, ...
+    static_assert(SUB % kUnroll == 0, "a class's slots hold its padded count");
+    const int cls = lane & (NG - 1);
+    const uint64_t in_cls = kClass0 << cls, in_grp = kClass0 << grp, below = (1ull << lane) - 1;
     Frag<NV> acc;
     zero<NV>(acc);
     for (int64_t t0 = beg; t0 < end; t0 += kWsumTile) {
         const int cnt = (int)((end - t0 < kWsumTile) ? end - t0 : kWsumTile);
         // the wave stages the tile: coalesced entry reads, all weight gathers in flight together
-        for (int e = lane; e < cnt; e += 64) {
-            ids[e] = ent_row[t0 + e];
-            ws[e] = wbuf[ent_w[t0 + e]];
+        int n_cls = 0, n = 0;   // entries kept so far of the class this lane stages / of the class its group walks
+        for (int e0 = 0; e0 < cnt; e0 += 64) {
+            const int e = e0 + lane;
+            int id = 0;
+            float w = 0.f;
+            if (e < cnt) {
+                id = ent_row[t0 + e];
+                w = wbuf[ent_w[t0 + e]];
+            }
+            const bool nz = w != 0.f;
+            const uint64_t b = __builtin_amdgcn_ballot_w64(nz);
+            if (nz) {
+                const int at = cls * SUB + n_cls + __popcll(b & in_cls & below);
+                ids[at] = id;
+                ws[at] = w;
+                if (((b & in_cls) >> lane) == 1) {   // the class's last entry so far pads its step (stage_nonzero, tmf_common.h)
+#pragma unroll
+                    for (int k = 1; k < kUnroll; ++k) {
+                        if ((at & (kUnroll - 1)) + k < kUnroll) {
+                            ids[at + k] = id;
+                            ws[at + k] = 0.f;
+                        }
+                    }
+                }
+            }
+            n_cls += __popcll(b & in_cls);
+            n += __popcll(b & in_grp);
         }
+        const int* idg = ids + grp * SUB;
+        const float* wsg = ws + grp * SUB;
+        n = staged_steps<kUnroll>(n);
         wave_lds_sync();
-        // lane group `grp` takes entries grp, grp + NG, ...; a row is only loaded when its weight is not 0
-        for (int e0 = grp; e0 < cnt; e0 += NG * kUnroll) {
+        for (int e0 = 0; e0 < n; e0 += kUnroll) {
             Raw<NV, T> raw[kUnroll];
             float wc[kUnroll];
 #pragma unroll
             for (int t = 0; t < kUnroll; ++t) {
-                const int e = e0 + t * NG;
-                wc[t] = (e < cnt) ? ws[e] : 0.f;
-                if constexpr (std::is_same<T, float>::value) {
-                    // fp32: skipping the load of a zero-weight row measured 0.7 ms faster at C4 than the branch-free form
-                    if (wc[t] != 0.f) load_raw<G, NV>(raw[t], Tab, ids[e], g);
-                    else zero_raw<NV>(raw[t]);
-                } else {
-                    // bf16: no branch around the load (a zero weight reads the tile's first row, an L1 hit, and multiplies it
-                    // by 0) - with a branch the compiler waits for every load before issuing the next
-                    load_raw<G, NV>(raw[t], Tab, ids[wc[t] != 0.f ? e : 0], g);
-                }
+                wc[t] = wsg[e0 + t];
+                load_raw<G, NV>(raw[t], Tab, idg[e0 + t], g);
             }
 #pragma unroll
             for (int t = 0; t < kUnroll; ++t) {
@@ -372,26 +398,38 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_wsum_pass_pg(
     float* ws = s_w[wave] + grp * TILE;
     Frag<NV> acc;
     zero<NV>(acc);
+    static_assert(TILE % kWsumUnroll == 0, "the tile buffers hold the padded count");
     for (int64_t t0 = beg; t0 < end; t0 += TILE) {
         const int cnt = (int)((end - t0 < TILE) ? end - t0 : TILE);
-        for (int e = g; e < cnt; e += G) {   // (non-temporal loads of the entry lists were measured: 30.65 -> 32.7 ms; not used)
-            ids[e] = ent_row[t0 + e];
-            ws[e] = wbuf[ent_w[t0 + e]];
+        int n = 0;   // entries kept so far: the compacted list reuses the tile buffers (n <= cnt)
+        // kWsumRounds rounds of G entries at a time: their entry reads, then their weight gathers, are in flight together
+        // (non-temporal loads of the entry lists were measured: 30.65 -> 32.7 ms; not used)
+        for (int e0 = 0; e0 < cnt; e0 += kWsumRounds * G) {
+            int id[kWsumRounds], iw[kWsumRounds];
+            float w[kWsumRounds];
+#pragma unroll
+            for (int k = 0; k < kWsumRounds; ++k) {
+                const int e = e0 + k * G + g;
+                id[k] = iw[k] = -1;
+                if (e < cnt) {
+                    id[k] = ent_row[t0 + e];
+                    iw[k] = ent_w[t0 + e];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kWsumRounds; ++k) w[k] = iw[k] >= 0 ? wbuf[iw[k]] : 0.f;
+#pragma unroll
+            for (int k = 0; k < kWsumRounds; ++k) stage_nonzero<G, kWsumUnroll>(ids, ws, n, id[k], w[k], g);
         }
+        n = staged_steps<kWsumUnroll>(n);
         wave_lds_sync();
-        for (int e0 = 0; e0 < cnt; e0 += kWsumUnroll) {
+        for (int e0 = 0; e0 < n; e0 += kWsumUnroll) {
             Raw<NV, T> raw[kWsumUnroll];
             float wc[kWsumUnroll];
 #pragma unroll
             for (int t = 0; t < kWsumUnroll; ++t) {
-                const int e = e0 + t;
-                wc[t] = (e < cnt) ? ws[e] : 0.f;
-                if constexpr (std::is_same<T, float>::value) {
-                    if (wc[t] != 0.f) load_raw<G, NV>(raw[t], Tab, ids[e], g);
-                    else zero_raw<NV>(raw[t]);
-                } else {
-                    load_raw<G, NV>(raw[t], Tab, ids[wc[t] != 0.f ? e : 0], g);
-                }
+                wc[t] = ws[e0 + t];
+                load_raw<G, NV>(raw[t], Tab, ids[e0 + t], g);
             }
 #pragma unroll
             for (int t = 0; t < kWsumUnroll; ++t) {

@@ -394,57 +394,101 @@ __device__ __forceinline__ int* slice_stage(char* smem_raw, int gid) {
     return reinterpret_cast<int*>(smem_raw) + gid * 2 * Stage<G>::tile;  // [ids | weights] per lane group
 }
 
-// One list (the negatives or the interactions of a user that fall into the slice): entries [beg, end) of `list`.
-//   GRADU = false: out[t] = <x, V[list[t]]>
-//   GRADU = true : acc += wts[t] V[list[t]] (rows with weight 0 are not loaded)
-template <int G, int NV, typename T, bool GRADU>
-__device__ __forceinline__ void slice_list(int* ids, float* dst, const int32_t* __restrict__ list, int beg, int end,
-                                           const T* __restrict__ V, const Frag<NV>& x, Frag<NV>& acc,
-                                           float* __restrict__ out, const float* __restrict__ wts, int g, int safe) {
+// Scores of one list (the negatives or the interactions of a user that fall into the slice): out[t] = <x, V[list[t]]> for the
+// entries [beg, end) of `list`.
+template <int G, int NV, typename T>
+__device__ __forceinline__ void slice_list(int* ids, const int32_t* __restrict__ list, int beg, int end, const T* __restrict__ V,
+                                           const Frag<NV>& x, float* __restrict__ out, int g, int safe) {
     constexpr int kStageTile = Stage<G>::tile;
+    static_assert(kUnrollW == 4, "vector LDS reads assume four entries per step");
     for (int t0 = beg; t0 < end; t0 += kStageTile) {
         const int cnt = (end - t0 < kStageTile) ? end - t0 : kStageTile;
-        for (int e = g; e < cnt; e += G) {
-            ids[e] = __builtin_nontemporal_load(list + t0 + e);
-            if (GRADU) dst[e] = __builtin_nontemporal_load(wts + t0 + e);
-        }
+        for (int e = g; e < cnt; e += G) ids[e] = __builtin_nontemporal_load(list + t0 + e);
         wave_lds_sync();
-        float keep = 0.f;  // scores: lane g keeps the score of entry (e & (G-1)) == g until G of them are complete
+        float keep = 0.f;  // lane g keeps the score of entry (e & (G-1)) == g until G of them are complete
         for (int e0 = 0; e0 < cnt; e0 += kUnrollW) {
             Raw<NV, T> raw[kUnrollW];
-            float d[kUnrollW];
-            // the four ids (and weights) of this step in ONE LDS read each (e0 % 4 == 0, 16-byte aligned tile buffers;
-            // slots past cnt hold stale values and are never used): one LDS round trip before the four row loads
-            static_assert(kUnrollW == 4, "vector LDS reads assume four entries per step");
+            // the four ids of this step in ONE LDS read (e0 % 4 == 0, 16-byte aligned tile buffers; slots past cnt hold stale
+            // values and are never used): one LDS round trip before the four row loads
             const int4 id4 = *reinterpret_cast<const int4*>(ids + e0);
-            const float4 w4 = GRADU ? *reinterpret_cast<const float4*>(dst + e0) : make_float4(0.f, 0.f, 0.f, 0.f);
             const int idv[4] = {id4.x, id4.y, id4.z, id4.w};
-            const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
 #pragma unroll
-            for (int t = 0; t < kUnrollW; ++t) {
-                const int e = e0 + t;
-                bool want = e < cnt;
-                d[t] = 0.f;
-                if (GRADU && want) { d[t] = wv[t]; want = d[t] != 0.f; }
-                load_raw<G, NV>(raw[t], V, want ? idv[t] : safe, g);  // `safe`: a row that is resident (first of the window)
-            }
+            for (int t = 0; t < kUnrollW; ++t)
+                load_raw<G, NV>(raw[t], V, e0 + t < cnt ? idv[t] : safe, g);  // `safe`: a row that is resident (first of the window)
 #pragma unroll
             for (int t = 0; t < kUnrollW; ++t) {
                 Frag<NV> y;
                 to_frag<NV>(y, raw[t]);
-                if (GRADU) {
-                    axpy<NV>(acc, d[t], y);
-                } else {
-                    const int e = e0 + t;
-                    const float pr = group_allsum<G>(dot_partial<NV>(x, y));
-                    if (g == (e & (G - 1))) keep = pr;
-                    // a full run of G scores (or the tail of the tile): one contiguous 4*G-byte store per group
-                    if (e < cnt && ((e & (G - 1)) == G - 1 || e == cnt - 1)) {
-                        if (g <= (e & (G - 1))) __builtin_nontemporal_store(keep, out + t0 + (e & ~(G - 1)) + g);
-                    }
+                const int e = e0 + t;
+                const float pr = group_allsum<G>(dot_partial<NV>(x, y));
+                if (g == (e & (G - 1))) keep = pr;
+                // a full run of G scores (or the tail of the tile): one contiguous 4*G-byte store per group
+                if (e < cnt && ((e & (G - 1)) == G - 1 || e == cnt - 1)) {
+                    if (g <= (e & (G - 1))) __builtin_nontemporal_store(keep, out + t0 + (e & ~(G - 1)) + g);
                 }
             }
         }
+    }
+}
+
+// Gradient role of a (user, slice) visit: acc += sum_t wts[t] V[list[t]] over the negatives (weights D) and then the interactions
+// (weights delta) of the user that fall into the slice.  Entries of weight 0 (an inactive hinge term, a positive without an
+// active sample; -0.f counts) are dropped while the lists are staged (stage_nonzero), and both lists of the visit go into ONE
+// compacted stream, so every row the gather loop loads is one the sum needs and only the visit's last step carries pads.  The
+// kept entries are added in list order to one running fp32 sum, as they were with the others between them, so for finite tables no
+// bit of the result changes: an accumulator starts at +0 and acc + (0 * row) = acc + (+-0) = acc.
+constexpr int kStageRounds = 4;   // rounds of G entries whose ids and weights are loaded together, before their ballots
+
+template <int G, int NV, typename T>
+__device__ __forceinline__ void gather_staged(const int* ids, const float* ws, int n, const T* __restrict__ V, Frag<NV>& acc, int g) {
+    static_assert(kUnrollW == 4, "vector LDS reads assume four entries per step");
+    wave_lds_sync();
+    for (int e0 = 0; e0 < n; e0 += kUnrollW) {
+        Raw<NV, T> raw[kUnrollW];
+        // the four ids and weights of this step in ONE LDS read each (e0 % 4 == 0, 16-byte aligned tile buffers): one LDS round
+        // trip before the four row loads
+        const int4 id4 = *reinterpret_cast<const int4*>(ids + e0);
+        const float4 w4 = *reinterpret_cast<const float4*>(ws + e0);
+        const int idv[4] = {id4.x, id4.y, id4.z, id4.w};
+        const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+        for (int t = 0; t < kUnrollW; ++t) load_raw<G, NV>(raw[t], V, idv[t], g);
+#pragma unroll
+        for (int t = 0; t < kUnrollW; ++t) {
+            Frag<NV> y;
+            to_frag<NV>(y, raw[t]);
+            axpy<NV>(acc, wv[t], y);
+        }
+    }
+}
+
+// Appends the entries [beg, end) of `list` whose weight is not 0 to the n staged ones; gathers what is staged (and starts over)
+// whenever the tile buffers may not hold another kStageRounds rounds.
+template <int G, int NV, typename T>
+__device__ __forceinline__ void slice_append(int* ids, float* ws, int& n, const int32_t* __restrict__ list,
+                                            const float* __restrict__ wts, int beg, int end, const T* __restrict__ V,
+                                            Frag<NV>& acc, int g) {
+    constexpr int kStageTile = Stage<G>::tile;
+    static_assert(kStageRounds * 2 <= 8, "a tile of 8 G entries holds two loads of rounds");
+    for (int e0 = beg; e0 < end; e0 += kStageRounds * G) {   // every lane of the group makes every round: the ballots are over the group
+        if (n > kStageTile - kStageRounds * G) {
+            gather_staged<G, NV, T>(ids, ws, staged_steps<kUnrollW>(n), V, acc, g);
+            n = 0;
+        }
+        int id[kStageRounds];
+        float w[kStageRounds];
+#pragma unroll
+        for (int k = 0; k < kStageRounds; ++k) {
+            const int e = e0 + k * G + g;
+            id[k] = 0;
+            w[k] = 0.f;
+            if (e < end) {
+                id[k] = __builtin_nontemporal_load(list + e);
+                w[k] = __builtin_nontemporal_load(wts + e);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kStageRounds; ++k) stage_nonzero<G, kUnrollW>(ids, ws, n, id[k], w[k], g);
     }
 }
 
@@ -539,7 +583,6 @@ __global__ __launch_bounds__(64 * WAVES) void k_wmrb_scores3(SliceLists a, const
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane & (G - 1), gid = wave * NG + lane / G;
     int* ids = slice_stage<G>(smem_raw, gid);
-    float* dst = reinterpret_cast<float*>(ids + Stage<G>::tile);
     int64_t sl, grp;
     if (!slice_of_block(a, blockIdx.x, sl, grp)) return;
     const int64_t ubeg = grp * a.upg;
@@ -573,12 +616,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_wmrb_scores3(SliceLists a, const
         const int64_t o = u * (a.n_slices + 1) + sl;
         const int nb = a.off[o], ne = a.off[o + 1], pb = a.poff[o], pe = a.poff[o + 1];
         if (nb == ne && pb == pe) continue;
-        Frag<NV> x, none;
+        Frag<NV> x;
         load_row_nt<G, NV>(x, U, u, g);   // read once per (user, slice) visit
-        slice_list<G, NV, T, false>(ids, dst, a.R + u * (int64_t)a.S, nb, ne, V, x, none, sp + u * (int64_t)a.S, nullptr, g,
-                                    a.item_base);
+        slice_list<G, NV, T>(ids, a.R + u * (int64_t)a.S, nb, ne, V, x, sp + u * (int64_t)a.S, g, a.item_base);
         const int64_t rb = a.rowptr[u];
-        slice_list<G, NV, T, false>(ids, dst, a.col + rb, pb, pe, V, x, none, p + rb, nullptr, g, a.item_base);
+        slice_list<G, NV, T>(ids, a.col + rb, pb, pe, V, x, p + rb, g, a.item_base);
     }
 }
 
@@ -615,11 +657,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_wmrb_gradu3(SliceLists a, const 
     for (int64_t u = ubeg + gid; u < uend; u += NGB) {
         const int64_t o = u * (a.n_slices + 1) + sl;
         const int nb = a.off[o], ne = a.off[o + 1], pb = a.poff[o], pe = a.poff[o + 1];
-        Frag<NV> acc, none;
+        Frag<NV> acc;
         zero<NV>(acc);
         const int64_t us = u * (int64_t)a.S, rb = a.rowptr[u];
-        slice_list<G, NV, T, true>(ids, dst, a.R + us, nb, ne, V, none, acc, nullptr, D + us, g, a.item_base);
-        slice_list<G, NV, T, true>(ids, dst, a.col + rb, pb, pe, V, none, acc, nullptr, delta + rb, g, a.item_base);
+        int n = 0;   // entries staged and not yet gathered
+        slice_append<G, NV, T>(ids, dst, n, a.R + us, D + us, nb, ne, V, acc, g);
+        slice_append<G, NV, T>(ids, dst, n, a.col + rb, delta + rb, pb, pe, V, acc, g);
+        gather_staged<G, NV, T>(ids, dst, staged_steps<kUnrollW>(n), V, acc, g);
         if (accumulate == 0) {
             store_row_f32<G, NV, T>(acc, part, sl * a.n_users + u, g);
         } else {  // one launch per slice: part is a single [users, ld] layer summed in slice order
