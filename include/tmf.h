@@ -364,6 +364,20 @@ int tmf_bias_adam_f32(const double* part, int64_t part_rows, float* b, float* g_
 int tmf_adam_bias_rows_f32(float* W, const float* G, const float* b_new, float* E, int64_t n_rows, int n_components,
                            tmf_adam adam, void* stream);
 
+/* LinearEmbedding over a SPARSE feature matrix F [rows, n_features] (embedding_graphs.py:30-38, features @ weights): the
+ * effective table is E = F W.  The passes read E and, under TMF_EPI_GRAD, write G = dL/dE [rows, ld]; dL/dW = F^T G, and W takes the
+ * fresh-Adam step (matrix_factorization.py:173-176).  Both products are one pass over a list view of F (tmf_segments over its
+ * CSR lists, id = feature of every entry, or over its CSC lists, id = row of every entry; val = the entry's value beside it):
+ *   g[i] = sum over the entries k of list row i of  val[k] * T[id[k]]   (no entry is skipped), then the epilogue:
+ *   TMF_EPI_GRAD: X_out[i] = g[i] (fp32; X_old unused, may be NULL)      - E = F W over the CSR lists
+ *   TMF_EPI_ADAM: X_out[i] = fresh_adam(X_old[i], g[i])                  - W step from G over the CSC lists
+ * Rows of several segments go to `slab` and are finished by tmf_combine_rows_f32 with the same epi.
+ * Tables are [rows, ld] fp32 with zero padding columns; an empty list row gives g = 0 (E row 0 / W row unchanged).
+ * No atomics and a fixed order of additions: results are bit-identical from call to call.  id, val and T are only read.
+ * Null tables or a bad epi: TMF_E_INVALID; nseg == 0: TMF_OK; nothing is launched in either case. */
+int tmf_feat_pass_f32(const tmf_segments* seg, const int32_t* id, const float* val, const float* T,
+                      const float* X_old, float* X_out, float* slab, int n_components, int epi, tmf_adam adam, void* stream);
+
 /* OPT-IN EXTENSION, not the reference's optimiser (which is rebuilt every epoch, matrix_factorization.py:176): Keras
  * Adam with persistent moments.  tmf_adam_step gives the scalars of iteration `step` (1-based; step 1 == tmf_adam_fresh),
  * tmf_adam_state_rows_f32 applies one step in place to a whole [n_rows, ld] table from its raw gradient G (the

@@ -701,7 +701,7 @@ class TrainState:
     (``share_scratch``) instead of once per state."""
 
     def __init__(self, U0, V0, plan, n_components, wplan=None, dtype=torch.float32, V_tables=None, scratch=None, kl=False,
-                 user_bias=None, item_bias=None):
+                 user_bias=None, item_bias=None, user_feat=None, item_feat=None):
         dev = plan.col_u.device
         if kl:   # epoch_kl: the per-segment fp64 moments of the user side and the six coefficients tmf_kl_coeffs derives from them
             self.kl_part = torch.zeros(max(plan.seg_u.nseg, 1), 6, dtype=torch.float64, device=dev)
@@ -712,22 +712,29 @@ class TrainState:
         self.dtype = dtype
         self.sfx = '_bf16' if dtype is torch.bfloat16 else '_f32'
         self.ld = _lib.padded_ld(self.r, dtype)
-        if (user_bias is not None or item_bias is not None) and (dtype is not torch.float32 or V_tables is not None):
-            raise ValueError('a biased side needs float32 factor tables of its own')
-        # a biased side (BiasSide): U / V is its effective table E = W + b, rebuilt in place every epoch - no second buffer
-        self.U = self._pad(U0, dev)
+        sided = [x for x in (user_bias, item_bias, user_feat, item_feat) if x is not None]
+        if sided and (dtype is not torch.float32 or V_tables is not None):
+            raise ValueError('a biased side or a side over sparse features needs float32 factor tables of its own')
+        if (user_bias is not None and user_feat is not None) or (item_bias is not None and item_feat is not None):
+            raise ValueError('a side over sparse features has no bias form')
+        # a biased side (BiasSide): U / V is its effective table E = W + b, rebuilt in place every epoch - no second buffer.
+        # A side over sparse features (FeatureSide): U0 / V0 are its weights [n_features, r] and U / V is E = F W, likewise
+        self.feat_u = None if user_feat is None else FeatureSide(user_feat, self._pad(U0, dev), self.r, plan.n_users)
+        self.U = self._pad(U0, dev) if user_feat is None else torch.zeros(plan.n_users, self.ld, dtype=torch.float32, device=dev)
         self.bias_u = None if user_bias is None else BiasSide(self.U, user_bias, self.r)
-        self.U_nxt = torch.empty_like(self.U) if user_bias is None else None
+        self.U_nxt = torch.empty_like(self.U) if user_bias is None and user_feat is None else None
+        self.feat_v = None if item_feat is None else FeatureSide(item_feat, self._pad(V0, dev), self.r, plan.n_items)
         if V_tables is None:
-            self.V = self._pad(V0, dev)
-            self.V_nxt = torch.empty_like(self.V) if item_bias is None else None
+            self.V = self._pad(V0, dev) if item_feat is None else torch.zeros(plan.n_items, self.ld, dtype=torch.float32, device=dev)
+            self.V_nxt = torch.empty_like(self.V) if item_bias is None and item_feat is None else None
         else:
             self.V, self.V_nxt = V_tables
         self.bias_v = None if item_bias is None else BiasSide(self.V, item_bias, self.r)
         self.plan, self.wplan = plan, wplan
         need = dict(slab=max(plan.seg_u.n_slab, plan.seg_i.n_slab if plan.seg_i else 0,
                              wplan.seg_e.n_slab if wplan is not None and wplan.seg_e is not None else 0,
-                             wplan.vrows.n_slab if wplan is not None and wplan.vrows is not None else 0, 1) * self.ld,
+                             wplan.vrows.n_slab if wplan is not None and wplan.vrows is not None else 0,
+                             *(f.n_slab for f in (self.feat_u, self.feat_v) if f is not None), 1) * self.ld,
                     loss_part=max(plan.seg_u.nseg, plan.n_users, 1))
         self.row_stationary = False
         if wplan is not None and wplan.sliced:
@@ -773,6 +780,9 @@ class TrainState:
                         else torch.empty(v, dtype=torch.float32, device=dev) for k, v in need.items()})
         else:
             scratch.setdefault('states', []).append(self)
+        for side, E in ((self.feat_u, self.U), (self.feat_v, self.V)):   # the initial E = F W0 (the slab is bound by now)
+            if side is not None:
+                feature_forward(side.plan, side.W, E, self.slab, self.r)
 
     def _bind(self, bufs):
         """Views of the (possibly shared, larger) flat fp32 scratch buffers in this state's shapes."""
@@ -792,9 +802,9 @@ class TrainState:
         return out
 
     def swap(self):
-        if self.bias_u is None:
+        if self.U_nxt is not None:
             self.U, self.U_nxt = self.U_nxt, self.U
-        if self.bias_v is None:
+        if self.V_nxt is not None:
             self.V, self.V_nxt = self.V_nxt, self.V
 
 
@@ -843,6 +853,72 @@ def epoch_biased(st, adam, loss_out, loss='mse', c=0.0, prof=None):
         bias_update(st.bias_u, st.U, adam, prof, 'user_')
     if st.bias_v is not None:
         bias_update(st.bias_v, st.V, adam, prof, 'item_')
+    st.swap()
+
+
+class FeatureSide:
+    """One LinearEmbedding side over sparse features F [rows, n_features] (embedding_graphs.py:30-38): the list views of F - an
+    InteractionPlan over its entries, CSR by row for E = F W and CSC by feature for dW = F^T G, heavy lists cut into segments -,
+    the weights W [n_features, ld] with their second buffer and the gradient table G [rows, ld] the passes fill under
+    TMF_EPI_GRAD.  The TrainState table of the side is the effective table E, rebuilt every epoch.
+    F: anything with .indices [nnz, 2] (row, feature), .values [nnz] and .shape (mf.sparse.SparseFeatures); W0: padded weights."""
+
+    def __init__(self, F, W0, r, n_rows, chunk=DEFAULT_CHUNK):
+        rows, n_features = (int(d) for d in F.shape)
+        if rows != n_rows or tuple(W0.shape[:1]) != (n_features,):
+            raise ValueError(f'features of shape {(rows, n_features)} for {n_rows} rows and weights of {W0.shape[0]} rows')
+        dev = W0.device
+        self.r = int(r)
+        self.plan = InteractionPlan(F.indices.to(dev), F.values.to(dev), rows, n_features, chunk=chunk, csc=True)
+        self.n_slab = max(self.plan.seg_u.n_slab, self.plan.seg_i.n_slab)
+        self.W, self.W_nxt = W0, torch.empty_like(W0)
+        self.G = torch.empty(rows, W0.shape[1], dtype=torch.float32, device=dev)
+
+
+def feature_forward(plan, W, E, slab, r):
+    """E = F W over the CSR lists of ``plan`` (every row of E is written; a row without entries becomes zeros)."""
+    lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
+    adam = lib.tmf_adam_fresh(0.0)   # unused by the GRAD epilogue
+    _lib.check(lib.tmf_feat_pass_f32(plan.seg_u.cstruct(), P(plan.col_u), P(plan.val_u), P(W), None, P(E), P(slab), r,
+                                     _lib.EPI_GRAD, adam, s), lib)
+    _row_pass_finish(lib, plan.seg_u, slab, None, E, r, _lib.EPI_GRAD, adam, s)
+
+
+def embed_features(F, W, r, chunk=DEFAULT_CHUNK):
+    """F W [rows, ld] for padded weights W [n_features, ld] on the GPU: the forward pass over a plan built for F alone."""
+    if F.nnz == 0:
+        return torch.zeros(int(F.shape[0]), W.shape[1], dtype=torch.float32, device=W.device)
+    plan = InteractionPlan(F.indices.to(W.device), F.values.to(W.device), int(F.shape[0]), int(F.shape[1]), chunk=chunk, csc=False)
+    E = torch.empty(plan.n_users, W.shape[1], dtype=torch.float32, device=W.device)
+    slab = torch.empty(max(plan.seg_u.n_slab, 1), W.shape[1], dtype=torch.float32, device=W.device)
+    feature_forward(plan, W, E, slab, r)
+    return E
+
+
+def feature_backward(side, slab, adam):
+    """W_nxt[f] = fresh_adam(W[f], sum_i x_if G[i]) over the CSC lists (a feature no row carries keeps its weights), then the swap."""
+    lib, s, P, p = _lib.get(), _lib.stream_ptr(), _lib.ptr, side.plan
+    _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(side.G), P(side.W), P(side.W_nxt), P(slab),
+                                     side.r, _lib.EPI_ADAM, adam, s), lib)
+    _row_pass_finish(lib, p.seg_i, slab, side.W, side.W_nxt, side.r, _lib.EPI_ADAM, adam, s)
+    side.W, side.W_nxt = side.W_nxt, side.W
+
+
+def epoch_featured(st, adam, loss_out, loss='mse', c=0.0, prof=None):
+    """One epoch of a state with at least one side over sparse features, after epoch_biased: the loss's own epoch on the effective
+    tables, a featured (or biased) side emitting its raw gradient (TMF_EPI_GRAD) where a plain one keeps the fused fresh-Adam
+    epilogue; then, for every featured side, the step of its weights from G and the rebuilt E = F W (both passes of the epoch
+    have read the pre-update tables by then), the updates of a biased side, and the swap of the plain ones.
+    Stream-ordered, nothing allocated, no host reads, no atomics: graph-capturable and bit-reproducible."""
+    sides = [(st.feat_u, st.bias_u, st.U, 'user_'), (st.feat_v, st.bias_v, st.V, 'item_')]
+    (ue, uo), (ie, io) = [(_lib.EPI_GRAD, (f or b).G) if (f or b) is not None else (_lib.EPI_ADAM, None) for f, b, _, _ in sides]
+    run_epoch(st, adam, loss_out, loss, c, ie, io, prof, ue, uo)
+    for feat, bias, E, tag in sides:
+        if feat is not None:
+            _timed(prof, tag + 'feat_backward', lambda: feature_backward(feat, st.slab, adam))
+            _timed(prof, tag + 'feat_forward', lambda: feature_forward(feat.plan, feat.W, E, st.slab, feat.r))
+        elif bias is not None:
+            bias_update(bias, E, adam, prof, tag)
     st.swap()
 
 

@@ -111,6 +111,7 @@ _BASE_SIGNATURES = {
     'tmf_bias_colsum_f32': (_I, [_P, _L, _I, _P, _L, _P, _P]),
     'tmf_bias_adam_f32': (_I, [_P, _L, _P, _P, _I, Adam, _P]),
     'tmf_adam_bias_rows_f32': (_I, [_P, _P, _P, _P, _L, _I, Adam, _P]),
+    'tmf_feat_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
     'tmf_adam_step': (Adam, [_F, _I]),
     'tmf_adam_state_rows_f32': (_I, [_P, _P, _P, _P, _L, _I, Adam, _P]),
     'tmf_mse_pass_bf16': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),

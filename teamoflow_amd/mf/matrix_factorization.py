@@ -3,12 +3,13 @@
 
 Dispatch (same isinstance test the reference uses at :115,:136-162): a model made of
 (``LinearEmbedding`` | ``BiasedLinearEmbedding``) x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss``)
+- or ``LinearEmbedding`` over ``SparseFeatures`` on either side -
 trains on the HIP engine (``_engine.py`` -> libtmf.so); for unbiased MSE / WMRB it needs a GPU - there is no CPU fallback for them.
 Any other combination of plug-ins (dense features, ReLU embeddings, user subclasses) trains
 through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins'
 own ``get_repr`` / ``get_loss`` - and so does KL without a GPU, with ``batch_users`` / ``shard_items`` /
 ``data_parallel`` set, or on a table with an empty class, and a biased side without a GPU, with those settings, with bf16 factor
-storage or with ``optimizer='adam'``.
+storage or with ``optimizer='adam'`` - the settings under which a side over ``SparseFeatures`` is handed over as a dense matrix too.
 """
 import os
 import timeit
@@ -21,7 +22,7 @@ from .. import _engine, _lib, _ops
 from .embedding_graphs import BiasedLinearEmbedding, Embeddings, LinearEmbedding, ReLUEmbedding
 from .initializer_graphs import NormalInitializer
 from .loss_graphs import KLDivergenceLoss, LossGraph, MSELoss, WMRBLoss
-from .sparse import IndicatorFeatures, SparseInteractions, default_device, is_indicator
+from .sparse import IndicatorFeatures, SparseFeatures, SparseInteractions, default_device, is_indicator
 from .utils import gather_matrix_indices, random_sampler, random_sampler_device
 
 PREDICT_CHUNK_BYTES = 2 << 30  # users are scored in blocks of at most this many bytes of scores
@@ -108,18 +109,24 @@ class MatrixFactorization:
     # training
     # ------------------------------------------------------------------------------------------
     def _on_fast_path(self, user_features, item_features):
-        kinds = (type(self.user_repr_graph), type(self.item_repr_graph))
-        if not (all(k in (LinearEmbedding, BiasedLinearEmbedding) for k in kinds)
-                and type(self.loss_graph) in (MSELoss, WMRBLoss, KLDivergenceLoss)
-                and is_indicator(user_features) and is_indicator(item_features)):
+        sides = ((type(self.user_repr_graph), user_features), (type(self.item_repr_graph), item_features))
+        featured = [isinstance(f, SparseFeatures) for _, f in sides]
+        # a side is an engine side as Linear / BiasedLinear over indicator features, or as Linear over SparseFeatures with entries
+        if not (type(self.loss_graph) in (MSELoss, WMRBLoss, KLDivergenceLoss)
+                and all((kind is LinearEmbedding and f.nnz > 0) if sparse else
+                        (kind in (LinearEmbedding, BiasedLinearEmbedding) and is_indicator(f))
+                        for (kind, f), sparse in zip(sides, featured))):
             return False
-        return BiasedLinearEmbedding not in kinds or self._biased_engine_allowed()
+        return not (any(featured) or BiasedLinearEmbedding in (k for k, _ in sides)) or self._sided_engine_allowed()
 
-    def _biased_engine_allowed(self):
-        """A BiasedLinearEmbedding side trains on the engine as float32 tables with the reference's fresh-Adam step, full-batch on
-        one GPU; anything else keeps the generic path, as before."""
+    def _sided_engine_allowed(self):
+        """A BiasedLinearEmbedding side, and a side over SparseFeatures, train on the engine as float32 tables with the reference's
+        fresh-Adam step, full-batch on one GPU; anything else keeps the generic path."""
         return (torch.cuda.is_available() and self.factor_dtype is torch.float32 and self.optimizer == 'fresh_adam'
                 and not getattr(self, 'batch_users', 0) and not getattr(self, 'shard_items', 0) and not self._data_parallel_active())
+
+    def _biased_engine_allowed(self):
+        return self._sided_engine_allowed()
 
     def _data_parallel_active(self):
         return bool(self.data_parallel and torch.distributed.is_available() and torch.distributed.is_initialized()
@@ -147,18 +154,25 @@ class MatrixFactorization:
             V = self.item_weight_graph.initialize_weights(self.item_aux_dim, self.n_components)
         interactions = _as_interactions(tf_interactions)
         kl = type(self.loss_graph) is KLDivergenceLoss
+        self._sparse_feature_sides = (isinstance(user_features, SparseFeatures), isinstance(item_features, SparseFeatures))
+        self._feature_weights = [None, None]   # padded engine weights of a side trained over SparseFeatures (embed_users / embed_items)
         if self._on_fast_path(user_features, item_features) and (not kl or self._kl_engine_allowed()):
-            if self._fit_sparse(epochs, n_users, n_items, interactions, lr, U, V):
+            feats = [f if sparse else None for f, sparse in zip((user_features, item_features), self._sparse_feature_sides)]
+            if self._fit_sparse(epochs, n_users, n_items, interactions, lr, U, V, *feats):
                 return
+        # the generic loop multiplies dense matrices: SparseFeatures works there as its dense form does
+        user_features, item_features = (f.to_dense(W.device) if isinstance(f, SparseFeatures) else f
+                                        for f, W in ((user_features, U), (item_features, V)))
         self._fit_generic(epochs, user_features, item_features, interactions, lr, U, V)
 
     def _report(self, epoch, loss, seconds):
         if self.verbose and (epoch + 1) % 25 == 0:
             print(f'Epoch {epoch + 1} Complete | Loss {loss} | Runtime {seconds:.5} s')
 
-    def _fit_sparse(self, epochs, n_users, n_items, interactions, lr, U0, V0):
+    def _fit_sparse(self, epochs, n_users, n_items, interactions, lr, U0, V0, user_feat=None, item_feat=None):
         """Trains on the HIP engine and returns True; False (nothing trained) for a KLDivergenceLoss table with an empty class,
-        which fit() hands to the generic path."""
+        which fit() hands to the generic path.  user_feat / item_feat: the SparseFeatures of a featured side (U0 / V0 are then its
+        [n_features, r] weights)."""
         _lib.get()  # fail loudly here when the HIP engine cannot run
         self._sharded_epoch = None
         dev = default_device()
@@ -181,7 +195,7 @@ class MatrixFactorization:
             else:
                 tdist.fit_data_parallel(self, epochs, n_users, n_items, interactions, lr, U0, V0)
             return True
-        st, c = self._sparse_state(loss, n_users, n_items, interactions, U0, V0, dev)
+        st, c = self._sparse_state(loss, n_users, n_items, interactions, U0, V0, dev, user_feat, item_feat)
         if st is None:
             return False   # an empty class: no moments to take (the reference's arithmetic gives NaN; the generic path keeps that)
         denom = st.plan.n_pos if loss == 'wmrb' else 1 if loss == 'kl' else st.plan.nnz   # KL: the loss is one scalar, its mean is itself
@@ -197,7 +211,7 @@ class MatrixFactorization:
         self._publish_sparse(st)
         return True
 
-    def _sparse_state(self, loss, n_users, n_items, interactions, U0, V0, dev):
+    def _sparse_state(self, loss, n_users, n_items, interactions, U0, V0, dev, user_feat=None, item_feat=None):
         """(TrainState, c) of a single-GPU full-batch fit: the interaction plan, for WMRB the checked negative table, its plan and
         c = n_items / n_samples, and the starting bias of a BiasedLinearEmbedding side.  (None, 0.0) for KL with an empty class."""
         wmrb, kl = loss == 'wmrb', loss == 'kl'
@@ -218,7 +232,8 @@ class MatrixFactorization:
         # a biased side starts from the bias an earlier fit left on the model, as in the reference (:139-146), else from zeros
         bias0 = [None if type(graph) is not BiasedLinearEmbedding else torch.zeros(r) if kept is None else kept
                  for graph, kept in ((self.user_repr_graph, self.user_linear_bias), (self.item_repr_graph, self.item_linear_bias))]
-        return _engine.TrainState(U0, V0, plan, r, wplan, dtype=self.factor_dtype, kl=kl, user_bias=bias0[0], item_bias=bias0[1]), c
+        return _engine.TrainState(U0, V0, plan, r, wplan, dtype=self.factor_dtype, kl=kl, user_bias=bias0[0], item_bias=bias0[1],
+                                  user_feat=user_feat, item_feat=item_feat), c
 
     def _sparse_step(self, st, loss, c, lr):
         """step(epoch, out): one epoch, its loss sum into ``out``, by the reference's fresh Adam or by optimizer='adam' (kept moments)."""
@@ -226,6 +241,8 @@ class MatrixFactorization:
         if self.optimizer not in ('fresh_adam', 'adam'):
             raise ValueError(f"optimizer={self.optimizer!r}: 'fresh_adam' (the reference's behaviour) or 'adam'")
         if self.optimizer == 'fresh_adam':
+            if st.feat_u is not None or st.feat_v is not None:
+                return lambda epoch, out: _engine.epoch_featured(st, adam, out, loss, c)
             if st.bias_u is not None or st.bias_v is not None:
                 return lambda epoch, out: _engine.epoch_biased(st, adam, out, loss, c)
 
@@ -299,6 +316,11 @@ class MatrixFactorization:
         if st.bias_v is not None:
             self.item_linear_bias = st.bias_v.b[:r].clone().view(1, r).requires_grad_(True)
             self.item_trainable = [st.bias_v.W[:, :r], self.item_linear_bias]
+        # a side over SparseFeatures: the embedding is E = F W, the variable its weights W [n_features, r]
+        if st.feat_u is not None:
+            self._feature_weights[0], self.user_trainable = st.feat_u.W, [st.feat_u.W[:, :r]]
+        if st.feat_v is not None:
+            self._feature_weights[1], self.item_trainable = st.feat_v.W, [st.feat_v.W[:, :r]]
 
     def _fit_generic(self, epochs, user_features, item_features, interactions, lr, U, V):
         """The reference's dense loop (:128-187) over arbitrary plug-ins, differentiated by autograd."""
@@ -361,6 +383,39 @@ class MatrixFactorization:
             _, self.item_linear_bias = self.item_trainable
         if isinstance(self.item_repr_graph, ReLUEmbedding):
             _, self.item_relu_weight, self.item_relu_bias = self.item_trainable
+
+    # ------------------------------------------------------------------------------------------
+    # cold start: embeddings of rows the fit has not seen, from their features
+    # ------------------------------------------------------------------------------------------
+    def _embed(self, side, features):
+        name = ('user', 'item')[side]
+        if not getattr(self, '_sparse_feature_sides', (False, False))[side]:
+            raise ValueError(f'embed_{name}s: the {name} side of the last fit was not trained over SparseFeatures (there are no feature '
+                             f'weights to multiply)')
+        if not isinstance(features, SparseFeatures):
+            raise TypeError(f'embed_{name}s takes SparseFeatures')
+        graph = (self.user_repr_graph, self.item_repr_graph)[side]
+        trainable = (self.user_trainable, self.item_trainable)[side]
+        W = trainable[0].detach()
+        if features.shape[1] != W.shape[0]:
+            raise ValueError(f'embed_{name}s: features of {features.shape[1]} columns for weights of {W.shape[0]} features')
+        padded = self._feature_weights[side]
+        if padded is not None:   # an engine fit: the forward kernel on the padded weights it left
+            return _engine.embed_features(features, padded, self.n_components)[:, :self.n_components]
+        aux = ((self.user_relu_weight, self.user_relu_bias, self.user_linear_bias),
+               (self.item_relu_weight, self.item_relu_bias, self.item_linear_bias))[side]
+        with torch.no_grad():   # a generic fit: the plug-in's own definition over the dense rows
+            return graph.get_repr(features=features.to_dense(W.device), weights=W, relu_weight=aux[0], relu_bias=aux[1],
+                                  linear_bias=aux[2])[0]
+
+    def embed_users(self, features):
+        """Extension: F_new W_u [rows, r] for the trained user weights - the embeddings of users the fit has not seen, from their
+        feature rows (SparseFeatures with the training matrix's columns).  Needs a user side trained over SparseFeatures."""
+        return self._embed(0, features)
+
+    def embed_items(self, features):
+        """Extension: F_new W_i [rows, r] for the trained item weights (embed_users for the item side)."""
+        return self._embed(1, features)
 
     # ------------------------------------------------------------------------------------------
     # prediction and ranking
