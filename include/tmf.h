@@ -154,6 +154,24 @@ int tmf_kl_pass_f32(const tmf_segments* seg, const int32_t* other, const float* 
                     const float* Y_old, float* X_out, float* slab, const double* coef, int n_components, int epi,
                     tmf_adam adam, void* stream);
 
+/* One side of a LogisticLoss epoch (mf/loss_graphs.py LogisticLoss: the pointwise logistic loss over signed feedback - an
+ * extension, the reference has no such loss) evaluated sparsely: the contract of tmf_mse_pass_* with another coefficient.
+ *   for every entry k of row i:  p = <X_old[i], Y_old[other[k]]>,  y = val[k] > 0 ? +1 : -1 (a stored 0 is a negative: the
+ *   class split of tmf_kl_*; a NaN value is a negative too),  w = weighted ? |val[k]| : 1,
+ *   loss += w log(1 + exp(-y p)),  g[i] += c Y_old[other[k]] with c = -y w sigma(-y p);  then the epilogue `epi` writes X_out[i].
+ * fp32 arithmetic, stable for every finite p: with x = -y p and t = exp(-|x|), sigma(x) = (x >= 0 ? 1 : t) / (1 + t) and
+ * softplus(x) = max(x, 0) + log1p(t) - no overflow and no NaN beyond |p| = 88.7, and c = -+w / 2 exactly at p = 0.
+ * Call once with (X = U, Y = V, CSR by user) and once with (X = V, Y = U, CSC by item); both read the PRE-update tables.
+ * loss_part (optional, [nseg]) receives the per-segment sum of w softplus(-y p); with loss_part == NULL no logarithm is
+ * computed.  Rows of several segments go to `slab` and are finished by tmf_combine_rows_* with the same epi.  `weighted`
+ * (0 | non-zero) stands before the stream; the other arguments are tmf_mse_pass_*'s.
+ * No atomics and a fixed order of additions: results are bit-identical from call to call.
+ * Null tables or lists, a bad `epi`, n_components outside [1, 1024]: TMF_E_INVALID; nseg == 0: TMF_OK; nothing is launched in
+ * either case. */
+int tmf_logistic_pass_f32(const tmf_segments* seg, const int32_t* other, const float* val, const float* X_old,
+                          const float* Y_old, float* X_out, float* slab, float* loss_part, int n_components, int epi,
+                          tmf_adam adam, int weighted, void* stream);
+
 /* Weighted row-gather-sum pass (item side of WMRB, matrix_factorization.py:170-171 through
  * loss_graphs.py:80-88):  g[i] = sum over entries e of row i of  wbuf[ent_w[e]] * T[ent_row[e]]
  * (entries with weight exactly 0 are skipped), then the epilogue writes X_out[i]. */
@@ -424,6 +442,9 @@ int tmf_kl_moments_bf16(const tmf_segments* seg, const int32_t* other, const flo
 int tmf_kl_pass_bf16(const tmf_segments* seg, const int32_t* other, const float* val, const void* X_old,
                      const void* Y_old, void* X_out, float* slab, const double* coef, int n_components, int epi,
                      tmf_adam adam, void* stream);
+int tmf_logistic_pass_bf16(const tmf_segments* seg, const int32_t* other, const float* val, const void* X_old,
+                           const void* Y_old, void* X_out, float* slab, float* loss_part, int n_components, int epi,
+                           tmf_adam adam, int weighted, void* stream);
 int tmf_wsum_pass_bf16(const tmf_segments* seg, const int32_t* ent_row, const int32_t* ent_w,
                        const float* wbuf, const void* T, const void* X_old, void* X_out,
                        float* slab, int n_components, int epi, tmf_adam adam, void* stream);

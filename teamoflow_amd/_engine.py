@@ -6,6 +6,7 @@ What replaces what (reference paths under /root/reference/src/teamoflow/mf/):
   epoch_mse   <- matrix_factorization.py:130-176 with MSELoss  (loss_graphs.py:47-52)
   epoch_wmrb  <- matrix_factorization.py:130-176 with WMRBLoss (loss_graphs.py:74-88, utils.py:94-105)
   epoch_kl    <- matrix_factorization.py:130-176 with KLDivergenceLoss (loss_graphs.py:91-122)
+  epoch_logistic: LogisticLoss (mf/loss_graphs.py; an extension - the reference has no such loss)
 """
 import ctypes
 import os
@@ -969,16 +970,37 @@ def _timed(prof, name, call):
         prof.stop(name)
 
 
+LOGISTIC_LOSSES = ('logistic', 'logistic_w')   # LogisticLoss(weighted=False) / LogisticLoss(weighted=True)
+
+
+def loss_name(loss_graph):
+    """The name run_epoch knows the loss of a fit by: 'mse', 'wmrb', 'kl', 'logistic' or 'logistic_w' for exactly the four built-in
+    loss classes (not their subclasses: what a subclass computes is its own business, and the generic path's).  Anything else
+    raises - no loss trains as another one because a chain of isinstance tests fell through."""
+    from .mf import loss_graphs as L
+    kind = type(loss_graph)
+    if kind is L.LogisticLoss:
+        return 'logistic_w' if loss_graph.weighted else 'logistic'
+    names = {L.MSELoss: 'mse', L.WMRBLoss: 'wmrb', L.KLDivergenceLoss: 'kl'}
+    if kind not in names:
+        raise TypeError(f'{kind.__name__} is not a loss the HIP engine trains (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss)')
+    return names[kind]
+
+
 def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM,
               user_out=None):
-    """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'kl' or 'mse' - on the state's tables: the ONE place that maps a
-    loss to its epoch.  The other arguments as in epoch_mse."""
+    """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'kl', 'logistic', 'logistic_w' or 'mse' - on the state's tables:
+    the ONE place that maps a loss to its epoch.  The other arguments as in epoch_mse."""
     if loss == 'wmrb':
         epoch_wmrb(st, adam, c, loss_out, item_epi, item_out, prof, user_epi, user_out)
     elif loss == 'kl':
         epoch_kl(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
-    else:
+    elif loss in LOGISTIC_LOSSES:
+        epoch_logistic(st, adam, loss_out, loss == 'logistic_w', item_epi, item_out, prof, user_epi, user_out)
+    elif loss == 'mse':
         epoch_mse(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
+    else:
+        raise ValueError(f'run_epoch: unknown loss {loss!r}')
 
 
 def _row_pass_finish(lib, seg, slab, X_old, X_out, r, epi, adam, stream, sfx='_f32'):
@@ -1003,6 +1025,27 @@ def epoch_mse(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=No
     V_out = st.V_nxt if item_out is None else item_out
     _timed(prof, 'mse_item_pass', lambda: mse_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(st.V), _lib.ptr(st.U),
                                                    _lib.ptr(V_out), _lib.ptr(st.slab), None, r, item_epi, adam, s))
+    _row_pass_finish(lib, p.seg_i, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
+
+
+def epoch_logistic(st, adam, loss_out, weighted=False, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM,
+                   user_out=None):
+    """One LogisticLoss epoch: epoch_mse with tmf_logistic_pass in place of tmf_mse_pass - user pass (+loss), item pass (no
+    loss, no logarithm); both read the pre-update tables.  loss_out receives sum_k w_k log(1 + exp(-y_k p_k)), y_k = +1 where the
+    stored value is > 0, else -1, w_k = |value| if ``weighted`` else 1.  item_epi / user_epi as in epoch_mse."""
+    lib, p, r = _lib.get(), st.plan, st.r
+    s, wt = _lib.stream_ptr(), int(bool(weighted))
+    U_out = st.U_nxt if user_out is None else user_out
+    lg_pass = getattr(lib, 'tmf_logistic_pass' + st.sfx)
+    _timed(prof, 'logistic_user_pass', lambda: lg_pass(p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U),
+                                                       _lib.ptr(st.V), _lib.ptr(U_out), _lib.ptr(st.slab), _lib.ptr(st.loss_part), r,
+                                                       user_epi, adam, wt, s))
+    _row_pass_finish(lib, p.seg_u, st.slab, st.U, U_out, r, user_epi, adam, s, st.sfx)
+    _lib.check(lib.tmf_sum_f32(_lib.ptr(st.loss_part), p.seg_u.nseg, _lib.ptr(loss_out), s), lib)
+    V_out = st.V_nxt if item_out is None else item_out
+    _timed(prof, 'logistic_item_pass', lambda: lg_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(st.V),
+                                                       _lib.ptr(st.U), _lib.ptr(V_out), _lib.ptr(st.slab), None, r, item_epi, adam,
+                                                       wt, s))
     _row_pass_finish(lib, p.seg_i, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
 
 

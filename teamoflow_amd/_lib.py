@@ -82,6 +82,8 @@ _BASE_SIGNATURES = {
     'tmf_kl_coeffs': (_I, [_P, _L, _P, _P, _P]),
     'tmf_kl_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
     'tmf_kl_pass_bf16': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
+    'tmf_logistic_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _I, _P]),
+    'tmf_logistic_pass_bf16': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _I, _P]),
     'tmf_wsum_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
     'tmf_wsum_rows4_rows_per_group': (_I, [_I, _I]),
     'tmf_wsum_rows4_workspace_bytes': (_SZ, [_I32, _I32, _I32]),

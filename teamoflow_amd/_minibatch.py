@@ -3,9 +3,9 @@
 The reference is full-batch: one optimiser step per epoch on the gradient of the loss summed over ALL interactions
 (matrix_factorization.py:130-176).  With ``model.batch_users = B`` an epoch is instead a sweep over contiguous batches of B
 users, each one a complete step of the same kind on that batch's part of the loss: its users' rows of U and the whole item
-table V are updated by the reference's fresh Adam from the gradient of  sum over the batch's interactions  (MSE) /
+table V are updated by the reference's fresh Adam from the gradient of  sum over the batch's interactions  (MSE, LogisticLoss) /
 positives (WMRB; the loss of a positive only involves its own user's scores, so it is separable by user).  The next batch
-sees the updated V.  Every batch is the resident engine's epoch (``_engine.epoch_mse`` / ``epoch_wmrb``) on the batch's own
+sees the updated V.  Every batch is the resident engine's epoch (``_engine.run_epoch``) on the batch's own
 plans; the batches share the double-buffered item table and one set of per-step scratch buffers."""
 import timeit
 
@@ -16,9 +16,11 @@ from . import _engine, _lib
 
 
 def fit_minibatch(model, epochs, n_users, n_items, interactions, lr, U0, V0, batch_users):
-    from .mf.loss_graphs import WMRBLoss
     dev = interactions.device
-    wmrb = isinstance(model.loss_graph, WMRBLoss)
+    loss = _engine.loss_name(model.loss_graph)
+    if loss == 'kl':
+        raise ValueError('KLDivergenceLoss has no mini-batch form (its moments are global)')
+    wmrb = loss == 'wmrb'
     if getattr(model, 'optimizer', 'fresh_adam') != 'fresh_adam':
         raise ValueError("batch_users needs optimizer='fresh_adam' (every batch step is the reference's first Adam step)")
     B = int(batch_users)
@@ -64,7 +66,7 @@ def fit_minibatch(model, epochs, n_users, n_items, interactions, lr, U0, V0, bat
     for epoch in range(epochs):
         for i, st in enumerate(states):
             st.V, st.V_nxt = tables
-            _engine.run_epoch(st, adam, sums[epoch, i:i + 1], 'wmrb' if wmrb else 'mse', c)
+            _engine.run_epoch(st, adam, sums[epoch, i:i + 1], loss, c)
             st.U, st.U_nxt = st.U_nxt, st.U
             tables.reverse()                      # the item table this batch wrote is the one the next batch reads
         if model.verbose and (epoch + 1) % 25 == 0:

@@ -7,7 +7,7 @@ them.  Everything numeric is the same libtmf.so kernels as the resident path, la
     walked twice - scores of the window's negatives / interactions (tmf_wmrb_scores3 on the window's slices), the hinge step
     once all scores exist (tmf_wmrb_hinge2), then per window the user-gradient partial (tmf_wmrb_gradu3, one [users, ld]
     layer summed in window order) and the item gradient of the window's rows (tmf_wsum_pass over the window's entry lists).
-  MSE (loss_graphs.py:47-52): every interaction touches one item, so one walk - a sub-problem per window (its interactions,
+  MSE (loss_graphs.py:47-52) and LogisticLoss: every interaction touches one item, so one walk - a sub-problem per window (its interactions,
     item ids relative to the window): user-gradient partials summed in window order, item gradient of the window's rows.
 
 U is updated by the reference's fresh Adam when the last window is done; the item gradient of every window is handed
@@ -135,17 +135,26 @@ class WindowedHipBackend:
             _engine._row_pass_finish(lib, seg, self.slab, None, out, r, _lib.EPI_GRAD, self.adam, s, self.sfx)
             return
         p = self.sub[t]
-        mse_pass = getattr(lib, 'tmf_mse_pass' + self.sfx)
+        # the losses that are separable per interaction differ in the pass alone
+        if self.loss in _engine.LOGISTIC_LOSSES:
+            lg_pass, wt = getattr(lib, 'tmf_logistic_pass' + self.sfx), int(self.loss == 'logistic_w')
+
+            def row_pass(*args):   # tmf_mse_pass's arguments; `weighted` stands before the stream
+                return lg_pass(*args[:-1], wt, args[-1])
+        elif self.loss == 'mse':
+            row_pass = getattr(lib, 'tmf_mse_pass' + self.sfx)
+        else:
+            raise ValueError(f'WindowedHipBackend: unknown loss {self.loss!r}')
         layer = self.part[:self.m] if t == 0 else self.part[self.m:2 * self.m]
         if self.m:
-            _lib.check(mse_pass(p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(self.U), _lib.ptr(Vwin),
+            _lib.check(row_pass(p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(self.U), _lib.ptr(Vwin),
                                 _lib.ptr(layer), _lib.ptr(self.slab), _lib.ptr(self.loss_part), r, _lib.EPI_GRAD, self.adam, s), lib)
             _engine._row_pass_finish(lib, p.seg_u, self.slab, self.U, layer, r, _lib.EPI_GRAD, self.adam, s, self.sfx)
             if t:   # layer 0 += layer 1 (the finish kernel sums layers row by row; reading and writing row u in one thread)
                 _lib.check(getattr(lib, 'tmf_wmrb_finish' + self.sfx)(_lib.ptr(self.part), i32(2), i32(self.m), None,
                                                                       _lib.ptr(self.part), r, _lib.EPI_GRAD, self.adam, s), lib)
         _lib.check(lib.tmf_sum_f32(_lib.ptr(self.loss_part), p.seg_u.nseg, _lib.ptr(self.loss_w[t:t + 1]), s), lib)
-        _lib.check(mse_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(Vwin), _lib.ptr(self.U),
+        _lib.check(row_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(Vwin), _lib.ptr(self.U),
                             _lib.ptr(out), _lib.ptr(self.slab), None, r, _lib.EPI_GRAD, self.adam, s), lib)
         _engine._row_pass_finish(lib, p.seg_i, self.slab, Vwin, out, r, _lib.EPI_GRAD, self.adam, s, self.sfx)
 

@@ -344,13 +344,15 @@ def fit_item_sharded(model, epochs, n_users, n_items, interactions, lr, U0, V0, 
     global ids); ``gather_item_embedding`` assembles the catalog where it fits."""
     import timeit
     from ._windowed import WindowedHipBackend, window_geometry
-    from .mf.loss_graphs import WMRBLoss
     t_plan = timeit.default_timer()
     if getattr(model, 'optimizer', 'fresh_adam') != 'fresh_adam':
         raise ValueError("the multi-GPU fits implement the reference's optimiser only (optimizer='fresh_adam')")
     world, rank = _world(group)
     dev = interactions.device
-    wmrb = isinstance(model.loss_graph, WMRBLoss)
+    loss = _engine.loss_name(model.loss_graph)
+    if loss == 'kl':
+        raise ValueError('KLDivergenceLoss has no multi-GPU form (its moments are global)')
+    wmrb = loss == 'wmrb'
     T = world * max(1, int(windows_per_rank))
     r, dtype = model.n_components, model.factor_dtype
     ld = _lib.padded_ld(r, dtype)
@@ -394,7 +396,7 @@ def fit_item_sharded(model, epochs, n_users, n_items, interactions, lr, U0, V0, 
     if local is not None and U_blk.shape[0] != e - b:
         raise ValueError(f'local_users = {local}: the user initialiser must return the {e - b} rows of this block')
     U_blk = U_blk if local is not None else U_blk[b:e]
-    backend = WindowedHipBackend(U_blk, V_own, idx, val, R, e - b, n_items, T, r, 'wmrb' if wmrb else 'mse', c, lr, dtype=dtype,
+    backend = WindowedHipBackend(U_blk, V_own, idx, val, R, e - b, n_items, T, r, loss, c, lr, dtype=dtype,
                                  world=world)
     ep = ItemShardedEpoch(backend, backend.n_loss, T, group=group, always_collective=getattr(model, 'shard_always_collective', False))
     losses = torch.zeros(max(epochs, 1), dtype=torch.float64, device=dev)
@@ -476,12 +478,14 @@ def fit_data_parallel(model, epochs, n_users, n_items, interactions, lr, U0, V0,
     ``model.random_ind`` and the user initialiser's rows are then this block's and nothing global is touched.
     On return the model holds ``item_embedding`` (replicated), ``user_embedding`` = this rank's block,
     ``user_block`` = (begin, end); ``gather_user_embedding(model)`` assembles the full table."""
-    from .mf.loss_graphs import WMRBLoss
     if getattr(model, 'optimizer', 'fresh_adam') != 'fresh_adam':
         raise ValueError("the multi-GPU fits implement the reference's optimiser only (optimizer='fresh_adam')")
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     dev = interactions.device
-    wmrb = isinstance(model.loss_graph, WMRBLoss)
+    loss = _engine.loss_name(model.loss_graph)
+    if loss == 'kl':
+        raise ValueError('KLDivergenceLoss has no multi-GPU form (its moments are global)')
+    wmrb = loss == 'wmrb'
     local = getattr(model, 'local_users', None)
     if local is not None:
         b, e = int(local[0]), int(local[1])
@@ -515,7 +519,7 @@ def fit_data_parallel(model, epochs, n_users, n_items, interactions, lr, U0, V0,
     U_blk = torch.as_tensor(U0).detach() if local is not None else torch.as_tensor(U0).detach()[b:e]
     st = _engine.TrainState(U_blk, V0p, plan, model.n_components, wplan, dtype=model.factor_dtype)
     adam = _engine.adam_constants(lr)
-    backend = HipBackend(st, 'wmrb' if wmrb else 'mse', c, adam)
+    backend = HipBackend(st, loss, c, adam)
     dp = DataParallelEpoch(backend, plan.n_pos if wmrb else plan.nnz, group=group)
     losses = torch.zeros(max(epochs, 1), dtype=torch.float64, device=dev)
     for epoch in range(epochs):

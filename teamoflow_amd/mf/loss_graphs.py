@@ -1,6 +1,7 @@
 """Loss graphs (plug-in interface of /root/reference/src/teamoflow/mf/loss_graphs.py).
 
-``MSELoss``, ``WMRBLoss`` and ``KLDivergenceLoss`` with ``LinearEmbedding`` over indicator features are recognised by
+``MSELoss``, ``WMRBLoss``, ``KLDivergenceLoss`` and ``LogisticLoss`` (an extension: the reference has no pointwise logistic loss)
+with ``LinearEmbedding`` over indicator features are recognised by
 ``MatrixFactorization.fit`` (same isinstance dispatch as matrix_factorization.py:152-162) and run as
 fused HIP kernels; ``get_loss`` below is the generic differentiable definition used when the model is
 built from other plug-ins (dense features, custom embeddings), always called by keyword like
@@ -69,3 +70,20 @@ class KLDivergenceLoss(LossGraph):
         scale = torch.sqrt(pos.var(unbiased=False) + neg.var(unbiased=False))
         cdf0 = 0.5 * (1.0 + torch.erf((0.0 - loc) / (scale * 2.0 ** 0.5)))
         return 1.0 - cdf0
+
+
+class LogisticLoss(LossGraph):
+    """Extension (LightFM's default objective; not in the reference): the pointwise logistic loss over signed feedback.  For every
+    stored interaction with score p:  y = +1 where the value is > 0, else -1 (KLDivergenceLoss's class split: a stored 0 is a
+    negative),  w = |value| if ``weighted`` else 1,  loss = w log(1 + exp(-y p)),  d loss / d p = -y w sigmoid(-y p)."""
+
+    def __init__(self, weighted=False):
+        self.weighted = bool(weighted)
+
+    def get_loss(self, tf_interactions, predictions, tf_sample_predictions=None, tf_prediction_serial=None,
+                 n_items=None, n_samples=None):
+        idx, values = tf_interactions.indices, tf_interactions.values
+        p = predictions[idx[:, 0], idx[:, 1]]
+        y = torch.where(values > 0.0, torch.ones_like(p), -torch.ones_like(p))
+        w = values.abs().to(p.dtype) if self.weighted else torch.ones_like(p)
+        return -w * torch.nn.functional.logsigmoid(y * p)

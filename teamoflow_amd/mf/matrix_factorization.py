@@ -2,9 +2,11 @@
 /root/reference/src/teamoflow/mf/matrix_factorization.py:23-475, computed sparsely on MI355X.
 
 Dispatch (same isinstance test the reference uses at :115,:136-162): a model made of
-(``LinearEmbedding`` | ``BiasedLinearEmbedding``) x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss``)
+(``LinearEmbedding`` | ``BiasedLinearEmbedding``) x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss`` |
+``LogisticLoss``)
 - or ``LinearEmbedding`` over ``SparseFeatures`` on either side -
 trains on the HIP engine (``_engine.py`` -> libtmf.so); for unbiased MSE / WMRB it needs a GPU - there is no CPU fallback for them.
+``LogisticLoss`` (an extension) takes the engine whenever there is a GPU and the generic path without one.
 Any other combination of plug-ins (dense features, ReLU embeddings, user subclasses) trains
 through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins'
 own ``get_repr`` / ``get_loss`` - and so does KL without a GPU, with ``batch_users`` / ``shard_items`` /
@@ -21,7 +23,7 @@ import torch
 from .. import _engine, _lib, _ops
 from .embedding_graphs import BiasedLinearEmbedding, Embeddings, LinearEmbedding, ReLUEmbedding
 from .initializer_graphs import NormalInitializer
-from .loss_graphs import KLDivergenceLoss, LossGraph, MSELoss, WMRBLoss
+from .loss_graphs import KLDivergenceLoss, LogisticLoss, LossGraph, MSELoss, WMRBLoss
 from .sparse import IndicatorFeatures, SparseFeatures, SparseInteractions, default_device, is_indicator
 from .utils import gather_matrix_indices, random_sampler, random_sampler_device
 
@@ -112,7 +114,7 @@ class MatrixFactorization:
         sides = ((type(self.user_repr_graph), user_features), (type(self.item_repr_graph), item_features))
         featured = [isinstance(f, SparseFeatures) for _, f in sides]
         # a side is an engine side as Linear / BiasedLinear over indicator features, or as Linear over SparseFeatures with entries
-        if not (type(self.loss_graph) in (MSELoss, WMRBLoss, KLDivergenceLoss)
+        if not (type(self.loss_graph) in (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss)
                 and all((kind is LinearEmbedding and f.nnz > 0) if sparse else
                         (kind in (LinearEmbedding, BiasedLinearEmbedding) and is_indicator(f))
                         for (kind, f), sparse in zip(sides, featured))):
@@ -138,6 +140,11 @@ class MatrixFactorization:
         return (torch.cuda.is_available() and not getattr(self, 'batch_users', 0) and not getattr(self, 'shard_items', 0)
                 and not self._data_parallel_active())
 
+    def _logistic_engine_allowed(self):
+        """LogisticLoss (an extension, with a generic form) takes the engine whenever there is a GPU, in every training form MSE
+        has, and the generic path without one - MSE and WMRB have no CPU form and fail there."""
+        return type(self.loss_graph) is not LogisticLoss or torch.cuda.is_available()
+
     def fit(self, epochs, user_features, item_features, tf_interactions, lr=1e-2):
         """matrix_factorization.py:96-187.  Re-initialises the weights on every call, runs ``epochs``
         full-batch steps (loss -> gradient of the SUM of the per-interaction losses -> a fresh Adam
@@ -156,7 +163,8 @@ class MatrixFactorization:
         kl = type(self.loss_graph) is KLDivergenceLoss
         self._sparse_feature_sides = (isinstance(user_features, SparseFeatures), isinstance(item_features, SparseFeatures))
         self._feature_weights = [None, None]   # padded engine weights of a side trained over SparseFeatures (embed_users / embed_items)
-        if self._on_fast_path(user_features, item_features) and (not kl or self._kl_engine_allowed()):
+        if (self._on_fast_path(user_features, item_features) and (not kl or self._kl_engine_allowed())
+                and self._logistic_engine_allowed()):
             feats = [f if sparse else None for f, sparse in zip((user_features, item_features), self._sparse_feature_sides)]
             if self._fit_sparse(epochs, n_users, n_items, interactions, lr, U, V, *feats):
                 return
@@ -179,7 +187,7 @@ class MatrixFactorization:
         t_plan = timeit.default_timer()
         if interactions.device != dev:
             interactions = interactions.to(dev)
-        loss = 'wmrb' if isinstance(self.loss_graph, WMRBLoss) else 'kl' if type(self.loss_graph) is KLDivergenceLoss else 'mse'
+        loss = _engine.loss_name(self.loss_graph)
         if loss == 'wmrb' and self.random_ind is None:
             raise SampleTableMissing('WMRBLoss needs generate_sample=True (random_ind is None)')
         if getattr(self, 'batch_users', 0):

@@ -7,7 +7,8 @@ With a third argument q >= 1 the ranks run the item-row-sharded fit instead (mod
 dist.ItemShardedEpoch - window broadcasts, per-window reduce into the owner), compared with the same single-process fit.
 
 env: RANK, WORLD_SIZE, MASTER_ADDR, MASTER_PORT; TMF_REHEARSE_NCCL=1: one GPU per rank and an nccl (RCCL) group instead - no longer
-a rehearsal.  usage: python tools/dp_rehearsal.py OUT.json [loss] [q]"""
+a rehearsal.  usage: python tools/dp_rehearsal.py OUT.json [loss] [q]   (loss: wmrb | mse | logistic - the latter on the same
+interactions with a random sign on every value)"""
 import json
 import os
 import sys
@@ -18,7 +19,7 @@ import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from teamoflow.mf.initializer_graphs import FixedInitializer  # noqa: E402
-from teamoflow.mf.loss_graphs import MSELoss, WMRBLoss  # noqa: E402
+from teamoflow.mf.loss_graphs import LogisticLoss, MSELoss, WMRBLoss  # noqa: E402
 from teamoflow.mf.matrix_factorization import MatrixFactorization  # noqa: E402
 from teamoflow.mf.sparse import SparseInteractions, eye  # noqa: E402
 from teamoflow_amd import dist as tdist  # noqa: E402
@@ -26,6 +27,8 @@ from teamoflow_amd import dist as tdist  # noqa: E402
 
 def main():
     out, loss = sys.argv[1], (sys.argv[2] if len(sys.argv) > 2 else 'wmrb')
+    if loss not in ('wmrb', 'mse', 'logistic'):
+        sys.exit(f'loss {loss!r}: wmrb, mse or logistic')
     shard = int(sys.argv[3]) if len(sys.argv) > 3 else 0
     rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
     if os.environ.get('TMF_REHEARSE_NCCL') == '1':
@@ -46,13 +49,15 @@ def main():
     U0 = (rng.standard_normal((m, r)) * 0.3).astype(np.float32)
     V0 = (rng.standard_normal((n, r)) * 0.3).astype(np.float32)
     R = np.stack([rng.choice(n, S, replace=False) for _ in range(m)])
+    if loss == 'logistic':   # signed feedback; drawn last, so the other losses' problem is the one it always was
+        val = val * rng.choice(np.array([-1.0, 1.0], np.float32), len(idx))
 
     def run(parallel, epochs=epochs):
         kw = dict(user_weight_graph=FixedInitializer(U0), item_weight_graph=FixedInitializer(V0))
         if loss == 'wmrb':
             kw.update(loss_graph=WMRBLoss(), n_users=m, n_items=n, n_samples=S)
         else:
-            kw.update(loss_graph=MSELoss())
+            kw.update(loss_graph=LogisticLoss() if loss == 'logistic' else MSELoss())
         model = MatrixFactorization(r, **kw)
         model.verbose, model.data_parallel = False, parallel and not shard
         if os.environ.get('TMF_REHEARSE_DTYPE') == 'bf16':     # config 5's storage: bf16 rows cross the wire, fp32 gradients
@@ -117,6 +122,8 @@ def main():
                'V_frac_equal': float((dp.item_embedding == one.item_embedding).float().mean()),
                'recall_dp_local': float(dp.recall_at_k(SparseInteractions(idx, val, (m, n))).mean())
                if world == 1 else None}
+        if loss == 'logistic':
+            res['signed_values'] = bool((val < 0).any() and (val > 0).any())
         with open(out, 'w') as f:
             json.dump(res, f)
     dist.barrier()
