@@ -396,6 +396,34 @@ int tmf_adam_bias_rows_f32(float* W, const float* G, const float* b_new, float* 
 int tmf_feat_pass_f32(const tmf_segments* seg, const int32_t* id, const float* val, const float* T,
                       const float* X_old, float* X_out, float* slab, int n_components, int epi, tmf_adam adam, void* stream);
 
+/* ReLUEmbedding (embedding_graphs.py:61-87): E = relu(F Wr + b) W with the hidden width aux (5 r in the reference).  The sparse
+ * products Z = F Wr and dWr = F^T dZ are tmf_feat_pass_f32 at width aux, the bias step is tmf_bias_colsum_f32 / tmf_bias_adam_f32
+ * at width aux; these are the dense products in between, on the exact-fp32 MFMA.  Tables are fp32, 16-byte aligned:
+ * Z, dZ [n_rows, ld(aux)], b [ld(aux)], W [aux, ld(r)], G, E [n_rows, ld(r)], ld = tmf_padded_ld.  The hidden value is
+ * h = max(fl(z + b), 0) (one fp32 add) and a unit is on where fl(z + b) > 0, the same expression in every call; H is never
+ * stored.  The padding columns of the inputs may hold anything; those of the outputs are written as zeros.
+ *
+ *   tmf_relu_embed_f32         E[i, c] = sum_a h[i, a] W[a, c].
+ *   tmf_relu_dhidden_f32       dZ[i, a] = on(i, a) ? sum_c G[i, c] W[a, c] : 0 (exactly 0 where the unit is off).  dZ != Z.
+ *   tmf_relu_part_rows         P, the blocks the rows are cut into for the weight gradient: a function of n_rows alone
+ *                              (0 for n_rows <= 0, at most 256).
+ *   tmf_relu_dweights_f32      part[p][a, c] = sum over the rows i of block p of h[i, a] G[i, c]; part: [P, aux, ld(r)] fp32.
+ *   tmf_relu_adam_weights_f32  g = sum_p part[p] in the order p = 0, 1, .. (stored in g_out [aux, ld(r)] when it is not NULL), then
+ *                              W_out = fresh_adam(W_old, g) (the arithmetic of tmf_adam_fresh_rows_f32).  part_rows = 0 (no rows):
+ *                              g = 0 and W_out = W_old.
+ * No atomics and a fixed order of additions: results are bit-identical from call to call.  Nothing is allocated; every call is
+ * stream-ordered.  n_rows == 0: TMF_OK, nothing is launched.  A null table, aux or n_components outside [1, 1024], a table that
+ * is not 16-byte aligned, dZ == Z or a part_rows other than tmf_relu_part_rows(n_rows): TMF_E_INVALID before anything is launched. */
+int tmf_relu_embed_f32(const float* Z, const float* b, const float* W, float* E, int64_t n_rows, int aux, int n_components,
+                       void* stream);
+int tmf_relu_dhidden_f32(const float* G, const float* W, const float* Z, const float* b, float* dZ, int64_t n_rows, int aux,
+                         int n_components, void* stream);
+int64_t tmf_relu_part_rows(int64_t n_rows);
+int tmf_relu_dweights_f32(const float* Z, const float* b, const float* G, float* part, int64_t part_rows, int64_t n_rows, int aux,
+                          int n_components, void* stream);
+int tmf_relu_adam_weights_f32(const float* part, int64_t part_rows, const float* W_old, float* W_out, float* g_out, int aux,
+                              int n_components, tmf_adam adam, void* stream);
+
 /* OPT-IN EXTENSION, not the reference's optimiser (which is rebuilt every epoch, matrix_factorization.py:176): Keras
  * Adam with persistent moments.  tmf_adam_step gives the scalars of iteration `step` (1-based; step 1 == tmf_adam_fresh),
  * tmf_adam_state_rows_f32 applies one step in place to a whole [n_rows, ld] table from its raw gradient G (the

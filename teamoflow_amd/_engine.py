@@ -7,6 +7,7 @@ What replaces what (reference paths under /root/reference/src/teamoflow/mf/):
   epoch_wmrb  <- matrix_factorization.py:130-176 with WMRBLoss (loss_graphs.py:74-88, utils.py:94-105)
   epoch_kl    <- matrix_factorization.py:130-176 with KLDivergenceLoss (loss_graphs.py:91-122)
   epoch_logistic: LogisticLoss (mf/loss_graphs.py; an extension - the reference has no such loss)
+  epoch_relu  <- the same loop with a ReLUEmbedding side (embedding_graphs.py:61-87)
 """
 import ctypes
 import os
@@ -702,7 +703,7 @@ class TrainState:
     (``share_scratch``) instead of once per state."""
 
     def __init__(self, U0, V0, plan, n_components, wplan=None, dtype=torch.float32, V_tables=None, scratch=None, kl=False,
-                 user_bias=None, item_bias=None, user_feat=None, item_feat=None):
+                 user_bias=None, item_bias=None, user_feat=None, item_feat=None, user_relu=None, item_relu=None):
         dev = plan.col_u.device
         if kl:   # epoch_kl: the per-segment fp64 moments of the user side and the six coefficients tmf_kl_coeffs derives from them
             self.kl_part = torch.zeros(max(plan.seg_u.nseg, 1), 6, dtype=torch.float64, device=dev)
@@ -713,21 +714,29 @@ class TrainState:
         self.dtype = dtype
         self.sfx = '_bf16' if dtype is torch.bfloat16 else '_f32'
         self.ld = _lib.padded_ld(self.r, dtype)
-        sided = [x for x in (user_bias, item_bias, user_feat, item_feat) if x is not None]
+        sided = [x for x in (user_bias, item_bias, user_feat, item_feat, user_relu, item_relu) if x is not None]
         if sided and (dtype is not torch.float32 or V_tables is not None):
-            raise ValueError('a biased side or a side over sparse features needs float32 factor tables of its own')
+            raise ValueError('a biased side, a side over sparse features or a ReLU side needs float32 factor tables of its own')
         if (user_bias is not None and user_feat is not None) or (item_bias is not None and item_feat is not None):
             raise ValueError('a side over sparse features has no bias form')
+        if (user_relu is not None and (user_bias is not None or user_feat is not None)) or \
+                (item_relu is not None and (item_bias is not None or item_feat is not None)):
+            raise ValueError('a ReLU side carries its own features and bias (user_relu / item_relu: dict(F=, Wr0=, b0=))')
         # a biased side (BiasSide): U / V is its effective table E = W + b, rebuilt in place every epoch - no second buffer.
         # A side over sparse features (FeatureSide): U0 / V0 are its weights [n_features, r] and U / V is E = F W, likewise
+        # A ReLU side (ReLUSide): U0 / V0 are its output weights [aux, r] and U / V is E = relu(F Wr + b) W, likewise
         self.feat_u = None if user_feat is None else FeatureSide(user_feat, self._pad(U0, dev), self.r, plan.n_users)
-        self.U = self._pad(U0, dev) if user_feat is None else torch.zeros(plan.n_users, self.ld, dtype=torch.float32, device=dev)
+        self.relu_u = None if user_relu is None else ReLUSide(self._pad(U0, dev), self.r, plan.n_users, **user_relu)
+        own_u = user_feat is None and user_relu is None   # the table is the variable itself
+        self.U = self._pad(U0, dev) if own_u else torch.zeros(plan.n_users, self.ld, dtype=torch.float32, device=dev)
         self.bias_u = None if user_bias is None else BiasSide(self.U, user_bias, self.r)
-        self.U_nxt = torch.empty_like(self.U) if user_bias is None and user_feat is None else None
+        self.U_nxt = torch.empty_like(self.U) if user_bias is None and own_u else None
         self.feat_v = None if item_feat is None else FeatureSide(item_feat, self._pad(V0, dev), self.r, plan.n_items)
+        self.relu_v = None if item_relu is None else ReLUSide(self._pad(V0, dev), self.r, plan.n_items, **item_relu)
+        own_v = item_feat is None and item_relu is None
         if V_tables is None:
-            self.V = self._pad(V0, dev) if item_feat is None else torch.zeros(plan.n_items, self.ld, dtype=torch.float32, device=dev)
-            self.V_nxt = torch.empty_like(self.V) if item_bias is None and item_feat is None else None
+            self.V = self._pad(V0, dev) if own_v else torch.zeros(plan.n_items, self.ld, dtype=torch.float32, device=dev)
+            self.V_nxt = torch.empty_like(self.V) if item_bias is None and own_v else None
         else:
             self.V, self.V_nxt = V_tables
         self.bias_v = None if item_bias is None else BiasSide(self.V, item_bias, self.r)
@@ -737,6 +746,8 @@ class TrainState:
                              wplan.vrows.n_slab if wplan is not None and wplan.vrows is not None else 0,
                              *(f.n_slab for f in (self.feat_u, self.feat_v) if f is not None), 1) * self.ld,
                     loss_part=max(plan.seg_u.nseg, plan.n_users, 1))
+        # the list passes of a ReLU side run at width aux: the one slab holds rows of max(ld(r), ld(aux)) floats
+        need['slab'] = max([need['slab']] + [f.n_slab * f.ld_aux for f in (self.relu_u, self.relu_v) if f is not None])
         self.row_stationary = False
         if wplan is not None and wplan.sliced:
             m, S = wplan.R.shape
@@ -784,6 +795,9 @@ class TrainState:
         for side, E in ((self.feat_u, self.U), (self.feat_v, self.V)):   # the initial E = F W0 (the slab is bound by now)
             if side is not None:
                 feature_forward(side.plan, side.W, E, self.slab, self.r)
+        for side, E in ((self.relu_u, self.U), (self.relu_v, self.V)):   # likewise E = relu(F Wr0 + b0) W0
+            if side is not None:
+                relu_forward(side, E, self.slab)
 
     def _bind(self, bufs):
         """Views of the (possibly shared, larger) flat fp32 scratch buffers in this state's shapes."""
@@ -916,6 +930,119 @@ def epoch_featured(st, adam, loss_out, loss='mse', c=0.0, prof=None):
     run_epoch(st, adam, loss_out, loss, c, ie, io, prof, ue, uo)
     for feat, bias, E, tag in sides:
         if feat is not None:
+            _timed(prof, tag + 'feat_backward', lambda: feature_backward(feat, st.slab, adam))
+            _timed(prof, tag + 'feat_forward', lambda: feature_forward(feat.plan, feat.W, E, st.slab, feat.r))
+        elif bias is not None:
+            bias_update(bias, E, adam, prof, tag)
+    st.swap()
+
+
+class ReLUSide:
+    """One ReLUEmbedding side (embedding_graphs.py:61-87), E = relu(F Wr + b) W with the hidden width aux = 5 r: a FeatureSide-like
+    plan over the entries of F (CSR by row for Z = F Wr, CSC by feature for dWr = F^T dZ) - indicator features are the identity
+    lists, one entry per row, no dense matrix -, the hidden weights Wr [n_features, ld(aux)] and the output weights W [aux, ld(r)],
+    each with its second buffer, the hidden bias b [ld(aux)], the pre-activations Z and their gradient dZ [rows, ld(aux)], the
+    gradient table G [rows, ld(r)] the passes fill under TMF_EPI_GRAD, and the partial sums of the W and b steps.  The hidden
+    values are never stored.  The TrainState table of the side is the effective table E, rebuilt every epoch.
+    W0: padded output weights; F: None (indicator features) or anything FeatureSide takes; Wr0 [n_features, aux]; b0 [aux]."""
+
+    def __init__(self, W0, r, n_rows, F=None, Wr0=None, b0=None, chunk=DEFAULT_CHUNK):
+        lib, dev = _lib.load_library(), W0.device
+        self.r, self.aux, self.rows = int(r), int(W0.shape[0]), int(n_rows)
+        self.ld_aux = _lib.padded_ld(self.aux)
+        if F is None:
+            own = torch.arange(self.rows, dtype=torch.int64, device=dev)
+            indices, values, n_features = torch.stack([own, own], 1), torch.ones(self.rows, dtype=torch.float32, device=dev), self.rows
+        else:
+            rows, n_features = (int(d) for d in F.shape)
+            if rows != self.rows:
+                raise ValueError(f'features of shape {(rows, n_features)} for {n_rows} rows')
+            indices, values = F.indices.to(dev), F.values.to(dev)
+        self.n_features = n_features
+        Wr0 = torch.as_tensor(Wr0).detach().to(device=dev, dtype=torch.float32)
+        b0 = torch.as_tensor(b0).detach().to(device=dev, dtype=torch.float32).reshape(-1)
+        if tuple(Wr0.shape) != (n_features, self.aux) or b0.numel() != self.aux:
+            raise ValueError(f'relu_weight of shape {tuple(Wr0.shape)} and relu_bias of {b0.numel()} elements for {n_features} '
+                             f'features and aux width {self.aux}')
+        self.plan = InteractionPlan(indices, values, self.rows, n_features, chunk=chunk, csc=True)
+        self.n_slab = max(self.plan.seg_u.n_slab, self.plan.seg_i.n_slab)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.W, self.W_nxt = W0, torch.empty_like(W0)
+        self.Wr = torch.zeros(n_features, self.ld_aux, **f32)
+        self.Wr[:, :self.aux] = Wr0
+        self.Wr_nxt = torch.empty_like(self.Wr)
+        self.b = torch.zeros(self.ld_aux, **f32)
+        self.b[:self.aux] = b0
+        self.g_b = torch.zeros(self.ld_aux, **f32)
+        self.Z = torch.empty(self.rows, self.ld_aux, **f32)
+        self.dZ = torch.empty(self.rows, self.ld_aux, **f32)
+        self.G = torch.empty(self.rows, W0.shape[1], **f32)
+        self.part_rows = int(lib.tmf_relu_part_rows(self.rows))
+        self.part = torch.empty(max(self.part_rows, 1), self.aux, W0.shape[1], **f32)
+        self.bias_part_rows = int(lib.tmf_bias_colsum_part_rows(self.rows))
+        self.bias_part = torch.empty(self.bias_part_rows, self.ld_aux, dtype=torch.float64, device=dev)
+
+
+def relu_forward(side, E, slab, prof=None, tag=''):
+    """E = relu(F Wr + b) W from the side's current variables: the pre-activations over the CSR lists, then tmf_relu_embed_f32."""
+    lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
+    _timed(prof, tag + 'relu_feat_forward', lambda: feature_forward(side.plan, side.Wr, side.Z, slab, side.aux))
+    _timed(prof, tag + 'relu_embed', lambda: lib.tmf_relu_embed_f32(P(side.Z), P(side.b), P(side.W), P(E), side.rows, side.aux,
+                                                                    side.r, s))
+
+
+def embed_relu(F, side, chunk=DEFAULT_CHUNK):
+    """relu(F Wr + b) W [rows, ld] for the variables of a trained ReLUSide on the GPU: the two forward kernels over a plan built for
+    F alone - for the rows the fit saw, bit for bit the table it left."""
+    lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
+    rows, dev = int(F.shape[0]), side.W.device
+    Z = embed_features(F, side.Wr, side.aux, chunk)
+    E = torch.empty(rows, side.W.shape[1], dtype=torch.float32, device=dev)
+    _lib.check(lib.tmf_relu_embed_f32(P(Z), P(side.b), P(side.W), P(E), rows, side.aux, side.r, s), lib)
+    return E
+
+
+def relu_update(side, E, slab, adam, prof=None, tag=''):
+    """The step of one ReLU side from its gradient table side.G (filled by this epoch's pass).  Every read of the pre-update W and
+    b comes before their steps: the partials of dW = H^T G and dZ = (G W^T) . mask first, then W, then b from the column sums of
+    dZ, then Wr from F^T dZ over the CSC lists (a feature no row carries keeps its weights); last the rebuilt Z = F Wr and
+    E = relu(Z + b) W.  Stream-ordered, nothing allocated, no host scalars, no atomics: graph-capturable and bit-reproducible.
+    tag: prefix of the span names under ``prof`` (KernelTimer)."""
+    lib, s, P, p = _lib.get(), _lib.stream_ptr(), _lib.ptr, side.plan
+    rows, aux, r = side.rows, side.aux, side.r
+    _timed(prof, tag + 'relu_dweights', lambda: lib.tmf_relu_dweights_f32(P(side.Z), P(side.b), P(side.G), P(side.part),
+                                                                          side.part_rows, rows, aux, r, s))
+    _timed(prof, tag + 'relu_dhidden', lambda: lib.tmf_relu_dhidden_f32(P(side.G), P(side.W), P(side.Z), P(side.b), P(side.dZ), rows,
+                                                                        aux, r, s))
+    _timed(prof, tag + 'relu_adam_weights', lambda: lib.tmf_relu_adam_weights_f32(P(side.part), side.part_rows, P(side.W),
+                                                                                  P(side.W_nxt), None, aux, r, adam, s))
+    side.W, side.W_nxt = side.W_nxt, side.W
+    _timed(prof, tag + 'relu_bias_colsum', lambda: lib.tmf_bias_colsum_f32(P(side.dZ), rows, aux, P(side.bias_part),
+                                                                           side.bias_part_rows, None, s))
+    _timed(prof, tag + 'relu_bias_adam', lambda: lib.tmf_bias_adam_f32(P(side.bias_part), side.bias_part_rows, P(side.b), P(side.g_b),
+                                                                       aux, adam, s))
+
+    def hidden_backward():
+        _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(side.dZ), P(side.Wr), P(side.Wr_nxt), P(slab),
+                                         aux, _lib.EPI_ADAM, adam, s), lib)
+        _row_pass_finish(lib, p.seg_i, slab, side.Wr, side.Wr_nxt, aux, _lib.EPI_ADAM, adam, s)
+        side.Wr, side.Wr_nxt = side.Wr_nxt, side.Wr
+    _timed(prof, tag + 'relu_feat_backward', hidden_backward)
+    relu_forward(side, E, slab, prof, tag)
+
+
+def epoch_relu(st, adam, loss_out, loss='mse', c=0.0, prof=None):
+    """One epoch of a state with at least one ReLU side, after epoch_featured: the loss's own epoch on the effective tables, every
+    ReLU, featured or biased side emitting its raw gradient (TMF_EPI_GRAD) where a plain one keeps the fused fresh-Adam epilogue;
+    then, side by side, relu_update, the steps of a featured or biased side, and the swap of the plain ones."""
+    sides = [(st.relu_u, st.feat_u, st.bias_u, st.U, 'user_'), (st.relu_v, st.feat_v, st.bias_v, st.V, 'item_')]
+    (ue, uo), (ie, io) = [(_lib.EPI_GRAD, (x or f or b).G) if (x or f or b) is not None else (_lib.EPI_ADAM, None)
+                          for x, f, b, _, _ in sides]
+    run_epoch(st, adam, loss_out, loss, c, ie, io, prof, ue, uo)
+    for relu, feat, bias, E, tag in sides:
+        if relu is not None:
+            relu_update(relu, E, st.slab, adam, prof, tag)
+        elif feat is not None:
             _timed(prof, tag + 'feat_backward', lambda: feature_backward(feat, st.slab, adam))
             _timed(prof, tag + 'feat_forward', lambda: feature_forward(feat.plan, feat.W, E, st.slab, feat.r))
         elif bias is not None:

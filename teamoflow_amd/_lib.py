@@ -114,6 +114,11 @@ _BASE_SIGNATURES = {
     'tmf_bias_adam_f32': (_I, [_P, _L, _P, _P, _I, Adam, _P]),
     'tmf_adam_bias_rows_f32': (_I, [_P, _P, _P, _P, _L, _I, Adam, _P]),
     'tmf_feat_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
+    'tmf_relu_embed_f32': (_I, [_P, _P, _P, _P, _L, _I, _I, _P]),
+    'tmf_relu_dhidden_f32': (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _P]),
+    'tmf_relu_part_rows': (_L, [_L]),
+    'tmf_relu_dweights_f32': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _P]),
+    'tmf_relu_adam_weights_f32': (_I, [_P, _L, _P, _P, _P, _I, _I, Adam, _P]),
     'tmf_adam_step': (Adam, [_F, _I]),
     'tmf_adam_state_rows_f32': (_I, [_P, _P, _P, _P, _L, _I, Adam, _P]),
     'tmf_mse_pass_bf16': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),

@@ -7,6 +7,7 @@ Dispatch (same isinstance test the reference uses at :115,:136-162): a model mad
 - or ``LinearEmbedding`` over ``SparseFeatures`` on either side -
 trains on the HIP engine (``_engine.py`` -> libtmf.so); for unbiased MSE / WMRB it needs a GPU - there is no CPU fallback for them.
 ``LogisticLoss`` (an extension) takes the engine whenever there is a GPU and the generic path without one.
+With ``relu_engine = True`` (off by default) a ``ReLUEmbedding`` side over indicator features or ``SparseFeatures`` trains there too.
 Any other combination of plug-ins (dense features, ReLU embeddings, user subclasses) trains
 through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins'
 own ``get_repr`` / ``get_loss`` - and so does KL without a GPU, with ``batch_users`` / ``shard_items`` /
@@ -106,6 +107,9 @@ class MatrixFactorization:
         # extension, OFF by default: 'adam' keeps Adam's moments across epochs.  The reference (and the default here,
         # 'fresh_adam') builds a new optimizer every epoch (:176), i.e. every step is Adam's first step.
         self.optimizer = 'fresh_adam'
+        # extension, OFF by default: True = a ReLUEmbedding side over eye() or SparseFeatures trains on the HIP engine
+        # (_engine.ReLUSide / epoch_relu) where a biased side would; False = the generic path, as before
+        self.relu_engine = False
 
     # ------------------------------------------------------------------------------------------
     # training
@@ -113,13 +117,17 @@ class MatrixFactorization:
     def _on_fast_path(self, user_features, item_features):
         sides = ((type(self.user_repr_graph), user_features), (type(self.item_repr_graph), item_features))
         featured = [isinstance(f, SparseFeatures) for _, f in sides]
+        # with relu_engine also exactly ReLUEmbedding, over either kind of features, while its aux width 5 r fits a table row
+        relu = getattr(self, 'relu_engine', False) and 5 * self.n_components <= 1024
+        linear = (LinearEmbedding, ReLUEmbedding) if relu else (LinearEmbedding,)
         # a side is an engine side as Linear / BiasedLinear over indicator features, or as Linear over SparseFeatures with entries
         if not (type(self.loss_graph) in (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss)
-                and all((kind is LinearEmbedding and f.nnz > 0) if sparse else
-                        (kind in (LinearEmbedding, BiasedLinearEmbedding) and is_indicator(f))
+                and all((kind in linear and f.nnz > 0) if sparse else
+                        (kind in linear + (BiasedLinearEmbedding,) and is_indicator(f))
                         for (kind, f), sparse in zip(sides, featured))):
             return False
-        return not (any(featured) or BiasedLinearEmbedding in (k for k, _ in sides)) or self._sided_engine_allowed()
+        kinds = [k for k, _ in sides]
+        return not (any(featured) or BiasedLinearEmbedding in kinds or ReLUEmbedding in kinds) or self._sided_engine_allowed()
 
     def _sided_engine_allowed(self):
         """A BiasedLinearEmbedding side, and a side over SparseFeatures, train on the engine as float32 tables with the reference's
@@ -163,6 +171,7 @@ class MatrixFactorization:
         kl = type(self.loss_graph) is KLDivergenceLoss
         self._sparse_feature_sides = (isinstance(user_features, SparseFeatures), isinstance(item_features, SparseFeatures))
         self._feature_weights = [None, None]   # padded engine weights of a side trained over SparseFeatures (embed_users / embed_items)
+        self._relu_sides = [None, None]        # the _engine.ReLUSide of a ReLU side trained on the engine (embed_users / embed_items)
         if (self._on_fast_path(user_features, item_features) and (not kl or self._kl_engine_allowed())
                 and self._logistic_engine_allowed()):
             feats = [f if sparse else None for f, sparse in zip((user_features, item_features), self._sparse_feature_sides)]
@@ -240,8 +249,20 @@ class MatrixFactorization:
         # a biased side starts from the bias an earlier fit left on the model, as in the reference (:139-146), else from zeros
         bias0 = [None if type(graph) is not BiasedLinearEmbedding else torch.zeros(r) if kept is None else kept
                  for graph, kept in ((self.user_repr_graph, self.user_linear_bias), (self.item_repr_graph, self.item_linear_bias))]
+        # a ReLU side (only relu_engine lets one get here) carries its features itself; its hidden variables start from what an
+        # earlier fit left on the model, else as get_repr draws them (:80-83): relu_weight ~ N(0, 1), relu_bias zeros
+        relu0, feat = [None, None], [user_feat, item_feat]
+        for side, (graph, rows, kept_w, kept_b) in enumerate((
+                (self.user_repr_graph, n_users, self.user_relu_weight, self.user_relu_bias),
+                (self.item_repr_graph, n_items, self.item_relu_weight, self.item_relu_bias))):
+            if type(graph) is ReLUEmbedding:
+                aux, n_features = 5 * r, rows if feat[side] is None else int(feat[side].shape[1])
+                relu0[side] = dict(F=feat[side],
+                                   Wr0=torch.randn(n_features, aux, device=dev) if kept_w is None else kept_w,
+                                   b0=torch.zeros(aux, device=dev) if kept_b is None else kept_b)
+                feat[side] = None
         return _engine.TrainState(U0, V0, plan, r, wplan, dtype=self.factor_dtype, kl=kl, user_bias=bias0[0], item_bias=bias0[1],
-                                  user_feat=user_feat, item_feat=item_feat), c
+                                  user_feat=feat[0], item_feat=feat[1], user_relu=relu0[0], item_relu=relu0[1]), c
 
     def _sparse_step(self, st, loss, c, lr):
         """step(epoch, out): one epoch, its loss sum into ``out``, by the reference's fresh Adam or by optimizer='adam' (kept moments)."""
@@ -249,6 +270,8 @@ class MatrixFactorization:
         if self.optimizer not in ('fresh_adam', 'adam'):
             raise ValueError(f"optimizer={self.optimizer!r}: 'fresh_adam' (the reference's behaviour) or 'adam'")
         if self.optimizer == 'fresh_adam':
+            if st.relu_u is not None or st.relu_v is not None:
+                return lambda epoch, out: _engine.epoch_relu(st, adam, out, loss, c)
             if st.feat_u is not None or st.feat_v is not None:
                 return lambda epoch, out: _engine.epoch_featured(st, adam, out, loss, c)
             if st.bias_u is not None or st.bias_v is not None:
@@ -329,6 +352,18 @@ class MatrixFactorization:
             self._feature_weights[0], self.user_trainable = st.feat_u.W, [st.feat_u.W[:, :r]]
         if st.feat_v is not None:
             self._feature_weights[1], self.item_trainable = st.feat_v.W, [st.feat_v.W[:, :r]]
+        # a ReLU side: [weights [aux, r], relu_weight [n_features, aux], relu_bias [1, aux]], the two hidden variables kept on the
+        # model as leaves that require grad (relu_weight a view of the engine's padded table: it is as large as the features)
+        for side, relu in enumerate((st.relu_u, st.relu_v)):
+            if relu is not None:
+                self._relu_sides[side] = relu
+                kept_w = relu.Wr[:, :relu.aux].detach().requires_grad_(True)
+                kept_b = relu.b[:relu.aux].clone().view(1, relu.aux).requires_grad_(True)
+                trainable = [relu.W[:, :r], kept_w, kept_b]
+                if side == 0:
+                    self.user_relu_weight, self.user_relu_bias, self.user_trainable = kept_w, kept_b, trainable
+                else:
+                    self.item_relu_weight, self.item_relu_bias, self.item_trainable = kept_w, kept_b, trainable
 
     def _fit_generic(self, epochs, user_features, item_features, interactions, lr, U, V):
         """The reference's dense loop (:128-187) over arbitrary plug-ins, differentiated by autograd."""
@@ -404,9 +439,13 @@ class MatrixFactorization:
             raise TypeError(f'embed_{name}s takes SparseFeatures')
         graph = (self.user_repr_graph, self.item_repr_graph)[side]
         trainable = (self.user_trainable, self.item_trainable)[side]
+        relu = getattr(self, '_relu_sides', (None, None))[side]
         W = trainable[0].detach()
-        if features.shape[1] != W.shape[0]:
-            raise ValueError(f'embed_{name}s: features of {features.shape[1]} columns for weights of {W.shape[0]} features')
+        n_features = W.shape[0] if relu is None else relu.n_features
+        if features.shape[1] != n_features:
+            raise ValueError(f'embed_{name}s: features of {features.shape[1]} columns for weights of {n_features} features')
+        if relu is not None:     # an engine fit of a ReLU side: the two forward kernels on the variables it left
+            return _engine.embed_relu(features, relu)[:, :self.n_components]
         padded = self._feature_weights[side]
         if padded is not None:   # an engine fit: the forward kernel on the padded weights it left
             return _engine.embed_features(features, padded, self.n_components)[:, :self.n_components]
