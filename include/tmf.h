@@ -329,6 +329,16 @@ int tmf_wmrb_hinge2(const int64_t* rowptr, const float* val, const float* p, con
 int tmf_wmrb_hinge2_ordered(const int64_t* rowptr, const float* val, const float* p, const float* sp, int32_t n_users,
                             int32_t n_samples, float c, float* delta, float* D, float* loss_part, const int32_t* user_order,
                             void* stream);
+/* BPRLoss (an extension) in the place of tmf_wmrb_hinge2_ordered, same layout of every argument: for the stored values > 0 of user u,
+ * x_ks = sp[u, s] - p[k]:  delta[k] = -(1 / S) sum_s sigmoid(x_ks) (0 for a stored value <= 0),  D[u, s] = (1 / S) sum_k
+ * sigmoid(x_ks),  loss_part[u] = (1 / S) sum_k sum_s softplus(x_ks) - the pairwise logistic loss -log sigmoid(p[k] - sp[u, s]),
+ * averaged over the user's row of the negative table; the epoch's loss is the sum of loss_part over the number of positives.
+ * Every element of delta [nnz], D [n_users, n_samples] and loss_part [n_users] is overwritten, whatever the buffers held.  Reads no
+ * table; O(P_u S) exponentials per user.  n_users = 0 is legal, and so are NULL val / p / delta for a table without interactions.
+ * No atomics; the outputs are bit-identical from run to run and do not depend on user_order (speed only: heavy users first).
+ * Finite for every finite score; +inf in sp gives loss inf and sigmoid 1; a NaN stays inside its user. */
+int tmf_bpr_pairs(const int64_t* rowptr, const float* val, const float* p, const float* sp, int32_t n_users, int32_t n_samples,
+                  float* delta, float* D, float* loss_part, const int32_t* user_order, void* stream);
 int tmf_wmrb_gradu3_f32(const tmf_slice_lists* lists, const float* D, const float* delta, const void* V, float* part,
                         int per_slice_launches, int n_components, void* stream);
 int tmf_wmrb_gradu3_bf16(const tmf_slice_lists* lists, const float* D, const float* delta, const void* V, float* part,

@@ -7,6 +7,7 @@ What replaces what (reference paths under /root/reference/src/teamoflow/mf/):
   epoch_wmrb  <- matrix_factorization.py:130-176 with WMRBLoss (loss_graphs.py:74-88, utils.py:94-105)
   epoch_kl    <- matrix_factorization.py:130-176 with KLDivergenceLoss (loss_graphs.py:91-122)
   epoch_logistic: LogisticLoss (mf/loss_graphs.py; an extension - the reference has no such loss)
+  epoch_wmrb(pairs='bpr'): BPRLoss (mf/loss_graphs.py; an extension): the WMRB epoch with tmf_bpr_pairs in the hinge kernel's place
   epoch_relu  <- the same loop with a ReLUEmbedding side (embedding_graphs.py:61-87)
 """
 import ctypes
@@ -515,14 +516,17 @@ def row_stationary_wanted(n_users, n_items, n_samples, nnz, n_components, dtype=
     return env == '1' or short_visits(n_users, n_items, n_samples, nnz, n_components, dtype)
 
 
-def wmrb_plan_for(plan, R, n_components, dtype=torch.float32, n_items=None):
+def wmrb_plan_for(plan, R, n_components, dtype=torch.float32, n_items=None, force_sliced=False):
     """The WmrbPlan a fit builds for (plan, R): the user-pass form (choose_wmrb_user_pass), the item-pass form (rows4_wanted) and the
     user blocks that go with it - ONE place for MatrixFactorization._fit_sparse, dist.fit_data_parallel and bench.py.
-    n_items: the catalog size for the slice geometry when the plan's table is padded (multi-GPU: rows padded to the world size)."""
+    n_items: the catalog size for the slice geometry when the plan's table is padded (multi-GPU: rows padded to the world size).
+    force_sliced: the sliced user pass whatever the shape (BPRLoss: the one-kernel pass has the hinge built in); the slice count
+    stays the one the shape gets."""
     m = plan.n_users
     n = plan.n_items if n_items is None else n_items
     ns, sliced = choose_wmrb_user_pass(m, n, _lib.padded_ld(n_components, dtype), int(R.shape[1]), plan.n_pos, n_components,
                                        elem_size=2 if dtype is torch.bfloat16 else 4)
+    sliced = sliced or bool(force_sliced)
     # short visits (config-5 shard): the row-stationary gradU with its own slice size, unless the environment decides
     # (TMF_ROW_STATIONARY = 0 | 1, TMF_ITEM_SLICES)
     rs = row_stationary_wanted(m, n, int(R.shape[1]), plan.nnz, n_components, dtype, sliced)
@@ -1100,26 +1104,34 @@ def _timed(prof, name, call):
 LOGISTIC_LOSSES = ('logistic', 'logistic_w')   # LogisticLoss(weighted=False) / LogisticLoss(weighted=True)
 
 
+PAIR_LOSSES = ('wmrb', 'bpr')   # the losses over the static negative table: WmrbPlan, sp / p / delta / D, denominator n_pos
+
+
 def loss_name(loss_graph):
-    """The name run_epoch knows the loss of a fit by: 'mse', 'wmrb', 'kl', 'logistic' or 'logistic_w' for exactly the four built-in
-    loss classes (not their subclasses: what a subclass computes is its own business, and the generic path's).  Anything else
-    raises - no loss trains as another one because a chain of isinstance tests fell through."""
+    """The name run_epoch knows the loss of a fit by: 'mse', 'wmrb', 'kl', 'bpr', 'logistic' or 'logistic_w' for exactly the five
+    built-in loss classes (not their subclasses: what a subclass computes is its own business, and the generic path's).  Anything
+    else raises - no loss trains as another one because a chain of isinstance tests fell through."""
     from .mf import loss_graphs as L
     kind = type(loss_graph)
     if kind is L.LogisticLoss:
         return 'logistic_w' if loss_graph.weighted else 'logistic'
-    names = {L.MSELoss: 'mse', L.WMRBLoss: 'wmrb', L.KLDivergenceLoss: 'kl'}
+    names = {L.MSELoss: 'mse', L.WMRBLoss: 'wmrb', L.KLDivergenceLoss: 'kl', L.BPRLoss: 'bpr'}
     if kind not in names:
-        raise TypeError(f'{kind.__name__} is not a loss the HIP engine trains (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss)')
+        raise TypeError(f'{kind.__name__} is not a loss the HIP engine trains (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, '
+                        f'BPRLoss)')
     return names[kind]
 
 
 def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM,
               user_out=None):
-    """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'kl', 'logistic', 'logistic_w' or 'mse' - on the state's tables:
-    the ONE place that maps a loss to its epoch.  The other arguments as in epoch_mse."""
+    """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'bpr', 'kl', 'logistic', 'logistic_w' or 'mse' - on the state's
+    tables: the ONE place that maps a loss to its epoch.  The other arguments as in epoch_mse.
+    'bpr' is an epoch only of a state whose WmrbPlan is sliced (wmrb_plan_for(force_sliced=True)): the one-kernel user pass has the
+    hinge built in.  On any other state it is refused like a name nobody knows - never run as WMRB."""
     if loss == 'wmrb':
         epoch_wmrb(st, adam, c, loss_out, item_epi, item_out, prof, user_epi, user_out)
+    elif loss == 'bpr' and getattr(getattr(st, 'wplan', None), 'sliced', False):
+        epoch_wmrb(st, adam, 0.0, loss_out, item_epi, item_out, prof, user_epi, user_out, pairs='bpr')
     elif loss == 'kl':
         epoch_kl(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
     elif loss in LOGISTIC_LOSSES:
@@ -1127,7 +1139,7 @@ def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=
     elif loss == 'mse':
         epoch_mse(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
     else:
-        raise ValueError(f'run_epoch: unknown loss {loss!r}')
+        raise ValueError(f'run_epoch: unknown loss {loss!r}' + (' on a state without a sliced WmrbPlan' if loss == 'bpr' else ''))
 
 
 def _row_pass_finish(lib, seg, slab, X_old, X_out, r, epi, adam, stream, sfx='_f32'):
@@ -1196,8 +1208,9 @@ def epoch_kl(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=Non
     _row_pass_finish(lib, p.seg_i, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
 
 
-def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, U_out=None):
-    """Sliced user pass: scores -> hinge -> gradU (+ weights into entry order) -> finish (csrc/tmf_wmrb.hip, tmf_hinge.hip)."""
+def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, U_out=None, pairs='hinge'):
+    """Sliced user pass: scores -> hinge -> gradU (+ weights into entry order) -> finish (csrc/tmf_wmrb.hip, tmf_hinge.hip).
+    pairs='bpr': tmf_bpr_pairs (csrc/tmf_bpr.hip) in the hinge kernel's place - same arguments but c, same layout of delta and D."""
     p, w, r = st.plan, st.wplan, st.r
     i32 = ctypes.c_int32
     m, S, ns = p.n_users, w.S, w.n_slices
@@ -1218,9 +1231,14 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
     else:
         _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores3' + st.sfx)(lists, _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(st.sp),
                                                                                 _lib.ptr(st.pk), r, s))
-    _timed(prof, 'wmrb_hinge', lambda: lib.tmf_wmrb_hinge2_ordered(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk), _lib.ptr(st.sp),
-                                                            i32(m), i32(S), c, _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part),
+    if pairs == 'bpr':
+        _timed(prof, 'bpr_pairs', lambda: lib.tmf_bpr_pairs(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk), _lib.ptr(st.sp),
+                                                            i32(m), i32(S), _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part),
                                                             _lib.ptr(w.hinge_order), s))
+    else:
+        _timed(prof, 'wmrb_hinge', lambda: lib.tmf_wmrb_hinge2_ordered(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk), _lib.ptr(st.sp),
+                                                                i32(m), i32(S), c, _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part),
+                                                                _lib.ptr(w.hinge_order), s))
     if st.row_stationary:
         # gradU + finish in one row-stationary kernel (lane groups own users and walk the slices; no partial rows)
         _timed(prof, 'wmrb_gradu', lambda: getattr(lib, 'tmf_wmrb_gradu4' + st.sfx)(
@@ -1235,12 +1253,19 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
                                                                           r, user_epi, adam, s))
 
 
-def epoch_wmrb(st, adam, c, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM, user_out=None):
-    """One WMRB epoch.  loss_out receives sum over positives of log(1 + M_k).  item_epi / user_epi as in epoch_mse."""
+def epoch_wmrb(st, adam, c, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM, user_out=None,
+               pairs='hinge'):
+    """One WMRB epoch.  loss_out receives sum over positives of log(1 + M_k).  item_epi / user_epi as in epoch_mse.
+    pairs='bpr': one BPRLoss epoch - the same scores, gathers and item pass around tmf_bpr_pairs (c is unused); loss_out receives
+    sum over positives of mean_s softplus(sp[u, s] - p_k).  Only on a sliced plan."""
     lib, p, w, r = _lib.get(), st.plan, st.wplan, st.r
     s = _lib.stream_ptr()
+    if pairs not in ('hinge', 'bpr'):
+        raise ValueError(f'epoch_wmrb: pairs={pairs!r} (hinge or bpr)')
+    if pairs == 'bpr' and not w.sliced:
+        raise ValueError('epoch_wmrb: pairs=bpr needs the sliced user pass (wmrb_plan_for(force_sliced=True))')
     if w.sliced:
-        _timed(prof, 'wmrb_user_pass', lambda: _wmrb_user_pass_sliced(lib, st, adam, c, prof, user_epi, user_out))
+        _timed(prof, 'wmrb_user_pass', lambda: _wmrb_user_pass_sliced(lib, st, adam, c, prof, user_epi, user_out, pairs))
     else:
         _timed(prof, 'wmrb_user_pass', lambda: getattr(lib, 'tmf_wmrb_user_pass' + st.sfx)(
             _lib.ptr(p.rowptr_u), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(w.R), p.n_users, w.S, c, _lib.ptr(st.U), _lib.ptr(st.V),

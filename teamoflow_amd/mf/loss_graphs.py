@@ -1,7 +1,7 @@
 """Loss graphs (plug-in interface of /root/reference/src/teamoflow/mf/loss_graphs.py).
 
-``MSELoss``, ``WMRBLoss``, ``KLDivergenceLoss`` and ``LogisticLoss`` (an extension: the reference has no pointwise logistic loss)
-with ``LinearEmbedding`` over indicator features are recognised by
+``MSELoss``, ``WMRBLoss``, ``KLDivergenceLoss``, ``LogisticLoss`` and ``BPRLoss`` (extensions: the reference has no logistic loss,
+pointwise or pairwise) with ``LinearEmbedding`` over indicator features are recognised by
 ``MatrixFactorization.fit`` (same isinstance dispatch as matrix_factorization.py:152-162) and run as
 fused HIP kernels; ``get_loss`` below is the generic differentiable definition used when the model is
 built from other plug-ins (dense features, custom embeddings), always called by keyword like
@@ -87,3 +87,17 @@ class LogisticLoss(LossGraph):
         y = torch.where(values > 0.0, torch.ones_like(p), -torch.ones_like(p))
         w = values.abs().to(p.dtype) if self.weighted else torch.ones_like(p)
         return -w * torch.nn.functional.logsigmoid(y * p)
+
+
+class BPRLoss(LossGraph):
+    """Extension (Bayesian personalised ranking, LightFM's and implicit's 'bpr'; not in the reference): the pairwise logistic loss over
+    the static negative table WMRBLoss samples from.  For every stored interaction k of user u with a value > 0 and score p_k, against
+    the user's row sp[u, :] of sampled scores:  loss_k = mean_s -log sigmoid(p_k - sp[u, s]).  Stored values <= 0 take no part, a
+    negative that coincides with one of the user's positives is not filtered (both as in WMRBLoss), and n_items / n_samples does
+    not enter."""
+
+    def get_loss(self, tf_interactions, tf_sample_predictions, tf_prediction_serial, n_items, n_samples, predictions=None):
+        mask = tf_interactions.values > 0.0
+        users = tf_interactions.indices[:, 0][mask]
+        pos = tf_prediction_serial[mask]
+        return -torch.nn.functional.logsigmoid(pos[:, None] - tf_sample_predictions[users]).mean(dim=1)

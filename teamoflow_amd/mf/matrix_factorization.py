@@ -3,10 +3,11 @@
 
 Dispatch (same isinstance test the reference uses at :115,:136-162): a model made of
 (``LinearEmbedding`` | ``BiasedLinearEmbedding``) x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss`` |
-``LogisticLoss``)
+``LogisticLoss`` | ``BPRLoss``)
 - or ``LinearEmbedding`` over ``SparseFeatures`` on either side -
 trains on the HIP engine (``_engine.py`` -> libtmf.so); for unbiased MSE / WMRB it needs a GPU - there is no CPU fallback for them.
-``LogisticLoss`` (an extension) takes the engine whenever there is a GPU and the generic path without one.
+``LogisticLoss`` and ``BPRLoss`` (extensions) take the engine whenever there is a GPU and the generic path without one; ``BPRLoss``
+trains full-batch on one GPU only and refuses ``batch_users`` / ``shard_items`` / ``data_parallel`` with ``NotImplementedError``.
 With ``relu_engine = True`` (off by default) a ``ReLUEmbedding`` side over indicator features or ``SparseFeatures`` trains there too.
 Any other combination of plug-ins (dense features, ReLU embeddings, user subclasses) trains
 through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins'
@@ -24,7 +25,7 @@ import torch
 from .. import _engine, _lib, _ops
 from .embedding_graphs import BiasedLinearEmbedding, Embeddings, LinearEmbedding, ReLUEmbedding
 from .initializer_graphs import NormalInitializer
-from .loss_graphs import KLDivergenceLoss, LogisticLoss, LossGraph, MSELoss, WMRBLoss
+from .loss_graphs import BPRLoss, KLDivergenceLoss, LogisticLoss, LossGraph, MSELoss, WMRBLoss
 from .sparse import IndicatorFeatures, SparseFeatures, SparseInteractions, default_device, is_indicator
 from .utils import gather_matrix_indices, random_sampler, random_sampler_device
 
@@ -35,7 +36,7 @@ GRAPH_MAX_WORK = 20_000_000    # interactions + sampled scores per epoch below w
 
 
 class SampleTableMissing(AttributeError):
-    """WMRB needs the static negative table: build the model with generate_sample=True
+    """WMRB and BPR need the static negative table: build the model with generate_sample=True
     (the reference fails with AttributeError inside gather_matrix_indices, matrix_factorization.py:153)."""
 
 
@@ -121,7 +122,7 @@ class MatrixFactorization:
         relu = getattr(self, 'relu_engine', False) and 5 * self.n_components <= 1024
         linear = (LinearEmbedding, ReLUEmbedding) if relu else (LinearEmbedding,)
         # a side is an engine side as Linear / BiasedLinear over indicator features, or as Linear over SparseFeatures with entries
-        if not (type(self.loss_graph) in (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss)
+        if not (type(self.loss_graph) in (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, BPRLoss)
                 and all((kind in linear and f.nnz > 0) if sparse else
                         (kind in linear + (BiasedLinearEmbedding,) and is_indicator(f))
                         for (kind, f), sparse in zip(sides, featured))):
@@ -153,10 +154,25 @@ class MatrixFactorization:
         has, and the generic path without one - MSE and WMRB have no CPU form and fail there."""
         return type(self.loss_graph) is not LogisticLoss or torch.cuda.is_available()
 
+    def _bpr_engine_allowed(self):
+        """BPRLoss (an extension, with a generic form) takes the engine whenever there is a GPU and the generic path without one."""
+        return type(self.loss_graph) is not BPRLoss or torch.cuda.is_available()
+
+    def _refuse_unbuilt_bpr_forms(self):
+        """BPRLoss trains full-batch on one GPU (or through the generic loop): the mini-batch, item-sharded and data-parallel fits have
+        call sites of their own for the pair step, which do not exist - such a fit is refused, never run as another loss or densely."""
+        if type(self.loss_graph) is not BPRLoss:
+            return
+        for name in ('batch_users', 'shard_items', 'data_parallel'):
+            if getattr(self, name, 0):
+                raise NotImplementedError(f'BPRLoss with {name}={getattr(self, name)!r}: only the single-GPU full-batch fit is built for '
+                                          f'this loss (set {name} back to its default)')
+
     def fit(self, epochs, user_features, item_features, tf_interactions, lr=1e-2):
         """matrix_factorization.py:96-187.  Re-initialises the weights on every call, runs ``epochs``
         full-batch steps (loss -> gradient of the SUM of the per-interaction losses -> a fresh Adam
         step), then stores user_embedding / item_embedding / *_trainable.  Returns None."""
+        self._refuse_unbuilt_bpr_forms()   # before any weight is drawn or plan built
         n_users, n_user_features = user_features.shape
         n_items, n_item_features = item_features.shape
         if not isinstance(self.user_repr_graph, ReLUEmbedding):
@@ -173,7 +189,7 @@ class MatrixFactorization:
         self._feature_weights = [None, None]   # padded engine weights of a side trained over SparseFeatures (embed_users / embed_items)
         self._relu_sides = [None, None]        # the _engine.ReLUSide of a ReLU side trained on the engine (embed_users / embed_items)
         if (self._on_fast_path(user_features, item_features) and (not kl or self._kl_engine_allowed())
-                and self._logistic_engine_allowed()):
+                and self._logistic_engine_allowed() and self._bpr_engine_allowed()):
             feats = [f if sparse else None for f, sparse in zip((user_features, item_features), self._sparse_feature_sides)]
             if self._fit_sparse(epochs, n_users, n_items, interactions, lr, U, V, *feats):
                 return
@@ -197,8 +213,8 @@ class MatrixFactorization:
         if interactions.device != dev:
             interactions = interactions.to(dev)
         loss = _engine.loss_name(self.loss_graph)
-        if loss == 'wmrb' and self.random_ind is None:
-            raise SampleTableMissing('WMRBLoss needs generate_sample=True (random_ind is None)')
+        if loss in _engine.PAIR_LOSSES and self.random_ind is None:
+            raise SampleTableMissing(f'{type(self.loss_graph).__name__} needs generate_sample=True (random_ind is None)')
         if getattr(self, 'batch_users', 0):
             if getattr(self, 'shard_items', 0) or self.data_parallel:
                 raise ValueError('batch_users cannot be combined with shard_items / data_parallel')
@@ -215,12 +231,12 @@ class MatrixFactorization:
         st, c = self._sparse_state(loss, n_users, n_items, interactions, U0, V0, dev, user_feat, item_feat)
         if st is None:
             return False   # an empty class: no moments to take (the reference's arithmetic gives NaN; the generic path keeps that)
-        denom = st.plan.n_pos if loss == 'wmrb' else 1 if loss == 'kl' else st.plan.nnz   # KL: the loss is one scalar, its mean is itself
+        denom = st.plan.n_pos if loss in _engine.PAIR_LOSSES else 1 if loss == 'kl' else st.plan.nnz   # KL: the loss is one scalar, its mean is itself
         self.loss_history_ = []
         step = self._sparse_step(st, loss, c, lr)
         # Launch-bound problems (a few hundred microseconds of kernels per epoch): capture an even number of
         # epochs into one hipGraph and replay it - the per-launch host cost disappears from the loop.
-        work = st.plan.nnz + (st.plan.n_users * st.wplan.S if loss == 'wmrb' else 0)
+        work = st.plan.nnz + (st.plan.n_users * st.wplan.S if loss in _engine.PAIR_LOSSES else 0)
         G = min(epochs - epochs % 2, GRAPH_EPOCHS)
         use_graph = G >= 4 and work <= GRAPH_MAX_WORK and os.environ.get('TMF_NO_GRAPH') is None and self.optimizer != 'adam'
         sums = self._run_epochs(step, epochs, G if use_graph else 0, denom, dev, t_plan).cpu().numpy()
@@ -229,9 +245,10 @@ class MatrixFactorization:
         return True
 
     def _sparse_state(self, loss, n_users, n_items, interactions, U0, V0, dev, user_feat=None, item_feat=None):
-        """(TrainState, c) of a single-GPU full-batch fit: the interaction plan, for WMRB the checked negative table, its plan and
-        c = n_items / n_samples, and the starting bias of a BiasedLinearEmbedding side.  (None, 0.0) for KL with an empty class."""
-        wmrb, kl = loss == 'wmrb', loss == 'kl'
+        """(TrainState, c) of a single-GPU full-batch fit: the interaction plan, for WMRB and BPR the checked negative table and its
+        plan (BPR: always the sliced user pass), for WMRB c = n_items / n_samples, and the starting bias of a BiasedLinearEmbedding
+        side.  (None, 0.0) for KL with an empty class."""
+        wmrb, kl = loss in _engine.PAIR_LOSSES, loss == 'kl'
         plan = _engine.InteractionPlan(interactions.indices, interactions.values, n_users, n_items,
                                        user_chunks=1 if wmrb else _engine.mse_user_chunks(), csc=not wmrb)
         if kl and (plan.n_pos == 0 or int((plan.val_u <= 0).sum()) == 0):
@@ -243,8 +260,9 @@ class MatrixFactorization:
                 raise ValueError(f'random_ind has shape {tuple(R.shape)}, expected [{n_users}, n_samples]')
             if R.numel() and (int(R.min()) < 0 or int(R.max()) >= n_items):
                 raise IndexError('random_ind holds item ids outside [0, n_items)')
-            c = self.n_items / self.n_samples  # constructor ints, true division (:167)
-            wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype)
+            if loss == 'wmrb':
+                c = self.n_items / self.n_samples  # constructor ints, true division (:167)
+            wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype, force_sliced=loss == 'bpr')
         r = self.n_components
         # a biased side starts from the bias an earlier fit left on the model, as in the reference (:139-146), else from zeros
         bias0 = [None if type(graph) is not BiasedLinearEmbedding else torch.zeros(r) if kept is None else kept
@@ -386,9 +404,9 @@ class MatrixFactorization:
             self._keep_aux_variables()
             predictions = user_embedding @ item_embedding.T
             tf_sample_predictions = tf_prediction_serial = None
-            if isinstance(self.loss_graph, WMRBLoss):
+            if isinstance(self.loss_graph, (WMRBLoss, BPRLoss)):
                 if random_ind is None:
-                    raise SampleTableMissing('WMRBLoss needs generate_sample=True (random_ind is None)')
+                    raise SampleTableMissing(f'{type(self.loss_graph).__name__} needs generate_sample=True (random_ind is None)')
                 tf_sample_predictions = torch.gather(predictions, 1, random_ind.to(torch.int64))
                 tf_prediction_serial = predictions[idx[:, 0], idx[:, 1]]
                 predictions = None
