@@ -442,6 +442,28 @@ tmf_adam tmf_adam_step(float lr, int step);
 int tmf_adam_state_rows_f32(float* W, const float* G, float* M, float* V, int64_t n_rows, int n_components,
                             tmf_adam adam, void* stream);
 
+/* EXTENSION (the reference has no regularisation): L2-regularised twins of the four table steps.  The objective gains
+ * alpha ||W||_F^2 per penalised table, so the raw gradient G of the data term (the TMF_EPI_GRAD output of the passes) becomes
+ *   g' = fl(g + fl(l2 * w)),   l2 = 2 alpha (fp32), w the weight BEFORE the step
+ * - one product and one sum, each rounded to nearest once, never contracted into an fma - and g' takes the op sequence of the
+ * function extended, unchanged.  l2 = 0 gives that function's bits.  G is only read.
+ *   tmf_adam_fresh_rows_l2_f32   W = fresh-Adam(W, g') in place over n_rows x ld floats (tmf_adam_fresh_rows_f32).
+ *   tmf_adam_fresh_rows_l2_bf16  the same on a bf16-stored table: widened, stepped in fp32, rounded once; G fp32 [n_rows, ld],
+ *                                ld = tmf_padded_ld_bf16 (tmf_adam_fresh_rows_bf16).
+ *   tmf_adam_state_rows_l2_f32   tmf_adam_state_rows_f32 with g' for g: the moments M, V see g'.
+ *   tmf_adam_bias_rows_l2_f32    tmf_adam_bias_rows_f32 with g' for g, w the raw weight W[i] (not E; the bias is never penalised);
+ *                                columns >= n_components of W and E are written as zeros; W, G, b_new, E 16-byte aligned, W != E.
+ * n_components outside [1, 1024], l2 negative or not finite (NaN included), a null table (n_rows > 0): TMF_E_INVALID and nothing
+ * is launched; n_rows == 0: TMF_OK. */
+int tmf_adam_fresh_rows_l2_f32(float* W, const float* G, int64_t n_rows, int n_components,
+                               tmf_adam adam, float l2, void* stream);
+int tmf_adam_fresh_rows_l2_bf16(void* W, const float* G, int64_t n_rows, int n_components,
+                                tmf_adam adam, float l2, void* stream);
+int tmf_adam_state_rows_l2_f32(float* W, const float* G, float* M, float* V, int64_t n_rows, int n_components,
+                               tmf_adam adam, float l2, void* stream);
+int tmf_adam_bias_rows_l2_f32(float* W, const float* G, const float* b_new, float* E, int64_t n_rows, int n_components,
+                              tmf_adam adam, float l2, void* stream);
+
 /* Deterministic sum of `n` floats into out[0] (fp64 accumulate, fixed order) - the reduce_mean
  * numerator of matrix_factorization.py:179. */
 int tmf_sum_f32(const float* x, int64_t n, double* out, void* stream);

@@ -745,6 +745,7 @@ class TrainState:
             self.V, self.V_nxt = V_tables
         self.bias_v = None if item_bias is None else BiasSide(self.V, item_bias, self.r)
         self.plan, self.wplan = plan, wplan
+        self.l2, self.l2_G = [0.0, 0.0], [None, None]   # set_l2: l2 = 2 alpha of (user, item) side; the gradient table of a penalised plain side
         need = dict(slab=max(plan.seg_u.n_slab, plan.seg_i.n_slab if plan.seg_i else 0,
                              wplan.seg_e.n_slab if wplan is not None and wplan.seg_e is not None else 0,
                              wplan.vrows.n_slab if wplan is not None and wplan.vrows is not None else 0,
@@ -820,6 +821,31 @@ class TrainState:
         out[:, :self.r] = W  # bf16: round-to-nearest-even, like the kernels' stores
         return out
 
+    def set_l2(self, user_alpha=0.0, item_alpha=0.0):
+        """L2 regularisation alpha ||W||_F^2 of either side's weight matrix (0 = none: nothing changes for that side).  A penalised
+        side steps from g' = g + l2 w, l2 = 2 alpha in fp32, by the _l2 twin of its table step; for that it emits its raw gradient
+        (TMF_EPI_GRAD) where it ran the fused fresh-Adam epilogue.  A plain side gets a gradient table in its second buffer's place
+        and steps in place (no swap); a side over sparse features likewise for its weights; a biased side has its table already."""
+        sides = ((user_alpha, self.feat_u, self.bias_u, self.U, 'U_nxt'), (item_alpha, self.feat_v, self.bias_v, self.V, 'V_nxt'))
+        for k, (alpha, feat, bias, W, nxt) in enumerate(sides):
+            l2 = ctypes.c_float(2.0 * float(alpha)).value
+            if not (0.0 <= l2 < float('inf')):
+                raise ValueError(f'alpha={alpha!r} of the {("user", "item")[k]} side is negative or not finite')
+            if l2 == 0.0:
+                continue
+            if self.relu_u is not None or self.relu_v is not None:   # epoch_relu knows no penalised side
+                raise NotImplementedError('L2 regularisation next to a ReLU side on the engine is not built')
+            self.l2[k] = l2
+            if feat is not None:
+                feat.l2, feat.GW, feat.W_nxt = l2, torch.empty_like(feat.W), None
+            elif bias is not None:
+                bias.l2 = l2
+            else:
+                if getattr(self, nxt) is None:
+                    raise NotImplementedError('L2 regularisation of a table that several states step is not built')
+                setattr(self, nxt, None)   # stepped in place from now on: the gradient table takes the second buffer's place
+                self.l2_G[k] = torch.empty(W.shape[0], self.ld, dtype=torch.float32, device=W.device)
+
     def swap(self):
         if self.U_nxt is not None:
             self.U, self.U_nxt = self.U_nxt, self.U
@@ -840,6 +866,7 @@ class BiasSide:
         if b0.numel() != r:
             raise ValueError(f'linear bias of {b0.numel()} elements for n_components={r}')
         self.r = int(r)
+        self.l2 = 0.0   # TrainState.set_l2
         self.W = E.clone()
         self.b = torch.zeros(ld, dtype=torch.float32, device=E.device)
         self.b[:r] = b0
@@ -858,20 +885,51 @@ def bias_update(side, E, adam, prof=None, tag=''):
     rows = E.shape[0]
     _timed(prof, tag + 'bias_colsum', lambda: lib.tmf_bias_colsum_f32(P(side.G), rows, side.r, P(side.part), side.part_rows, None, s))
     _timed(prof, tag + 'bias_adam', lambda: lib.tmf_bias_adam_f32(P(side.part), side.part_rows, P(side.b), P(side.g_b), side.r, adam, s))
+    if side.l2:   # the weights are penalised, the bias never: its step above saw the raw gradient
+        _timed(prof, tag + 'adam_bias_rows_l2', lambda: lib.tmf_adam_bias_rows_l2_f32(P(side.W), P(side.G), P(side.b), P(E), rows, side.r,
+                                                                                      adam, side.l2, s))
+        return
     _timed(prof, tag + 'adam_bias_rows', lambda: lib.tmf_adam_bias_rows_f32(P(side.W), P(side.G), P(side.b), P(E), rows, side.r, adam, s))
+
+
+def _plain_epi(st, k):
+    """(epilogue, output table) of the pass of a PLAIN side k (0 = user, 1 = item): the fused fresh-Adam step into the second buffer,
+    or, penalised (TrainState.set_l2), the raw gradient into the side's gradient table."""
+    return (_lib.EPI_GRAD, st.l2_G[k]) if st.l2_G[k] is not None else (_lib.EPI_ADAM, None)
+
+
+def plain_l2_update(st, adam, prof=None):
+    """The in-place step W = fresh-Adam(W, G + l2 W) of every penalised plain side from its gradient table (filled by this epoch's
+    pass; both passes have read the pre-update tables by then).  Stream-ordered, no host scalars: graph-capturable."""
+    lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
+    for k, (W, tag) in enumerate(((st.U, 'user_'), (st.V, 'item_'))):
+        if st.l2_G[k] is not None:
+            step = getattr(lib, 'tmf_adam_fresh_rows_l2' + st.sfx)
+            _timed(prof, tag + 'adam_rows_l2', lambda: step(P(W), P(st.l2_G[k]), W.shape[0], st.r, adam, st.l2[k], s))
+
+
+def epoch_plain_l2(st, adam, loss_out, loss='mse', c=0.0, prof=None):
+    """One epoch of a state of two plain sides of which at least one is penalised: the loss's own epoch, a penalised side emitting its
+    raw gradient where the other keeps the fused epilogue; then the regularised steps in place and the swap of an unpenalised side."""
+    (ue, uo), (ie, io) = _plain_epi(st, 0), _plain_epi(st, 1)
+    run_epoch(st, adam, loss_out, loss, c, ie, io, prof, ue, uo)
+    plain_l2_update(st, adam, prof)
+    st.swap()
 
 
 def epoch_biased(st, adam, loss_out, loss='mse', c=0.0, prof=None):
     """One epoch of a state with at least one biased side: the loss's own epoch on the effective tables, a biased side emitting
     its raw gradient (TMF_EPI_GRAD) where an unbiased one keeps the fused fresh-Adam epilogue into its second buffer; then the
-    bias and row updates of the biased sides (both passes have read the pre-update tables by then) and the swap of the others."""
-    ue, uo = (_lib.EPI_GRAD, st.bias_u.G) if st.bias_u is not None else (_lib.EPI_ADAM, None)
-    ie, io = (_lib.EPI_GRAD, st.bias_v.G) if st.bias_v is not None else (_lib.EPI_ADAM, None)
+    bias and row updates of the biased sides (both passes have read the pre-update tables by then) and the swap of the others.
+    A penalised plain side (TrainState.set_l2) emits its raw gradient too and steps in place (plain_l2_update)."""
+    ue, uo = (_lib.EPI_GRAD, st.bias_u.G) if st.bias_u is not None else _plain_epi(st, 0)
+    ie, io = (_lib.EPI_GRAD, st.bias_v.G) if st.bias_v is not None else _plain_epi(st, 1)
     run_epoch(st, adam, loss_out, loss, c, ie, io, prof, ue, uo)
     if st.bias_u is not None:
         bias_update(st.bias_u, st.U, adam, prof, 'user_')
     if st.bias_v is not None:
         bias_update(st.bias_v, st.V, adam, prof, 'item_')
+    plain_l2_update(st, adam, prof)
     st.swap()
 
 
@@ -892,6 +950,7 @@ class FeatureSide:
         self.n_slab = max(self.plan.seg_u.n_slab, self.plan.seg_i.n_slab)
         self.W, self.W_nxt = W0, torch.empty_like(W0)
         self.G = torch.empty(rows, W0.shape[1], dtype=torch.float32, device=dev)
+        self.l2, self.GW = 0.0, None   # TrainState.set_l2: l2 > 0 = the weights step in place from GW [n_features, ld] (no W_nxt)
 
 
 def feature_forward(plan, W, E, slab, r):
@@ -915,8 +974,17 @@ def embed_features(F, W, r, chunk=DEFAULT_CHUNK):
 
 
 def feature_backward(side, slab, adam):
-    """W_nxt[f] = fresh_adam(W[f], sum_i x_if G[i]) over the CSC lists (a feature no row carries keeps its weights), then the swap."""
+    """W_nxt[f] = fresh_adam(W[f], sum_i x_if G[i]) over the CSC lists (a feature no row carries keeps its weights), then the swap.
+    With penalised weights (side.l2 > 0): the sums as a table of their own, then the regularised step in place and no swap."""
     lib, s, P, p = _lib.get(), _lib.stream_ptr(), _lib.ptr, side.plan
+    if side.l2:
+        # penalised weights: dW = F^T G into GW (a feature no row carries gets a zero row), then W = fresh-Adam(W, dW + l2 W) in
+        # place over EVERY feature - one no row carries decays, its penalty gradient is not zero
+        _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(side.G), None, P(side.GW), P(slab),
+                                         side.r, _lib.EPI_GRAD, adam, s), lib)
+        _row_pass_finish(lib, p.seg_i, slab, None, side.GW, side.r, _lib.EPI_GRAD, adam, s)
+        _lib.check(lib.tmf_adam_fresh_rows_l2_f32(P(side.W), P(side.GW), side.W.shape[0], side.r, adam, side.l2, s), lib)
+        return
     _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(side.G), P(side.W), P(side.W_nxt), P(slab),
                                      side.r, _lib.EPI_ADAM, adam, s), lib)
     _row_pass_finish(lib, p.seg_i, slab, side.W, side.W_nxt, side.r, _lib.EPI_ADAM, adam, s)
@@ -927,10 +995,12 @@ def epoch_featured(st, adam, loss_out, loss='mse', c=0.0, prof=None):
     """One epoch of a state with at least one side over sparse features, after epoch_biased: the loss's own epoch on the effective
     tables, a featured (or biased) side emitting its raw gradient (TMF_EPI_GRAD) where a plain one keeps the fused fresh-Adam
     epilogue; then, for every featured side, the step of its weights from G and the rebuilt E = F W (both passes of the epoch
-    have read the pre-update tables by then), the updates of a biased side, and the swap of the plain ones.
+    have read the pre-update tables by then), the updates of a biased side, the in-place step of a penalised plain side
+    (TrainState.set_l2) and the swap of the other plain ones.
     Stream-ordered, nothing allocated, no host reads, no atomics: graph-capturable and bit-reproducible."""
     sides = [(st.feat_u, st.bias_u, st.U, 'user_'), (st.feat_v, st.bias_v, st.V, 'item_')]
-    (ue, uo), (ie, io) = [(_lib.EPI_GRAD, (f or b).G) if (f or b) is not None else (_lib.EPI_ADAM, None) for f, b, _, _ in sides]
+    (ue, uo), (ie, io) = [(_lib.EPI_GRAD, (f or b).G) if (f or b) is not None else _plain_epi(st, k)
+                          for k, (f, b, _, _) in enumerate(sides)]
     run_epoch(st, adam, loss_out, loss, c, ie, io, prof, ue, uo)
     for feat, bias, E, tag in sides:
         if feat is not None:
@@ -938,6 +1008,7 @@ def epoch_featured(st, adam, loss_out, loss='mse', c=0.0, prof=None):
             _timed(prof, tag + 'feat_forward', lambda: feature_forward(feat.plan, feat.W, E, st.slab, feat.r))
         elif bias is not None:
             bias_update(bias, E, adam, prof, tag)
+    plain_l2_update(st, adam, prof)
     st.swap()
 
 

@@ -122,6 +122,10 @@ _BASE_SIGNATURES = {
     'tmf_relu_adam_weights_f32': (_I, [_P, _L, _P, _P, _P, _I, _I, Adam, _P]),
     'tmf_adam_step': (Adam, [_F, _I]),
     'tmf_adam_state_rows_f32': (_I, [_P, _P, _P, _P, _L, _I, Adam, _P]),
+    'tmf_adam_fresh_rows_l2_f32': (_I, [_P, _P, _L, _I, Adam, _F, _P]),
+    'tmf_adam_fresh_rows_l2_bf16': (_I, [_P, _P, _L, _I, Adam, _F, _P]),
+    'tmf_adam_state_rows_l2_f32': (_I, [_P, _P, _P, _P, _L, _I, Adam, _F, _P]),
+    'tmf_adam_bias_rows_l2_f32': (_I, [_P, _P, _P, _P, _L, _I, Adam, _F, _P]),
     'tmf_mse_pass_bf16': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
     'tmf_wsum_rows4_bf16': (_I, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _I32, _P, _SZ, _P]),
     'tmf_wsum_rows5_bf16': (_I, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I, _I, Adam, _I32, _P, _SZ, _P]),

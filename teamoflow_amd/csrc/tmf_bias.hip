@@ -96,13 +96,17 @@ __global__ __launch_bounds__(kCombineThreads) void k_bias_combine(const double* 
 
 // W <- fresh-Adam(W, G) in place (the arithmetic of k_adam_rows), E <- W + b, one float4 per lane, grid-stride.  Columns >= r of W
 // and E are written as zeros whatever W, G and b hold there.
+// L2 = true: the step takes g' = fl(g + fl(l2 w)) (l2_grad, tmf_common.h), w the RAW pre-update weight - the bias is not penalised and
+// E plays no part in g'.  L2 = false ignores l2.
+template <bool L2>
 __global__ __launch_bounds__(256) void k_adam_bias_rows(float4* __restrict__ W, const float4* __restrict__ Gr,
                                                         const float4* __restrict__ b, float4* __restrict__ E, int64_t n4, int L4, int r,
-                                                        tmf_adam adam) {
+                                                        tmf_adam adam, float l2) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         const int c4 = (int)(i & (int64_t)(L4 - 1));
         const float4 w = W[i];
-        const float4 g = Gr[i];
+        float4 g = Gr[i];
+        if constexpr (L2) g = make_float4(l2_grad(g.x, w.x, l2), l2_grad(g.y, w.y, l2), l2_grad(g.z, w.z, l2), l2_grad(g.w, w.w, l2));
         const float4 bb = b[c4];
         // all four columns are stepped and the dead ones masked afterwards: whole 16-byte loads, no divergent branch in the sweep
         const float4 nw = make_float4(adam_fresh(w.x, g.x, adam), adam_fresh(w.y, g.y, adam), adam_fresh(w.z, g.z, adam),
@@ -163,8 +167,25 @@ extern "C" int tmf_adam_bias_rows_f32(float* W, const float* G, const float* b_n
     const int64_t n4 = n_rows * (geom.ld / 4);
     const int64_t want = (n4 + 255) / 256;
     const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);
-    hipLaunchKernelGGL(k_adam_bias_rows, dim3(blocks), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<float4*>(W),
+    hipLaunchKernelGGL(k_adam_bias_rows<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<float4*>(W),
                        reinterpret_cast<const float4*>(G), reinterpret_cast<const float4*>(b_new), reinterpret_cast<float4*>(E), n4,
-                       geom.ld / 4, n_components, adam);
+                       geom.ld / 4, n_components, adam, 0.f);
     return check_launch("tmf_adam_bias_rows_f32");
+}
+
+extern "C" int tmf_adam_bias_rows_l2_f32(float* W, const float* G, const float* b_new, float* E, int64_t n_rows, int n_components,
+                                         tmf_adam adam, float l2, void* stream) {
+    const RowGeom geom = row_geom(n_components);
+    TMF_REQUIRE(geom.ld > 0, "adam_bias_rows_l2: unsupported n_components %d", n_components);
+    TMF_REQUIRE(l2_valid(l2), "adam_bias_rows_l2: l2=%g is negative or not finite", (double)l2);
+    if (n_rows == 0) return TMF_OK;
+    TMF_REQUIRE(W && G && b_new && E && n_rows > 0, "adam_bias_rows_l2: bad arguments");
+    TMF_REQUIRE(W != E, "adam_bias_rows_l2: W and E are the same table");
+    TMF_REQUIRE(aligned16(W) && aligned16(G) && aligned16(b_new) && aligned16(E), "adam_bias_rows_l2: a table is not 16-byte aligned");
+    const int64_t n4 = n_rows * (geom.ld / 4);
+    const int64_t want = (n4 + 255) / 256;
+    hipLaunchKernelGGL(k_adam_bias_rows<true>, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<float4*>(W), reinterpret_cast<const float4*>(G), reinterpret_cast<const float4*>(b_new),
+                       reinterpret_cast<float4*>(E), n4, geom.ld / 4, n_components, adam, l2);
+    return check_launch("tmf_adam_bias_rows_l2_f32");
 }

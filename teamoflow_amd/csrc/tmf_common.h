@@ -591,6 +591,13 @@ __device__ __forceinline__ float adam_fresh(float w, float g, const tmf_adam a) 
     return w - __fdiv_rn(m * a.alpha, __fsqrt_rn(v) + a.eps);
 }
 
+// Gradient of one element under the penalty alpha w^2: g' = fl(g + fl(l2 w)), l2 = 2 alpha - a product and a sum, each rounded
+// once (the intrinsics are never contracted into an fma).
+__device__ __forceinline__ float l2_grad(float g, float w, float l2) { return __fadd_rn(g, __fmul_rn(l2, w)); }
+
+// l2 of the regularised steps: finite and not negative (NaN fails the comparison).
+inline bool l2_valid(float l2) { return l2 >= 0.f && l2 <= 3.402823466e38f; }
+
 template <int NV>
 __device__ __forceinline__ void adam_fresh(Frag<NV>& w, const Frag<NV>& g, const tmf_adam a) {
 #pragma unroll

@@ -555,12 +555,18 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_combine_rows(
 
 // ---------------------------------------------------------------------------------------------
 // K6 standalone: elementwise fresh-Adam over a [n_rows, ld] table (float4 per lane, grid-stride).
+// L2 = true: the L2-regularised form.  The gradient of alpha ||W||_F^2 joins the raw gradient before the step,
+//   g' = fl(g + fl(l2 w)),  l2 = 2 alpha,  w the pre-update weight
+// - two roundings, spelled with the non-contracted intrinsics (l2_grad, tmf_common.h) so that no fma forms under -ffp-contract=on
+// and g' can be restated bit for bit on the host; g' then takes the op sequence of the plain form unchanged.  L2 = false ignores l2.
 // ---------------------------------------------------------------------------------------------
+template <bool L2>
 __global__ __launch_bounds__(256) void k_adam_rows(float4* __restrict__ W, const float4* __restrict__ Gr,
-                                                   int64_t n4, tmf_adam adam) {
+                                                   int64_t n4, tmf_adam adam, float l2) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         float4 w = W[i];
-        const float4 g = Gr[i];
+        float4 g = Gr[i];
+        if constexpr (L2) g = make_float4(l2_grad(g.x, w.x, l2), l2_grad(g.y, w.y, l2), l2_grad(g.z, w.z, l2), l2_grad(g.w, w.w, l2));
         w.x = adam_fresh(w.x, g.x, adam);
         w.y = adam_fresh(w.y, g.y, adam);
         w.z = adam_fresh(w.z, g.z, adam);
@@ -569,11 +575,16 @@ __global__ __launch_bounds__(256) void k_adam_rows(float4* __restrict__ W, const
     }
 }
 
+template <bool L2>
 __global__ __launch_bounds__(256) void k_adam_rows_bf16(bf16x8* __restrict__ W, const float4* __restrict__ Gr,
-                                                        int64_t n8, tmf_adam adam) {
+                                                        int64_t n8, tmf_adam adam, float l2) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
         f32x8 w = __builtin_convertvector(W[i], f32x8);
-        const float4 a = Gr[2 * i], b = Gr[2 * i + 1];
+        float4 a = Gr[2 * i], b = Gr[2 * i + 1];
+        if constexpr (L2) {
+            a = make_float4(l2_grad(a.x, w[0], l2), l2_grad(a.y, w[1], l2), l2_grad(a.z, w[2], l2), l2_grad(a.w, w[3], l2));
+            b = make_float4(l2_grad(b.x, w[4], l2), l2_grad(b.y, w[5], l2), l2_grad(b.z, w[6], l2), l2_grad(b.w, w[7], l2));
+        }
         w[0] = adam_fresh(w[0], a.x, adam); w[1] = adam_fresh(w[1], a.y, adam);
         w[2] = adam_fresh(w[2], a.z, adam); w[3] = adam_fresh(w[3], a.w, adam);
         w[4] = adam_fresh(w[4], b.x, adam); w[5] = adam_fresh(w[5], b.y, adam);
@@ -585,12 +596,15 @@ __global__ __launch_bounds__(256) void k_adam_rows_bf16(bf16x8* __restrict__ W, 
 // Opt-in extension (not the reference's behaviour): Keras Adam with PERSISTENT moments, one step over a whole table.
 //   m += (g - m)(1 - b1);  v += (g g - v)(1 - b2);  w -= (m alpha_t) / (sqrt(v) + eps)
 // - the same fp32 op sequence as adam_fresh, which it equals bit for bit at step 1 with zero moments.
+// L2 = true: g' (above) for g - the moments see g'.
+template <bool L2>
 __global__ __launch_bounds__(256) void k_adam_state_rows(float4* __restrict__ W, const float4* __restrict__ Gr,
                                                          float4* __restrict__ M, float4* __restrict__ V2, int64_t n4,
-                                                         tmf_adam a) {
+                                                         tmf_adam a, float l2) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         float4 w = W[i], m = M[i], v = V2[i];
-        const float4 g = Gr[i];
+        float4 g = Gr[i];
+        if constexpr (L2) g = make_float4(l2_grad(g.x, w.x, l2), l2_grad(g.y, w.y, l2), l2_grad(g.z, w.z, l2), l2_grad(g.w, w.w, l2));
         float* wp = &w.x;
         float* mp = &m.x;
         float* vp = &v.x;
@@ -931,8 +945,8 @@ extern "C" int tmf_adam_fresh_rows_f32(float* W, const float* G, int64_t n_rows,
     const int64_t n4 = n_rows * geom.ld / 4;
     const int64_t want = (n4 + 255) / 256;
     const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);
-    hipLaunchKernelGGL(k_adam_rows, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<float4*>(W), reinterpret_cast<const float4*>(G), n4, adam);
+    hipLaunchKernelGGL(k_adam_rows<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<float4*>(W), reinterpret_cast<const float4*>(G), n4, adam, 0.f);
     return check_launch("tmf_adam_fresh_rows_f32");
 }
 
@@ -945,8 +959,8 @@ extern "C" int tmf_adam_fresh_rows_bf16(void* W, const float* G, int64_t n_rows,
     const int64_t n8 = n_rows * geom.ld / 8;
     const int64_t want = (n8 + 255) / 256;
     const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);
-    hipLaunchKernelGGL(k_adam_rows_bf16, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<bf16x8*>(W), reinterpret_cast<const float4*>(G), n8, adam);
+    hipLaunchKernelGGL(k_adam_rows_bf16<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<bf16x8*>(W), reinterpret_cast<const float4*>(G), n8, adam, 0.f);
     return check_launch("tmf_adam_fresh_rows_bf16");
 }
 
@@ -958,10 +972,53 @@ extern "C" int tmf_adam_state_rows_f32(float* W, const float* G, float* M, float
     TMF_REQUIRE(W && G && M && V && n_rows > 0, "adam_state_rows: bad arguments");
     const int64_t n4 = n_rows * geom.ld / 4;
     const int64_t want = (n4 + 255) / 256;
-    hipLaunchKernelGGL(k_adam_state_rows, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_adam_state_rows<false>, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<float4*>(W), reinterpret_cast<const float4*>(G), reinterpret_cast<float4*>(M),
-                       reinterpret_cast<float4*>(V), n4, adam);
+                       reinterpret_cast<float4*>(V), n4, adam, 0.f);
     return check_launch("tmf_adam_state_rows_f32");
+}
+
+extern "C" int tmf_adam_fresh_rows_l2_f32(float* W, const float* G, int64_t n_rows, int n_components,
+                                          tmf_adam adam, float l2, void* stream) {
+    const RowGeom geom = row_geom(n_components);
+    TMF_REQUIRE(geom.ld > 0, "adam_fresh_rows_l2: unsupported n_components %d", n_components);
+    TMF_REQUIRE(l2_valid(l2), "adam_fresh_rows_l2: l2=%g is negative or not finite", (double)l2);
+    if (n_rows == 0) return TMF_OK;
+    TMF_REQUIRE(W && G && n_rows > 0, "adam_fresh_rows_l2: bad arguments");
+    const int64_t n4 = n_rows * geom.ld / 4;
+    const int64_t want = (n4 + 255) / 256;
+    hipLaunchKernelGGL(k_adam_rows<true>, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<float4*>(W), reinterpret_cast<const float4*>(G), n4, adam, l2);
+    return check_launch("tmf_adam_fresh_rows_l2_f32");
+}
+
+extern "C" int tmf_adam_fresh_rows_l2_bf16(void* W, const float* G, int64_t n_rows, int n_components,
+                                           tmf_adam adam, float l2, void* stream) {
+    const RowGeom geom = row_geom_bf16(n_components);
+    TMF_REQUIRE(geom.ld > 0, "adam_fresh_rows_l2: unsupported n_components %d", n_components);
+    TMF_REQUIRE(l2_valid(l2), "adam_fresh_rows_l2: l2=%g is negative or not finite", (double)l2);
+    if (n_rows == 0) return TMF_OK;
+    TMF_REQUIRE(W && G && n_rows > 0, "adam_fresh_rows_l2: bad arguments");
+    const int64_t n8 = n_rows * geom.ld / 8;
+    const int64_t want = (n8 + 255) / 256;
+    hipLaunchKernelGGL(k_adam_rows_bf16<true>, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<bf16x8*>(W), reinterpret_cast<const float4*>(G), n8, adam, l2);
+    return check_launch("tmf_adam_fresh_rows_l2_bf16");
+}
+
+extern "C" int tmf_adam_state_rows_l2_f32(float* W, const float* G, float* M, float* V, int64_t n_rows, int n_components,
+                                          tmf_adam adam, float l2, void* stream) {
+    const RowGeom geom = row_geom(n_components);
+    TMF_REQUIRE(geom.ld > 0, "adam_state_rows_l2: unsupported n_components %d", n_components);
+    TMF_REQUIRE(l2_valid(l2), "adam_state_rows_l2: l2=%g is negative or not finite", (double)l2);
+    if (n_rows == 0) return TMF_OK;
+    TMF_REQUIRE(W && G && M && V && n_rows > 0, "adam_state_rows_l2: bad arguments");
+    const int64_t n4 = n_rows * geom.ld / 4;
+    const int64_t want = (n4 + 255) / 256;
+    hipLaunchKernelGGL(k_adam_state_rows<true>, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<float4*>(W), reinterpret_cast<const float4*>(G), reinterpret_cast<float4*>(M),
+                       reinterpret_cast<float4*>(V), n4, adam, l2);
+    return check_launch("tmf_adam_state_rows_l2_f32");
 }
 
 extern "C" int tmf_sum_f32(const float* x, int64_t n, double* out, void* stream) {

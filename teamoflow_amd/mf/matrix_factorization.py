@@ -14,6 +14,8 @@ through ``_fit_generic``: the reference's dense loop written with torch autograd
 own ``get_repr`` / ``get_loss`` - and so does KL without a GPU, with ``batch_users`` / ``shard_items`` /
 ``data_parallel`` set, or on a table with an empty class, and a biased side without a GPU, with those settings, with bf16 factor
 storage or with ``optimizer='adam'`` - the settings under which a side over ``SparseFeatures`` is handed over as a dense matrix too.
+``user_alpha`` / ``item_alpha`` > 0 (extensions, off by default) add ``alpha ||W_side||_F^2`` to the objective on either path: on the engine
+through the ``_l2`` twins of the table steps (``_engine.TrainState.set_l2``), in the generic loop as a term of the differentiated sum.
 """
 import os
 import timeit
@@ -111,6 +113,12 @@ class MatrixFactorization:
         # extension, OFF by default: True = a ReLUEmbedding side over eye() or SparseFeatures trains on the HIP engine
         # (_engine.ReLUSide / epoch_relu) where a biased side would; False = the generic path, as before
         self.relu_engine = False
+        # extension, OFF by default (the reference has no regularisation): the objective whose gradient a fit takes gains
+        # user_alpha ||W_user||_F^2 + item_alpha ||W_item||_F^2 over the sides' weight matrices (never a bias); loss_history_ stays
+        # the data term.  The penalty stands against the gradient of a SUM over interactions: a useful alpha grows with the
+        # interactions per row
+        self.user_alpha = 0.0
+        self.item_alpha = 0.0
 
     # ------------------------------------------------------------------------------------------
     # training
@@ -168,11 +176,38 @@ class MatrixFactorization:
                 raise NotImplementedError(f'BPRLoss with {name}={getattr(self, name)!r}: only the single-GPU full-batch fit is built for '
                                           f'this loss (set {name} back to its default)')
 
+    def _alphas(self):
+        """(user_alpha, item_alpha) as floats, checked: negative or non-finite raises ValueError."""
+        out = []
+        for name in ('user_alpha', 'item_alpha'):
+            try:
+                a = float(getattr(self, name, 0.0))
+            except (TypeError, ValueError):
+                raise ValueError(f'{name}={getattr(self, name)!r} is not a number') from None
+            if not 0.0 <= 2.0 * a <= float(np.finfo(np.float32).max):   # 2 alpha travels as an fp32 scalar; NaN fails both comparisons
+                raise ValueError(f'{name}={a!r}: the L2 penalty must be finite and >= 0')
+            out.append(a)
+        return tuple(out)
+
+    def _refuse_unbuilt_l2_forms(self, alphas):
+        """A penalised side trains full-batch on one GPU through the table steps' _l2 twins, or through the generic loop.  The ReLU
+        engine, the mini-batch, item-sharded and data-parallel fits have update sites of their own that know no penalty: such a fit
+        is refused - never run unregularised."""
+        if not any(alphas):
+            return
+        relu_side = ReLUEmbedding in (type(self.user_repr_graph), type(self.item_repr_graph))
+        for name in ('relu_engine', 'batch_users', 'shard_items', 'data_parallel'):
+            if getattr(self, name, 0) and (name != 'relu_engine' or relu_side):
+                raise NotImplementedError(f'user_alpha / item_alpha > 0 with {name}={getattr(self, name)!r}: L2 regularisation is built for '
+                                          f'the single-GPU full-batch fit and the generic loop only (set {name} back to its default)')
+
     def fit(self, epochs, user_features, item_features, tf_interactions, lr=1e-2):
         """matrix_factorization.py:96-187.  Re-initialises the weights on every call, runs ``epochs``
         full-batch steps (loss -> gradient of the SUM of the per-interaction losses -> a fresh Adam
         step), then stores user_embedding / item_embedding / *_trainable.  Returns None."""
         self._refuse_unbuilt_bpr_forms()   # before any weight is drawn or plan built
+        alphas = self._alphas()
+        self._refuse_unbuilt_l2_forms(alphas)
         n_users, n_user_features = user_features.shape
         n_items, n_item_features = item_features.shape
         if not isinstance(self.user_repr_graph, ReLUEmbedding):
@@ -279,8 +314,12 @@ class MatrixFactorization:
                                    Wr0=torch.randn(n_features, aux, device=dev) if kept_w is None else kept_w,
                                    b0=torch.zeros(aux, device=dev) if kept_b is None else kept_b)
                 feat[side] = None
-        return _engine.TrainState(U0, V0, plan, r, wplan, dtype=self.factor_dtype, kl=kl, user_bias=bias0[0], item_bias=bias0[1],
-                                  user_feat=feat[0], item_feat=feat[1], user_relu=relu0[0], item_relu=relu0[1]), c
+        st = _engine.TrainState(U0, V0, plan, r, wplan, dtype=self.factor_dtype, kl=kl, user_bias=bias0[0], item_bias=bias0[1],
+                                user_feat=feat[0], item_feat=feat[1], user_relu=relu0[0], item_relu=relu0[1])
+        alphas = self._alphas()
+        if any(alphas):   # never called with zeros: an unpenalised fit is today's state, launch for launch
+            st.set_l2(*alphas)
+        return st, c
 
     def _sparse_step(self, st, loss, c, lr):
         """step(epoch, out): one epoch, its loss sum into ``out``, by the reference's fresh Adam or by optimizer='adam' (kept moments)."""
@@ -295,6 +334,9 @@ class MatrixFactorization:
             if st.bias_u is not None or st.bias_v is not None:
                 return lambda epoch, out: _engine.epoch_biased(st, adam, out, loss, c)
 
+            if any(st.l2):   # a penalised plain side: its raw gradient, then the regularised step in place
+                return lambda epoch, out: _engine.epoch_plain_l2(st, adam, out, loss, c)
+
             def fresh(epoch, out):
                 _engine.run_epoch(st, adam, out, loss, c)
                 st.swap()
@@ -302,13 +344,19 @@ class MatrixFactorization:
         if self.factor_dtype is not torch.float32:
             raise ValueError("optimizer='adam' (persistent moments) needs float32 factor tables")
         lib = _lib.get()
-        gU, gV = torch.empty_like(st.U), torch.empty_like(st.V)
-        sides = [(W, G, torch.zeros_like(W), torch.zeros_like(W)) for W, G in ((st.U, gU), (st.V, gV))]   # table, gradient, m, v
+        # a penalised side has its gradient table already (TrainState.set_l2)
+        gU, gV = (torch.empty_like(W) if G is None else G for W, G in zip((st.U, st.V), st.l2_G))
+        sides = [(W, G, torch.zeros_like(W), torch.zeros_like(W), l2)
+                 for W, G, l2 in ((st.U, gU, st.l2[0]), (st.V, gV, st.l2[1]))]   # table, gradient, m, v, l2 = 2 alpha
 
         def persistent(epoch, out):   # raw gradients of both sides from the pre-update tables, then one Adam step with state, in place
             a = lib.tmf_adam_step(float(lr), epoch + 1)
             _engine.run_epoch(st, a, out, loss, c, _lib.EPI_GRAD, gV, None, _lib.EPI_GRAD, gU)
-            for W, G, M, V2 in sides:
+            for W, G, M, V2, l2 in sides:
+                if l2:   # the moments see g' = g + l2 w
+                    _lib.check(lib.tmf_adam_state_rows_l2_f32(_lib.ptr(W), _lib.ptr(G), _lib.ptr(M), _lib.ptr(V2), W.shape[0],
+                                                              self.n_components, a, l2, _lib.stream_ptr()), lib)
+                    continue
                 _lib.check(lib.tmf_adam_state_rows_f32(_lib.ptr(W), _lib.ptr(G), _lib.ptr(M), _lib.ptr(V2), W.shape[0],
                                                        self.n_components, a, _lib.stream_ptr()), lib)
         return persistent
@@ -393,6 +441,7 @@ class MatrixFactorization:
         self.loss_history_ = []
         cumulative_time = 0.0
         random_ind = None if self.random_ind is None else torch.as_tensor(self.random_ind).to(dev)
+        user_alpha, item_alpha = self._alphas()
         for epoch in range(epochs):
             start = timeit.default_timer()
             user_embedding, self.user_trainable = self.user_repr_graph.get_repr(
@@ -417,7 +466,13 @@ class MatrixFactorization:
                                                tf_prediction_serial=tf_prediction_serial, predictions=predictions,
                                                n_items=self.n_items, n_samples=self.n_samples)
             variables = self.user_trainable + self.item_trainable
-            grads = torch.autograd.grad(loss_fn.sum(), variables, allow_unused=True)
+            objective = loss_fn.sum()
+            for penalty, graph, trainable in ((user_alpha, self.user_repr_graph, self.user_trainable),
+                                              (item_alpha, self.item_repr_graph, self.item_trainable)):
+                if penalty:   # penalty ||W||_F^2 over the side's weight matrices: the weights, and relu_weight of a ReLU side - never a bias
+                    for w in trainable[:2 if isinstance(graph, ReLUEmbedding) else 1]:
+                        objective = objective + penalty * (w * w).sum()
+            grads = torch.autograd.grad(objective, variables, allow_unused=True)
             with torch.no_grad():
                 for w, g in zip(variables, grads):
                     if g is not None:  # fresh Adam, t = 1 (:176)
@@ -822,6 +877,7 @@ def _save_to_disk(model, path, include_samples=True, allow_pickle=False):
             'item_embedding': None if model.item_embedding is None else model.item_embedding.detach().float().cpu(),
             'factor_dtype': str(model.factor_dtype).replace('torch.', ''),
             'optimizer': getattr(model, 'optimizer', 'fresh_adam'),
+            'user_alpha': float(getattr(model, 'user_alpha', 0.0)), 'item_alpha': float(getattr(model, 'item_alpha', 0.0)),
             'loss_history': [float(x) for x in (getattr(model, 'loss_history_', []) or [])],
             'random_ind': (torch.as_tensor(model.random_ind).cpu() if include_samples and model.random_ind is not None else None)}
     torch.save(blob, path)
@@ -843,6 +899,7 @@ def _load_from_disk(cls, path, device=None, allow_pickle=False):
     dt = getattr(torch, blob['factor_dtype'])
     model.factor_dtype = dt
     model.optimizer = blob.get('optimizer', 'fresh_adam')
+    model.user_alpha, model.item_alpha = float(blob.get('user_alpha', 0.0)), float(blob.get('item_alpha', 0.0))
     for name in ('user_embedding', 'item_embedding'):
         t = blob[name]
         setattr(model, name, None if t is None else t.to(device=dev, dtype=dt))
