@@ -321,6 +321,24 @@ int tmf_wmrb_scores6_f32(const int32_t* ids, const int32_t* outs, const int64_t*
 int tmf_wmrb_scores6_bf16(const int32_t* ids, const int32_t* outs, const int64_t* chunk_ptr, int64_t n_groups, int32_t n_slices,
                           int64_t n_users, int64_t n_items, const void* U, const void* V, float* sp, float* p, int n_components,
                           void* stream);
+/* Item runs (speed only - the same sp / p as tmf_wmrb_scores3 up to the order of the fp32 sum inside a dot product, exact on dyadic
+ * data): one workgroup per chunk = (item slice, group of tmf_wmrb_scores7_users_per_group() consecutive users) as for
+ * tmf_wmrb_scores6, the group's rows in LDS - but the chunk's entries come by ITEM, so the users of a group that need a row of V
+ * share one load of it.
+ *   steps [n_steps] 16-byte records {int32 item; uint8 local_user[4]; uint16 slot[4]}: one item and up to 4 users of the group
+ *                   that need it; a short step is padded with a valid local user and the slot tmf_wmrb_scores7_slots()
+ *   place [n_entries]      where the score of a slot goes: >= 0 -> sp[place], < 0 -> p[~place]
+ *   sub_step / sub_place [n_sub + 1]   first step / first place of every SUB-CHUNK: the steps whose scores fill one LDS buffer of
+ *                   at most tmf_wmrb_scores7_slots() slots; the buffer is then stored slot i -> place[sub_place[sub] + i]
+ *   chunk_sub [n_slices * n_groups + 1]   first sub-chunk of chunk slice * n_groups + group
+ * Every (user, item) pair of the epoch is in exactly one non-pad slot.  fp32 rows of 65..128 components, n_items < 2^24, V below
+ * 4 GB (tmf_wmrb_scores7_supported; 0 for everything else, bf16 included). */
+int tmf_wmrb_scores7_users_per_group(void);
+int tmf_wmrb_scores7_slots(void);
+int tmf_wmrb_scores7_supported(int n_components, int bf16, int64_t n_items);
+int tmf_wmrb_scores7_f32(const void* steps, const int32_t* place, const int64_t* sub_step, const int64_t* sub_place,
+                         const int32_t* chunk_sub, int64_t n_groups, int32_t n_slices, int64_t n_users, int64_t n_items,
+                         const void* U, const void* V, float* sp, float* p, int n_components, void* stream);
 int tmf_wmrb_hinge2(const int64_t* rowptr, const float* val, const float* p, const float* sp, int32_t n_users,
                     int32_t n_samples, float c, float* delta, float* D, float* loss_part, void* stream);
 /* The same with the order in which the waves take the users (a permutation of 0 .. n_users - 1, or NULL = 0, 1, 2 ...): a user

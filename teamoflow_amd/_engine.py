@@ -475,7 +475,7 @@ class WmrbPlan:
         self.hinge_order = hinge_user_order(plan.rowptr_u)
         self.D = self.wbuf[nnz:].view(m, S)
         self._lists = None
-        self.s5 = self.s6 = None   # Scores5Plan / Scores6Plan, built by the TrainState that wants that scores kernel (scores5_wanted, scores6_wanted)
+        self.s5 = self.s6 = self.s7 = None   # Scores5Plan / Scores6Plan / Scores7Plan, built by the TrainState that wants that scores kernel (scores5_wanted ...)
 
     def lists(self, plan):
         """tmf_slice_lists of the sliced pass (kept alive with the plan)."""
@@ -646,6 +646,131 @@ class Scores6Plan(_ScoreStreams):
         self.chunk_ptr, _ = self._build(plan, wplan, UG, lambda grp, item: (item // width) * ng + grp, ns * ng)
 
 
+SCORES7_SLICE_BYTES = 4 << 20   # slices of the item-run scores kernel (TMF_S7_SLICE_BYTES)
+SCORES7_MIN_SHARE = 1.5         # expected entries per distinct row of a group from which sharing the row load pays (C4: 2.9; config-5 shard: 0.29)
+
+
+def scores7_wanted(plan, wplan, n_components, dtype=torch.float32):
+    """Whether the sliced user pass computes its scores by item runs (tmf_wmrb_scores7, Scores7Plan): a group of users' rows in LDS,
+    one load of a row of V for all users of the group that need it.  TMF_SCORES7 = 1 | 0 forces the choice (where the kernel exists:
+    fp32 rows of 65..128 components, fewer than 2^24 items, a table below 4 GB, int32 places); TMF_SCORES5=1 / TMF_SCORES6=1 win
+    over the default, which is on where the catalog is far beyond one slice and a group of users meets every row of a slice
+    SCORES7_MIN_SHARE times or more: UG (S + nnz / m) / n."""
+    env = os.environ.get('TMF_SCORES7')
+    if env == '0' or wplan is None or not wplan.sliced or not plan.col_u.is_cuda:
+        return False
+    m, S = wplan.R.shape
+    if m * S >= 2 ** 31 or plan.nnz >= 2 ** 31:
+        return False
+    lib = _lib.load_library()
+    if not lib.tmf_wmrb_scores7_supported(int(n_components), int(dtype is torch.bfloat16), int(plan.n_items)):
+        return False
+    if env == '1':
+        return True
+    if os.environ.get('TMF_SCORES5') == '1' or os.environ.get('TMF_SCORES6') == '1':
+        return False
+    if plan.n_items * row_bytes(n_components, dtype) < 8 * VISIT_SLICE_BYTES:
+        return False
+    UG = int(lib.tmf_wmrb_scores7_users_per_group())
+    return UG * (S + plan.nnz / max(m, 1)) / plan.n_items >= SCORES7_MIN_SHARE
+
+
+class Scores7Plan:
+    """Streams of tmf_wmrb_scores7 (include/tmf.h), built once per fit from the sliced plan; the builder needs no GPU.
+    Every (user, item) pair whose score the epoch needs - interaction k of the CSR (place ~k) and negative (u, pos) of the item-sorted
+    table (place u * S + pos) - is an ENTRY.  chunk = slice * n_groups + user group; the entries of a chunk, by (item, local user),
+    are cut every `slots` entries into SUB-CHUNKS (so a sub-chunk is an item range of its chunk; neighbours may share their border
+    item).  Inside a sub-chunk a run of entries with one item is cut into STEPS of up to K users; a slot is an entry's rank in its
+    sub-chunk by (local user, place order): the slots of a user are consecutive and so are their addresses in sp / p.
+      steps [n_steps, 4] int32   item | K 8-bit local users | K 16-bit slots; pads: the step's first user, slot = pad_slot
+      place [n_entries] int32    sub-chunk after sub-chunk, slot order
+      sub_step, sub_place [n_sub + 1] int64; chunk_sub [n_slices * n_groups + 1] int32"""
+
+    K = 4
+
+    def __init__(self, plan, wplan, n_components, dtype=torch.float32, slice_bytes=None, slots=None):
+        lib = _lib.load_library()
+        self.key = (int(n_components), dtype)
+        dev, i32, i64, K = plan.col_u.device, torch.int32, torch.int64, self.K
+        self.users_per_group = UG = int(lib.tmf_wmrb_scores7_users_per_group())
+        self.pad_slot = cap = int(lib.tmf_wmrb_scores7_slots())
+        self.slots = SL = max(1, min(cap, int(os.environ.get('TMF_S7_SLOTS', slots or cap))))
+        m, S = wplan.R.shape
+        n, nnz = plan.n_items, plan.nnz
+        E = nnz + m * S
+        self.n_groups = ng = -(-m // UG)
+        slice_bytes = int(os.environ.get('TMF_S7_SLICE_BYTES', slice_bytes or SCORES7_SLICE_BYTES))
+        ns = int(min(max(1, -(-n * row_bytes(n_components, dtype) // slice_bytes)), max(1, (2 ** 31 - 1) // max(ng, 1))))
+        self.width = width = -(-n // ns)
+        self.n_slices = ns = -(-n // width)
+        nc = ns * ng
+        ar = torch.arange(E, device=dev, dtype=i64)
+        # entries in place order: e < nnz is interaction e, e >= nnz is negative e - nnz = u * S + pos
+        user = torch.cat([plan.user_of.to(i64), torch.arange(m, device=dev, dtype=i64).repeat_interleave(S)])
+        item = torch.cat([plan.col_u.to(i64), wplan.R.reshape(-1).to(i64)])
+        lu = (user % UG).to(i32)
+        chunk = (item // width) * ng + user // UG
+        del user
+        ordA = torch.sort((chunk * width + item % width) * UG + lu, stable=True)[1]   # entries by (chunk, item, local user)
+        chunkA = chunk[ordA]
+        cnt_c = torch.bincount(chunk, minlength=nc)
+        del chunk
+        chunk_sub = _excl_cumsum((cnt_c + SL - 1) // SL)
+        subA = chunk_sub[chunkA] + (ar - _excl_cumsum(cnt_c)[chunkA]) // SL           # the sub-chunk of every entry, ascending
+        del chunkA, cnt_c
+        self.n_sub = n_sub = int(chunk_sub[-1])
+        self.chunk_sub = chunk_sub.to(i32)
+        self.sub_place = sub_place = _excl_cumsum(torch.bincount(subA, minlength=n_sub))
+        # slots: a stable sort of the entries in place order by (sub-chunk, local user)
+        sub_e = torch.empty(E, dtype=i64, device=dev)
+        sub_e[ordA] = subA
+        ordB = torch.sort(sub_e * UG + lu, stable=True)[1]
+        place_e = torch.cat([-1 - torch.arange(nnz, device=dev, dtype=i32), torch.arange(m * S, device=dev, dtype=i32)])
+        self.place = place_e[ordB]
+        del place_e
+        slot_e = torch.empty(E, dtype=i32, device=dev)
+        slot_e[ordB] = (ar - sub_place[sub_e[ordB]]).to(i32)
+        del sub_e, ordB
+        slotA, itemA, luA = slot_e[ordA], item[ordA].to(i32), lu[ordA]
+        del slot_e, item, lu, ordA
+        # steps: runs of one item inside a sub-chunk, cut every K entries
+        new_run = torch.ones(E, dtype=torch.bool, device=dev)
+        if E > 1:
+            new_run[1:] = (subA[1:] != subA[:-1]) | (itemA[1:] != itemA[:-1])
+        run_start = torch.nonzero(new_run).flatten()
+        run_of = torch.cumsum(new_run, 0) - 1
+        del new_run
+        run_len = torch.diff(run_start, append=torch.tensor([E], device=dev, dtype=i64))
+        run_steps = (run_len + K - 1) // K
+        del run_len
+        run_step0 = _excl_cumsum(run_steps)
+        self.n_steps = n_steps = int(run_step0[-1])
+        sub_steps = torch.zeros(n_sub, dtype=i64, device=dev)
+        sub_steps.scatter_add_(0, subA[run_start], run_steps)
+        self.sub_step = _excl_cumsum(sub_steps)
+        del subA, sub_steps, run_steps
+        pos = ar - run_start[run_of]
+        del ar, run_start
+        stepA = run_step0[run_of] + pos // K
+        k = pos % K
+        del pos, run_of, run_step0
+        users = torch.zeros(n_steps, K, dtype=i64, device=dev)
+        slot4 = torch.full((n_steps, K), cap, dtype=i64, device=dev)
+        first = k == 0
+        users[stepA[first]] = luA[first].to(i64)[:, None]          # pads repeat the step's first user: a resident row
+        users[stepA, k] = luA.to(i64)
+        slot4[stepA, k] = slotA.to(i64)
+        steps = torch.zeros(n_steps + 1, 4, dtype=i32, device=dev)  # one record behind the last: 16-byte loads never leave the buffer
+        steps[stepA[first], 0] = itemA[first]
+        del first, stepA, k, luA, slotA, itemA
+        w = users[:, 0] | (users[:, 1] << 8) | (users[:, 2] << 16) | (users[:, 3] << 24)
+        steps[:n_steps, 1] = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(i32)
+        steps[:n_steps, 2] = (slot4[:, 0] | (slot4[:, 1] << 16)).to(i32)
+        steps[:n_steps, 3] = (slot4[:, 2] | (slot4[:, 3] << 16)).to(i32)
+        self.steps = steps
+        self.n_entries = E
+
+
 def scores5_wanted(plan, wplan, n_components, dtype=torch.float32):
     """Whether the sliced user pass computes its scores with the row-stationary kernel (tmf_wmrb_scores5: workgroups own 256
     users, keep their rows in LDS and walk one flat stream of (user, item) pairs ordered by item) instead of tmf_wmrb_scores3.
@@ -771,7 +896,18 @@ class TrainState:
             else:
                 self.part_layers, self.gradu_launches = 1, 1           # a launch per slice
             need.update(sp=m * S, pk=max(plan.nnz, 1), part=self.part_layers * max(m, 1) * self.ld)
-            if scores6_wanted(plan, wplan, self.r, dtype):
+            if scores7_wanted(plan, wplan, self.r, dtype):
+                if wplan.s7 is None or wplan.s7.key != (self.r, dtype):
+                    if os.environ.get('TMF_SCORES7') == '1':
+                        wplan.s7 = Scores7Plan(plan, wplan, self.r, dtype)
+                    else:   # the default: streams of ~10 bytes per entry that do not fit leave the pass with scores3 / scores6
+                        try:
+                            wplan.s7 = Scores7Plan(plan, wplan, self.r, dtype)
+                        except torch.OutOfMemoryError:
+                            wplan.s7 = None
+            else:
+                wplan.s7 = None
+            if wplan.s7 is None and scores6_wanted(plan, wplan, self.r, dtype):
                 if wplan.s6 is None or wplan.s6.key != (self.r, dtype):
                     wplan.s6 = Scores6Plan(plan, wplan, self.r, dtype)
             else:
@@ -1287,8 +1423,13 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
     m, S, ns = p.n_users, w.S, w.n_slices
     s = _lib.stream_ptr()
     lists = w.lists(p)
-    s5, s6 = w.s5, w.s6
-    if s6 is not None:
+    s5, s6, s7 = w.s5, w.s6, w.s7
+    if s7 is not None:
+        # item runs: one workgroup per (slice, group of 256 users) chunk, the group's rows in LDS, one load of a V row per run
+        _timed(prof, 'wmrb_scores', lambda: lib.tmf_wmrb_scores7_f32(
+            _lib.ptr(s7.steps), _lib.ptr(s7.place), _lib.ptr(s7.sub_step), _lib.ptr(s7.sub_place), _lib.ptr(s7.chunk_sub), s7.n_groups,
+            i32(s7.n_slices), m, p.n_items, _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(st.sp), _lib.ptr(st.pk), r, s))
+    elif s6 is not None:
         # flat streams on the slice-major grid: one workgroup per (slice, group of 32 users) chunk, the group's rows in LDS
         _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores6' + st.sfx)(
             _lib.ptr(s6.ids), _lib.ptr(s6.outs), _lib.ptr(s6.chunk_ptr), s6.n_groups, i32(s6.n_slices), m, p.n_items, _lib.ptr(st.U),

@@ -1481,6 +1481,219 @@ static int wmrb_scores6_impl(const int32_t* ids, const int32_t* outs, const int6
     return check_launch("tmf_wmrb_scores6");
 }
 
+// ---------------------------------------------------------------------------------------------
+// Item runs ("scores7").  At C4 the gather kernels sit at the ceiling of the CU's L1 return path (64 bytes per clock):
+// only fewer row bytes through that path move them.  A workgroup takes one (slice, group of kS7Users users) CHUNK as scores6 does
+// and keeps the group's rows in LDS - but its entries come sorted by ITEM, so all users of the group that need a row of V share
+// ONE load of it: 256 users x (1024 negatives + ~100 interactions) on a slice of ~7700 rows is ~3 entries per distinct row.
+// The stream is prepared once per fit (_engine.Scores7Plan):
+//   step   = one item and up to kS7K users of the group that need it, a 16-byte record
+//              x  item id            y  kS7K 8-bit local users            z, w  kS7K 16-bit slots
+//            short steps are padded with a valid local user and the slot kS7Slots, which is never flushed
+//   sub-chunk = steps whose scores fill at most kS7Slots slots of an LDS score buffer; place[slot] says where a slot's score goes
+//            (>= 0 -> sp[place], < 0 -> p[~place]); slots are numbered by user, then in the order of sp / p, so the flush - thread
+//            i stores slot i - writes consecutive addresses for every user (pieces of ~20-90 bytes instead of isolated floats)
+// A row is read by a group of 8 lanes, 64 bytes per lane as four 16-byte pieces 128 bytes apart; lane groups 2 and 3 of every 32
+// lanes take the pieces of a 256-byte half in the other order (`par`), which puts the four rows that one ds_read_b128 pass serves
+// (lanes {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31}: MI355X LDS table) on disjoint banks.  The sum is
+//   ((q0 + q2) + (q1 + q3)) over the lane's pieces (q = dot_raw of a 16-byte piece), then xor 1, 2, 4 over the 8 lanes:
+// the tree of the lean k_wmrb_scores3 and of scores5 / scores6 (32 lanes x 16 bytes: xor 16, 8, 1, 2, 4), so the scores are THEIRS
+// bit for bit; swapping q0 <-> q1 and q2 <-> q3 does not change it, so a score does not depend on the lane group, step or chunk.
+// Steps go round-robin to the 128 lane groups; kS7Flight rows are in flight per lane group, records are fetched 2 kS7Flight ahead.
+// No atomics, no waiting between workgroups; __syncthreads around the flush only.
+// VALU wave-instructions per round of one wave (8 steps = 32 entry slots), counted in the gfx950 disassembly of the unrolled loop:
+// 110 = 16 v_pk_mul + 16 v_pk_fma + 38 v_add_f32 (12 of them DPP) + 8 v_cndmask + 32 address / select / bookkeeping: 3.4 per
+// entry slot (the lean scores3 walk: 7.7 per row).
+// ---------------------------------------------------------------------------------------------
+namespace tmf {
+// C4 scores ms, same box, scores3 26.8 (profiles/scores7_c4.json): 256 users / 16 waves / 6144 slots / 2 rows in flight 19.1 - 20.2
+// (2.58 real entries per step); 3 rows in flight 19.4 - 20.0 (no gain: kept at 2, 102 VGPRs); 128 users / 8 waves / 3584 slots - two
+// workgroups per CU, the flush of one behind the steps of the other - 22.6 (1.85 entries per step: the shared loads lost outweigh
+// the overlap).  K = 2 and 16 / 32 lanes per row were not built.
+constexpr int kS7Users = 256;    // users per chunk: 128 KB of LDS (8-bit local user)
+constexpr int kS7Slots = 6144;   // scores per sub-chunk: 24 KB of LDS; with the rows 152 KB of the CU's 160
+constexpr int kS7K = 4;          // users per step
+constexpr int kS7Waves = 16;     // one workgroup of 1024 threads per CU: 128 lane groups of 8
+constexpr int kS7Flight = 2;     // rows of V in flight per lane group
+constexpr uint32_t kS7RowBytes = 512;
+constexpr size_t kS7Lds = (size_t)kS7Users * kS7RowBytes + (size_t)(kS7Slots + 64) * sizeof(float);
+
+struct S7Streams {
+    const int4* steps;          // [n_steps] records, sub-chunk after sub-chunk
+    const int32_t* place;       // [n_entries] places, sub-chunk after sub-chunk, slot order
+    const int64_t* sub_step;    // [n_sub + 1] first step of every sub-chunk
+    const int64_t* sub_place;   // [n_sub + 1] first place of every sub-chunk
+    const int32_t* chunk_sub;   // [n_chunks + 1] first sub-chunk of every chunk
+};
+
+__global__ __launch_bounds__(64 * kS7Waves) void k_wmrb_scores7(S7Streams a, int64_t chunk0, int64_t n_groups, int64_t n_users,
+                                                                const float* __restrict__ U, const float* __restrict__ V,
+                                                                float* __restrict__ sp, float* __restrict__ p) {
+    constexpr int NG = 8 * kS7Waves, NT = 64 * kS7Waves, FL = kS7Flight;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];   // [kS7Users] rows | [kS7Slots + 64] scores (the pad slot behind them)
+    float* sbuf = reinterpret_cast<float*>(smem_raw + (size_t)kS7Users * kS7RowBytes);
+    const int tid = threadIdx.x, lane = tid & 63, g = lane & 7, gid = tid >> 3;
+    const int64_t chunk = chunk0 + blockIdx.x;   // = slice * n_groups + group
+    const int sub_b = a.chunk_sub[chunk], sub_e = a.chunk_sub[chunk + 1];
+    if (sub_b == sub_e) return;                  // no entry of this group in this slice (whole workgroup)
+    const int64_t ubeg = (chunk % n_groups) * kS7Users;
+    const int nu = (int)((n_users - ubeg < kS7Users) ? n_users - ubeg : kS7Users);
+    {
+        const tmf_f4* src = reinterpret_cast<const tmf_f4*>(reinterpret_cast<const char*>(U) + ubeg * (int64_t)kS7RowBytes);
+        tmf_f4* dst = reinterpret_cast<tmf_f4*>(smem_raw);
+        for (int i = tid; i < nu * (int)(kS7RowBytes / 16); i += NT) dst[i] = __builtin_nontemporal_load(src + i);
+    }
+    __syncthreads();
+    const uint32_t par = (lane >> 4) & 1;
+    const uint32_t offA = 16u * g + 128u * par, offB = 16u * g + 128u * (par ^ 1u);   // pieces (0, 1) or (1, 0) of a 256-byte half
+    struct Row {
+        float4 v[4];
+    };
+    // The summation tree of the lean k_wmrb_scores3 / scores5 / scores6 (dot_raw + Reduce4x32 / Reduce8x32 on 32 lanes x 16 bytes),
+    // bit for bit: a 16-byte piece gives q = dot_raw of that piece; there lane l is first added to lane l ^ 16, then l ^ 8 - here the
+    // pieces 128 v bytes apart of ONE lane: (q0 + q2) + (q1 + q3) - then xor 1, 2, 4 across lanes as there.
+    auto dot = [](const Row& x, const Row& y) {
+        float q[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            tmf_f2 a = tmf_f2{x.v[v].x, x.v[v].y} * tmf_f2{y.v[v].x, y.v[v].y};
+            a = __builtin_elementwise_fma(tmf_f2{x.v[v].z, x.v[v].w}, tmf_f2{y.v[v].z, y.v[v].w}, a);
+            q[v] = a.x + a.y;
+        }
+        return (q[0] + q[2]) + (q[1] + q[3]);
+    };
+    for (int sub = sub_b; sub < sub_e; ++sub) {
+        const int64_t st0 = a.sub_step[sub];
+        const int nsteps = (int)(a.sub_step[sub + 1] - st0);
+        const int64_t pl0 = a.sub_place[sub];
+        const int nslots = (int)(a.sub_place[sub + 1] - pl0);   // <= kS7Slots
+        const int4* rec0 = a.steps + st0;
+        // step i of this lane group is gid + NG i; the wave runs as many rounds as its first group has steps; beyond its last step
+        // a group repeats the sub-chunk's last step into the pad slot, so every load below is unconditional
+        const int mine = nsteps > gid ? (nsteps - gid + NG - 1) / NG : 0;
+        const int rounds = __builtin_amdgcn_readfirstlane(mine);
+        // the places of the flush, asked for before the steps: they are the oldest loads in flight and cost the flush no round trip
+        const int32_t* pl = a.place + pl0;
+        int32_t where[kS7Slots / NT];
+#pragma unroll
+        for (int q = 0; q < kS7Slots / NT; ++q) where[q] = (tid + NT * q < nslots) ? __builtin_nontemporal_load(pl + tid + NT * q) : 0;
+        if (rounds > 0) {
+            auto fetch = [&](int i) {   // the record as loaded: whether round i is past the group's last step is decided where it is used
+                const int st = gid + NG * i;
+                return rec0[st < nsteps ? st : nsteps - 1];
+            };
+            auto gather = [&](Row& y, const int4& r) {
+                const char* base = reinterpret_cast<const char*>(V);
+                const uint32_t oa = row_byte_off<kS7RowBytes>((uint32_t)r.x, offA), ob = row_byte_off<kS7RowBytes>((uint32_t)r.x, offB);
+                y.v[0] = *reinterpret_cast<const float4*>(base + oa);
+                y.v[1] = *reinterpret_cast<const float4*>(base + ob);
+                y.v[2] = *reinterpret_cast<const float4*>(base + oa + 256);
+                y.v[3] = *reinterpret_cast<const float4*>(base + ob + 256);
+            };
+            auto finish = [&](const Row& y, const int4& r, int i) {
+                float s[kS7K];
+#pragma unroll
+                for (int k = 0; k < kS7K; ++k) {
+                    const uint32_t lu = ((uint32_t)r.y >> (8 * k)) & 0xffu;
+                    const char* xa = smem_raw + (lu * kS7RowBytes + offA);
+                    const char* xb = smem_raw + (lu * kS7RowBytes + offB);
+                    Row x;
+                    x.v[0] = *reinterpret_cast<const float4*>(xa);
+                    x.v[1] = *reinterpret_cast<const float4*>(xb);
+                    x.v[2] = *reinterpret_cast<const float4*>(xa + 256);
+                    x.v[3] = *reinterpret_cast<const float4*>(xb + 256);
+                    float t = dot(x, y);
+                    t += TMF_DPP_MOV(t, 0xB1);    // quad_perm [1,0,3,2]
+                    t += TMF_DPP_MOV(t, 0x4E);    // quad_perm [2,3,0,1]
+                    t += TMF_DPP_MOV(t, 0x141);   // row_half_mirror (quads are uniform by now): all 8 lanes hold the score
+                    s[k] = t;
+                }
+                // lane k < kS7K of the group stores score k at its slot (a pad's slot is the one behind the buffer: never flushed)
+                const float mine_s = (g & 2) ? ((g & 1) ? s[3] : s[2]) : ((g & 1) ? s[1] : s[0]);
+                const uint32_t w = (g & 2) ? (uint32_t)r.w : (uint32_t)r.z;
+                uint32_t slot = (g & 1) ? (w >> 16) : (w & 0xffffu);
+                slot = (slot < (uint32_t)kS7Slots && gid + NG * i < nsteps) ? slot : (uint32_t)kS7Slots;
+                if (g < kS7K) sbuf[slot] = mine_s;
+            };
+            // Loads return in order (vmcnt): the record of round i + 2 FL is asked for BEHIND the rows of round i + FL, so waiting for
+            // the rows of a round never waits for anything issued after them
+            // (a ring of 2 FL records, the loop unrolled as far: a record is never copied, which would wait for its load).
+            Row y[FL];
+            int4 rec[2 * FL];
+            // The body is branch-free - with a branch per round the compiler's wait counts fall back to vmcnt(0) - and the last
+            // rounds (fewer than 2 FL) run in a tail of their own.
+#pragma unroll
+            for (int j = 0; j < FL; ++j) rec[j] = fetch(j);
+#pragma unroll
+            for (int j = 0; j < FL; ++j) {
+                gather(y[j], rec[j]);
+                rec[FL + j] = fetch(FL + j);
+            }
+            int i = 0;
+            for (; i + 2 * FL <= rounds; i += 2 * FL) {
+#pragma unroll
+                for (int j = 0; j < 2 * FL; ++j) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    finish(y[j % FL], rec[j], i + j);
+                    __builtin_amdgcn_sched_barrier(0);
+                    gather(y[j % FL], rec[(j + FL) % (2 * FL)]);   // round i + j + FL (past the end: the last step again, never used)
+                    rec[j] = fetch(i + j + 2 * FL);
+                }
+            }
+            const int rem = rounds - i;
+#pragma unroll
+            for (int j = 0; j < 2 * FL - 1; ++j) {
+                if (j < rem) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    finish(y[j % FL], rec[j], i + j);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (j + FL < rem) gather(y[j % FL], rec[j + FL]);
+                }
+            }
+        }
+        __syncthreads();
+        // flush: thread i stores slot i where place[] says; consecutive slots of a user are consecutive addresses
+#pragma unroll
+        for (int q = 0; q < kS7Slots / NT; ++q)
+            if (tid + NT * q < nslots)
+                __builtin_nontemporal_store(sbuf[tid + NT * q], where[q] >= 0 ? sp + where[q] : p + ~where[q]);
+        __syncthreads();
+    }
+}
+
+}  // namespace tmf
+
+static bool s7_supported(int n_components, int bf16, int64_t n_items) {
+    return !bf16 && n_components >= 65 && n_components <= 128 && s6_supported(n_components, 0, n_items);
+}
+
+static int wmrb_scores7_impl(const void* steps, const int32_t* place, const int64_t* sub_step, const int64_t* sub_place,
+                             const int32_t* chunk_sub, int64_t n_groups, int32_t n_slices, int64_t n_users, int64_t n_items,
+                             const void* U, const void* V, float* sp, float* p, int n_components, void* stream) {
+    if (n_users == 0 || n_slices == 0) return TMF_OK;
+    TMF_REQUIRE(steps && place && sub_step && sub_place && chunk_sub && U && V && sp && p, "wmrb_scores7: null pointer");
+    TMF_REQUIRE(n_groups == (n_users + kS7Users - 1) / kS7Users && n_slices > 0, "wmrb_scores7: %lld groups for %lld users (%d per group), %d slices",
+                (long long)n_groups, (long long)n_users, kS7Users, n_slices);
+    if (!s7_supported(n_components, 0, n_items)) {
+        set_error("wmrb_scores7: needs fp32 rows of 65..128 components and fewer than 2^24 items in a table below 4 GB "
+                  "(got %d components, %lld items)", n_components, (long long)n_items);
+        return TMF_E_UNSUPPORTED;
+    }
+    static LdsGrant grant;
+    if (int rc = grant_dynamic_lds(reinterpret_cast<const void*>(&k_wmrb_scores7), kS7Lds, grant)) return rc;
+    const S7Streams a{static_cast<const int4*>(steps), place, sub_step, sub_place, chunk_sub};
+    // whole slices per launch, fewer than 2^32 work-items each
+    const int64_t per_slice = n_groups * 64 * kS7Waves;
+    const int max_slices = (int)((((int64_t)1 << 32) - 1) / per_slice);
+    TMF_REQUIRE(max_slices >= 1, "wmrb_scores7: %lld user groups exceed one launch", (long long)n_groups);
+    for (int s0 = 0; s0 < n_slices; s0 += max_slices) {
+        const int nsl = (n_slices - s0 < max_slices) ? n_slices - s0 : max_slices;
+        hipLaunchKernelGGL(k_wmrb_scores7, dim3((unsigned)(n_groups * nsl)), dim3(64 * kS7Waves), kS7Lds, (hipStream_t)stream, a,
+                           (int64_t)s0 * n_groups, n_groups, n_users, (const float*)U, (const float*)V, sp, p);
+    }
+    return check_launch("tmf_wmrb_scores7");
+}
+
 static int s5_launches(int64_t n_wg, int wgs_per_launch) { return (int)((n_wg + wgs_per_launch - 1) / wgs_per_launch); }
 static int s5_wgs_per_launch(int wgs_per_launch) {
     if (wgs_per_launch > 0) return wgs_per_launch;
@@ -1598,6 +1811,15 @@ TMF_SLICED_ENTRY_POINTS(bf16, __bf16)
 
 extern "C" int tmf_wmrb_scores6_users_per_group(void) { return tmf::kS6Users; }
 extern "C" int tmf_wmrb_scores6_supported(int n_components, int bf16, int64_t n_items) { return s6_supported(n_components, bf16, n_items); }
+extern "C" int tmf_wmrb_scores7_f32(const void* steps, const int32_t* place, const int64_t* sub_step, const int64_t* sub_place,
+                                    const int32_t* chunk_sub, int64_t n_groups, int32_t n_slices, int64_t n_users, int64_t n_items,
+                                    const void* U, const void* V, float* sp, float* p, int n_components, void* stream) {
+    return wmrb_scores7_impl(steps, place, sub_step, sub_place, chunk_sub, n_groups, n_slices, n_users, n_items, U, V, sp, p,
+                             n_components, stream);
+}
+extern "C" int tmf_wmrb_scores7_users_per_group(void) { return tmf::kS7Users; }
+extern "C" int tmf_wmrb_scores7_slots(void) { return tmf::kS7Slots; }
+extern "C" int tmf_wmrb_scores7_supported(int n_components, int bf16, int64_t n_items) { return s7_supported(n_components, bf16, n_items); }
 extern "C" int tmf_wmrb_scores5_users_per_workgroup(void) { return tmf::kS5Users; }
 extern "C" size_t tmf_wmrb_scores5_workspace_bytes(int64_t n_wg, int32_t n_windows, int wgs_per_launch) {
     if (n_wg <= 0 || n_windows <= 1) return 0;
