@@ -667,6 +667,27 @@ int tmf_rank_count_rows_f32(float* X, int64_t rows, int64_t cols, int64_t ldx, i
 int tmf_dcg_idcg_f32(const int64_t* rowptr, const int32_t* cols, const float* gain, int64_t m, int64_t n_items, const int32_t* top,
                      int64_t ldt, int k, const float* den, const int64_t* n_zero, float* dcg, float* idcg, void* stream);
 
+/* EXTENSION (the reference ranks user-item scores only): unit rows for cosine similarity inside one side (similar_items /
+ * similar_users rank them with the fused top-k).  Gather and normalisation in one launch, every source row read once:
+ *   out[j, :r] = T[row_j, :r] / ||T[row_j, :r]||_2 as fp32,  norms[j] = that Euclidean norm (norms may be NULL),
+ *   row_j = ids[j], or j when ids == NULL (then q <= n_rows).  ids may repeat and come in any order; the caller has checked
+ *   them against [0, n_rows) - the library cannot (they are device memory).
+ * T: fp32 (_f32) or bf16 (_bf16) rows of 16 bytes alignment - T 16-byte aligned, ldt %% 4 == 0 (bf16: ldt %% 8 == 0), ldt >= r;
+ * only columns [0, r) of the rows asked for are read, so padding columns, skipped rows and other rows may hold anything.
+ * out: fp32 [q, ldo], 16-byte aligned, ldo >= r, ldo %% 4 == 0; columns [0, ldo) of rows [0, q) are written, zeros in [r, ldo),
+ * and nothing else is.  r in [1, 1024].
+ * Arithmetic, right for every FINITE row whatever its scale: the row is multiplied by the power of two that brings its largest
+ * magnitude into [1, 2) (exact), the squares are summed in fp32 in a fixed order (no atomics), square root and division are
+ * correctly rounded, and the norm is scaled back by the same power of two (exact unless it leaves the fp32 range).  A row of
+ * zeros gives a row of zeros and norm 0.  A row with a non-finite element is outside the contract (its outputs are unspecified).
+ * The unit row depends on the row's contents and r alone: bit-identical wherever the row stands and whichever j asks for it.
+ * q == 0: TMF_OK without a launch.  r, ldt, ldo, q, n_rows out of range, a null or misaligned table: TMF_E_INVALID before any
+ * launch. */
+int tmf_unit_rows_f32(const float* T, int64_t n_rows, int r, int64_t ldt, const int32_t* ids, int64_t q, float* out,
+                      int64_t ldo, float* norms, void* stream);
+int tmf_unit_rows_bf16(const void* T, int64_t n_rows, int r, int64_t ldt, const int32_t* ids, int64_t q, float* out,
+                       int64_t ldo, float* norms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

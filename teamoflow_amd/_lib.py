@@ -164,6 +164,8 @@ _BASE_SIGNATURES = {
     'tmf_item_ranks_split': (_I, [_P, _P, _L, _I, _L, _L, _RR, _P, _P, _EX, _P, _P, _SZ, _P]),
     'tmf_rank_count_rows_f32': (_I, [_P, _L, _L, _L, _L, _RR, _P, _EX, _P, _P]),
     'tmf_dcg_idcg_f32': (_I, [_P, _P, _P, _L, _L, _P, _L, _I, _P, _P, _P, _P, _P]),
+    'tmf_unit_rows_f32': (_I, [_P, _L, _I, _L, _P, _L, _P, _L, _P, _P]),
+    'tmf_unit_rows_bf16': (_I, [_P, _L, _I, _L, _P, _L, _P, _L, _P, _P]),
 }
 
 SIGNATURES.update(_BASE_SIGNATURES)

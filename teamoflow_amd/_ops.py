@@ -378,6 +378,115 @@ def gather_rows_cols(x, idx):
     return out
 
 
+# ---- nearest neighbours inside one side (tmf_unit_rows_* + the fused top-k: implicit's similar_items / similar_users) ----
+SIMILAR_BLOCK_BYTES = 2 << 30   # score block of the non-fused path (k > 64 or r > 256): MatrixFactorization._user_blocks' budget
+
+
+def _row_ids(ids, n_rows, what='row'):
+    """ids (an int sequence, array or tensor; any order, repeats allowed) as a flat int32 tensor where it is, every id checked
+    against [0, n_rows): IndexError - no library needed."""
+    ids = torch.as_tensor(ids).reshape(-1)
+    if ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
+        raise TypeError(f'{what} ids must be integers, got {ids.dtype}')
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n_rows):
+        raise IndexError(f'{what} id out of range [0, {n_rows})')
+    return ids.to(torch.int32).contiguous()
+
+
+def _table_2d(t, what):
+    t = t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t))
+    if t.dim() != 2:
+        raise ValueError(f'{what} must be 2-D [rows, r], got shape {tuple(t.shape)}')
+    return t
+
+
+def unit_rows(table, ids=None, return_norms=False):
+    """Unit rows of table [n, r] (fp32 or bf16, any layout) in one launch of tmf_unit_rows_*: row j of the result is
+    table[ids[j]] / ||table[ids[j]]|| (ids=None: every row in order), always fp32 - the [q, r] view of a [q, padded_ld(r)] buffer
+    whose other columns are zero.  Right for every finite row whatever its scale; a zero row stays zero (norm 0); the same row
+    content gives the same bits wherever it stands.  ids out of range raise IndexError.  return_norms: also the Euclidean norms
+    (float32 [q])."""
+    table = _table_2d(table, 'table')
+    n, r = table.shape
+    if ids is not None:
+        ids = _row_ids(ids, n)
+    lib = _lib.get()
+    bf16 = table.dtype == torch.bfloat16
+    T, n, r, ldt = _operand(table, 8 if bf16 else 4)
+    ids = None if ids is None else ids.to(T.device)
+    q = n if ids is None else ids.numel()
+    ldo = _lib.padded_ld(r)
+    out = torch.empty(q, ldo, dtype=torch.float32, device=T.device)
+    norms = torch.empty(q, dtype=torch.float32, device=T.device) if return_norms else None
+    run = lib.tmf_unit_rows_bf16 if bf16 else lib.tmf_unit_rows_f32
+    _lib.check(run(_lib.ptr(T), n, r, ldt, _lib.ptr(ids), q, _lib.ptr(out), ldo, _lib.ptr(norms), _lib.stream_ptr()), lib)
+    return (out[:, :r], norms) if return_norms else out[:, :r]
+
+
+def similar_rows(table, k, *, ids=None, queries=None, metric='cosine', include_self=False, arithmetic=None, block_bytes=None):
+    """The k rows of table [n, r] nearest to each query row -> (ids int32 [q, k], values float32 [q, k]), value descending, ties by
+    ascending id.  The query rows are table[ids] (ids=None: every row), or ``queries`` [q, r] (embeddings of rows the table does
+    not hold).  metric 'cosine' ranks unit_rows of both sides (a zero row has cosine 0 with everything), 'dot' the raw rows.
+    Unless include_self is set or queries are given, query j never returns ids[j] (the exclusion CSR with one entry per row), so
+    k <= n - 1 then and k <= n otherwise: ValueError beyond; ids out of range: IndexError.  All checks run before the library is
+    touched.
+    One fused predict_topk call where fused_topk_supported holds (arithmetic as there; a form whose kernel does not take this
+    (r, k) - 'split' beyond k = 40, 'half2' beyond 32 - is answered by the fp32 MFMA kernel); otherwise blocks of at most
+    block_bytes of scores (tmf_predict_gemm_f32 + tmf_topk_stable_*): no [q, n] matrix is ever whole in memory."""
+    if metric not in ('cosine', 'dot'):
+        raise ValueError(f"metric={metric!r}: expected 'cosine' or 'dot'")
+    if ids is not None and queries is not None:
+        raise ValueError('give ids (rows of the table) or queries (embeddings), not both')
+    table = _table_2d(table, 'table')
+    n, r = table.shape
+    if queries is not None:
+        queries = _table_2d(queries, 'queries')
+        if queries.shape[1] != r:
+            raise ValueError(f'queries are {queries.shape[1]} wide, the table {r}')
+    if ids is not None:
+        ids = _row_ids(ids, n)
+    drop_self = queries is None and not include_self
+    k, limit = int(k), n - 1 if drop_self else n
+    if not 1 <= k <= limit:
+        raise ValueError(f'k={k} must be in [1, {limit}]' + (f': {n} rows, and a row never returns itself' if drop_self else ''))
+    arithmetic = arithmetic or PREDICT_ARITHMETIC
+    if arithmetic not in ('auto', 'fp32', 'split', 'half2'):
+        raise ValueError(f"arithmetic={arithmetic!r}: expected 'auto', 'fp32', 'split' or 'half2'")
+    T = _cuda(table).detach()
+    dev = T.device
+    ids = None if ids is None else ids.to(dev)
+    q = queries.shape[0] if queries is not None else n if ids is None else ids.numel()
+    if q == 0:
+        return torch.empty(0, k, dtype=torch.int32, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
+    if metric == 'cosine':
+        B = unit_rows(T)
+        A = unit_rows(queries) if queries is not None else B if ids is None else unit_rows(T, ids)
+    else:
+        B = T
+        A = _cuda(queries).detach() if queries is not None else T if ids is None else T[ids.long()]
+    ex = None
+    if drop_self:   # row j leaves out ids[j]: one sorted entry per row, nothing to sort
+        cols = torch.arange(n, dtype=torch.int32, device=dev) if ids is None else ids
+        ex = Exclusion(torch.arange(q + 1, dtype=torch.int64, device=dev), cols, q, n)
+    if fused_topk_supported(A, B, k):
+        both_bf16 = A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16
+        if not both_bf16 and ((arithmetic == 'split' and not split_topk_supported(r, k))
+                              or (arithmetic == 'half2' and not half2_topk_supported(r, k))):
+            arithmetic = 'fp32'
+        vals, idx = predict_topk(A, B, k, return_values=True, arithmetic=arithmetic, exclude=ex)
+        return idx, vals
+    Bf = B if B.dtype == torch.float32 else B.float()
+    budget = SIMILAR_BLOCK_BYTES if block_bytes is None else int(block_bytes)
+    step = max(1, min(q, budget // (4 * n)))
+    out_i, out_v = [], []
+    for b in range(0, q, step):
+        scores = predict_gemm(A[b:b + step], Bf)
+        v_, i_ = topk_stable(scores, k, return_values=True, exclude=None if ex is None else ex.shifted(b), overwrite=True)
+        out_v.append(v_)
+        out_i.append(i_)
+    return (torch.cat(out_i), torch.cat(out_v)) if len(out_i) > 1 else (out_i[0], out_v[0])
+
+
 # ---- full-catalog ranks of held-out pairs (tmf_item_ranks_*: LightFM's predict_rank / auc_score / reciprocal_rank) ----
 RANK_ROW_PAIRS = 16          # include/tmf.h TMF_RANK_ROW_PAIRS: positives per virtual row of the rank kernels
 RANK_BLOCK_BYTES = 1 << 30   # score block of the non-fused path (tmf_predict_gemm_f32 + tmf_rank_count_rows_f32)

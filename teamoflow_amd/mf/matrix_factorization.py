@@ -784,6 +784,35 @@ class MatrixFactorization:
         kk = num_items if k is None else k
         return self._top_items(kk, clamp=False, users=user, exclude=exclude).cpu().numpy()
 
+    def _similar(self, side, rows, k, metric, include_self, queries):
+        name = ('user', 'item')[side]
+        if self._item_sharded():
+            raise NotImplementedError(f'item-row-sharded fit: this rank holds only its item rows; similar_{name}s needs the whole '
+                                      f'table (dist.gather_item_embedding assembles it where it fits)')
+        table = (self.user_embedding, self.item_embedding)[side]
+        single = isinstance(rows, (int, np.integer)) and not isinstance(rows, bool)
+        idx, vals = _ops.similar_rows(table, k, ids=[rows] if single else rows, queries=queries, metric=metric,
+                                      include_self=include_self, arithmetic=getattr(self, 'predict_arithmetic', None),
+                                      block_bytes=PREDICT_CHUNK_BYTES)
+        idx, vals = idx.cpu().numpy(), vals.cpu().numpy()
+        return (idx[0], vals[0]) if single else (idx, vals)
+
+    def similar_items(self, items=None, k=10, *, metric='cosine', include_self=False, queries=None):
+        """Extension (implicit's similar_items): the k items nearest to each query item by their trained embeddings, without an
+        [n, n] matrix -> (ids int32, similarities float32) as NumPy arrays, similarity descending, ties by ascending id.
+        items: None = every item, an int = one item (1-D results, as retrieve_user_recs(user=...)), or a sequence / array / tensor
+        of ids, in any order and with repeats ([q, k] results).  An item never returns itself unless include_self is set.
+        queries: [q, r] embeddings instead of ids - for instance embed_items(SparseFeatures(...)) of items the fit has not seen;
+        nothing is excluded then.  metric: 'cosine' (unit rows from tmf_unit_rows_*: right for rows of any scale, a zero row has
+        similarity 0 with everything) or 'dot'.  Ranked under predict_arithmetic; fp32 and bf16 stored tables.
+        k outside [1, n - 1] ([1, n] when nothing is excluded), a bad metric, ids together with queries or queries of another
+        width raise ValueError, an id out of range IndexError - all before the engine is touched."""
+        return self._similar(1, items, k, metric, include_self, queries)
+
+    def similar_users(self, users=None, k=10, *, metric='cosine', include_self=False, queries=None):
+        """Extension (implicit's similar_users): similar_items over user_embedding."""
+        return self._similar(0, users, k, metric, include_self, queries)
+
     # ------------------------------------------------------------------------------------------
     # persistence
     # ------------------------------------------------------------------------------------------
