@@ -688,6 +688,39 @@ int tmf_unit_rows_f32(const float* T, int64_t n_rows, int r, int64_t ldt, const 
 int tmf_unit_rows_bf16(const void* T, int64_t n_rows, int r, int64_t ldt, const int32_t* ids, int64_t q, float* out,
                        int64_t ldo, float* norms, void* stream);
 
+/* EXTENSION (the reference trains by gradient steps only): alternating least squares - implicit feedback after Hu, Koren and
+ * Volinsky, and plain least squares over the stored entries.  Two entry points; fit_als / fold_in_users / fold_in_items are built on
+ * them.  TMF_VERSION stays 203, as for the other entry points added since: nothing that existed changes.
+ *
+ * G = T^T T, [r, r] fp32 (G[i * ldg + j]), r in [1, 128].  Blocks of rows give partial sums, which are added in block order: no
+ * atomics, so reruns are bit-identical, and G is exactly symmetric.  Only columns [0, r) of T are read.  T 16-byte aligned,
+ * ldt >= r, ldt %% 4 == 0, ldg >= r; `workspace` holds the partials (tmf_gram_workspace_bytes; overwritten per call).  n_rows == 0
+ * gives zeros.  Anything out of range: TMF_E_INVALID before any launch. */
+size_t tmf_gram_workspace_bytes(int64_t n_rows, int r);
+int tmf_gram_f32(const float* T, int64_t n_rows, int r, int64_t ldt, float* G, int64_t ldg, void* workspace, size_t workspace_bytes,
+                 void* stream);
+
+/* One ALS half-step for q rows of a CSR (rowptr int64, col int32: ids of rows of Y; w, t: per-entry weight and target).  Row
+ * `row` = ids[p], or p when ids == NULL, p < q, gets the solution of
+ *     A x = b,   A = G0 + reg I + sum_k w[k] y_k y_k^T,   b = sum_k t[k] y_k,   y_k = Y[col[k], :r],  k in [rowptr[row], rowptr[row+1])
+ * written to X[row * ldx ...]: columns [0, r) the solution, columns [r, ldx) exactly zero, and nothing else is written - with ids,
+ * X is the whole table and rows not named keep their contents (a row named twice is written twice with the same bits).  G0: [r, r]
+ * with pitch ldg (its lower triangle is read), or NULL for none.  A row without entries gets x = 0.  Duplicate columns add up.
+ * Only columns [0, r) of the gathered rows of Y are read: padding columns and rows no entry names may hold anything.
+ * Arithmetic: fp32 throughout; every sum over entries runs in entry order (the normal matrix on the fp32 MFMA, an fmaf chain) and
+ * every step of the Cholesky factorisation A = L L^T and of the two triangular solves in a fixed order inside the one workgroup
+ * that owns the row, so a row's x depends on its entries, Y, G0 and reg alone: bit-identical whichever launch, position in ids or
+ * rerun computes it.  With reg > 0 and w >= 0, A is positive definite.  A pivot that is not a positive finite number fails the row:
+ * its x is zeros and *n_failed (int32, device memory, zeroed by the caller) is incremented by an atomic add; no other row is affected.
+ * r in [1, 128]; reg finite and > 0; Y and X 16-byte aligned, ldy >= r, ldy %% 4 == 0, ldx >= r, ldg >= r with G0: otherwise
+ * TMF_E_INVALID before any launch.  q == 0: TMF_OK without a launch.  ids, col and rowptr are the caller's to check (device memory).
+ * All row and entry offsets are 64-bit.
+ * KNOWN LIMIT: one workgroup walks a row's entries serially, so a row with millions of entries serialises its workgroup; splitting
+ * such rows into partial normal matrices is a follow-up, as is a conjugate-gradient form for r > 128. */
+int tmf_als_solve_rows_f32(const float* Y, int64_t n_other, int r, int64_t ldy, const float* G0, int64_t ldg, const int64_t* rowptr,
+                           const int32_t* col, const float* w, const float* t, float reg, const int32_t* ids, int64_t q, float* X,
+                           int64_t ldx, int32_t* n_failed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

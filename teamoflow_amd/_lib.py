@@ -166,6 +166,9 @@ _BASE_SIGNATURES = {
     'tmf_dcg_idcg_f32': (_I, [_P, _P, _P, _L, _L, _P, _L, _I, _P, _P, _P, _P, _P]),
     'tmf_unit_rows_f32': (_I, [_P, _L, _I, _L, _P, _L, _P, _L, _P, _P]),
     'tmf_unit_rows_bf16': (_I, [_P, _L, _I, _L, _P, _L, _P, _L, _P, _P]),
+    'tmf_gram_workspace_bytes': (_SZ, [_L, _I]),
+    'tmf_gram_f32': (_I, [_P, _L, _I, _L, _P, _L, _P, _SZ, _P]),
+    'tmf_als_solve_rows_f32': (_I, [_P, _L, _I, _L, _P, _L, _P, _P, _P, _P, _F, _P, _L, _P, _L, _P, _P]),
 }
 
 SIGNATURES.update(_BASE_SIGNATURES)

@@ -775,3 +775,95 @@ def reciprocal_rank_from_ranks(rowptr, ranks, n_items):
     best = torch.full((m,), int(n_items), dtype=torch.int64, device=rowptr.device)
     best = best.scatter_reduce(0, _csr_rows(rowptr), ranks.to(device=rowptr.device, dtype=torch.int64), reduce='amin')
     return (1.0 / (1.0 + best.to(torch.float64))).to(torch.float32), counts
+
+
+# ---- alternating least squares (tmf_gram_f32 + tmf_als_solve_rows_f32: implicit's ALS and recalculate_user) ----
+ALS_MAX_COMPONENTS = 128   # include/tmf.h: the per-row factorisation holds the packed triangle of an r x r matrix in LDS
+
+
+def _als_reg(reg):
+    reg = float(reg)
+    if not 0.0 < reg <= float(np.finfo(np.float32).max):   # NaN fails both comparisons
+        raise ValueError(f'reg={reg!r}: the ALS regulariser must be finite and > 0')
+    return reg
+
+
+def gram(table):
+    """table^T table of a [n, r] fp32 table (any layout), r <= 128 -> [r, r] float32.  Fixed summation order: exactly symmetric, and
+    bit-identical from run to run (tmf_gram_f32)."""
+    table = _table_2d(table, 'table')
+    if not 1 <= table.shape[1] <= ALS_MAX_COMPONENTS:
+        raise ValueError(f'gram: width {table.shape[1]} outside [1, {ALS_MAX_COMPONENTS}]')
+    lib = _lib.get()
+    T, n, r, ldt = _operand(table)
+    G = torch.empty(r, r, dtype=torch.float32, device=T.device)
+    ws = torch.empty(lib.tmf_gram_workspace_bytes(n, r), dtype=torch.uint8, device=T.device)
+    _lib.check(lib.tmf_gram_f32(_lib.ptr(T), n, r, ldt, _lib.ptr(G), r, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), lib)
+    return G
+
+
+def als_solve_rows(Y, rowptr, col, w, t, reg, G0=None, ids=None, out=None, n_failed=None, check=True):
+    """One ALS half-step (tmf_als_solve_rows_f32): for the rows of the CSR (rowptr int64 [n_rows + 1], col: row ids of Y, w / t the
+    per-entry weights and targets) the solutions of (G0 + reg I + sum w y y^T) x = sum t y -> (X, n_failed).  X is the [n_rows, r]
+    view of a [n_rows, padded_ld(r)] table: ``out`` (such a view, written in place) or a fresh one of zeros.  ids: only these rows
+    are solved (any order, repeats allowed) and the others keep what X held.  n_failed: int32 [1] on the device, counting the rows
+    whose matrix was not positive definite (their x is zeros); pass the previous call's to keep counting.  check=False skips the id
+    and CSR checks (a caller that has made them once)."""
+    reg = _als_reg(reg)
+    Y = _table_2d(Y, 'Y')
+    n_other, r = Y.shape
+    if not 1 <= r <= ALS_MAX_COMPONENTS:
+        raise ValueError(f'als_solve_rows: width {r} outside [1, {ALS_MAX_COMPONENTS}]')
+    rowptr = torch.as_tensor(rowptr).reshape(-1)
+    n_rows = rowptr.numel() - 1
+    if n_rows < 0:
+        raise ValueError('rowptr must hold at least one offset')
+    col, w, t = (torch.as_tensor(x).reshape(-1) for x in (col, w, t))
+    if not (col.numel() == w.numel() == t.numel()):
+        raise ValueError(f'col, w and t disagree on the number of entries: {col.numel()}, {w.numel()}, {t.numel()}')
+    if check:
+        col = _row_ids(col, n_other, 'column')
+        if int(rowptr[0]) != 0 or int(rowptr[-1]) != col.numel() or (n_rows and bool((rowptr[1:] < rowptr[:-1]).any())):
+            raise ValueError('rowptr is not a CSR row pointer over the entries given')
+    if ids is not None:
+        ids = _row_ids(ids, n_rows) if check else torch.as_tensor(ids).reshape(-1)
+    lib = _lib.get()
+    Yt, _, _, ldy = _operand(Y)
+    dev = Yt.device
+    rowptr = _cuda(rowptr, torch.int64).contiguous()
+    col, w, t = _cuda(col, torch.int32).contiguous(), _cuda(w, torch.float32).contiguous(), _cuda(t, torch.float32).contiguous()
+    ids = None if ids is None else _cuda(ids, torch.int32).contiguous()
+    if col.numel() == 0:   # no stored entry at all: every row is empty and gets zeros; the library wants valid pointers all the same
+        col, w, t = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, device=dev), torch.zeros(1, device=dev)
+    g0, ldg = None, 0
+    if G0 is not None:
+        g0 = _cuda(_table_2d(G0, 'G0'), torch.float32).contiguous()
+        if tuple(g0.shape) != (r, r):
+            raise ValueError(f'G0 must be [{r}, {r}], got {tuple(g0.shape)}')
+        ldg = r
+    if out is None:
+        out = torch.zeros(n_rows, _lib.padded_ld(r), dtype=torch.float32, device=dev)[:, :r]
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n_rows, r)
+              and (n_rows == 0 or (out.stride(1) == 1 and out.stride(0) >= r)) and out.data_ptr() % 16 == 0):
+        raise ValueError(f'out must be a CUDA float32 [{n_rows}, {r}] view with unit column stride, a row stride >= {r} and a 16-byte '
+                         f'aligned base')
+    if n_failed is None:
+        n_failed = torch.zeros(1, dtype=torch.int32, device=dev)
+    q = n_rows if ids is None else ids.numel()
+    ldx = max(out.stride(0), r)   # a view of at most one row may state any stride
+    _lib.check(lib.tmf_als_solve_rows_f32(_lib.ptr(Yt), n_other, r, ldy, _lib.ptr(g0), ldg, _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(w),
+                                          _lib.ptr(t), reg, _lib.ptr(ids), q, _lib.ptr(out), ldx, _lib.ptr(n_failed),
+                                          _lib.stream_ptr()), lib)
+    return out, n_failed
+
+
+def pair_scores(A, B, pair_a, pair_b):
+    """out[p] = <A[pair_a[p]], B[pair_b[p]]> as float32 (tmf_pair_scores_f32; ids int32 on the device, checked by the caller)."""
+    lib = _lib.get()
+    At, _, r, lda = _operand(A)
+    Bt, _, _, ldb = _operand(B)
+    out = torch.empty(pair_a.numel(), dtype=torch.float32, device=At.device)
+    if pair_a.numel():
+        _lib.check(lib.tmf_pair_scores_f32(_lib.ptr(At), _lib.ptr(Bt), r, lda, ldb, _lib.ptr(pair_a), _lib.ptr(pair_b), pair_a.numel(),
+                                           _lib.ptr(out), _lib.stream_ptr()), lib)
+    return out

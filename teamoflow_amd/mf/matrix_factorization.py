@@ -16,6 +16,8 @@ own ``get_repr`` / ``get_loss`` - and so does KL without a GPU, with ``batch_use
 storage or with ``optimizer='adam'`` - the settings under which a side over ``SparseFeatures`` is handed over as a dense matrix too.
 ``user_alpha`` / ``item_alpha`` > 0 (extensions, off by default) add ``alpha ||W_side||_F^2`` to the objective on either path: on the engine
 through the ``_l2`` twins of the table steps (``_engine.TrainState.set_l2``), in the generic loop as a term of the differentiated sum.
+``fit_als`` (an extension) trains the same tables by alternating least squares instead of gradient steps, and ``fold_in_users`` /
+``fold_in_items`` embed rows that arrived after a fit from their interactions (``teamoflow_amd/_als.py``, ``csrc/tmf_als.hip``).
 """
 import os
 import timeit
@@ -24,7 +26,7 @@ import warnings
 import numpy as np
 import torch
 
-from .. import _engine, _lib, _ops
+from .. import _als, _engine, _lib, _ops
 from .embedding_graphs import BiasedLinearEmbedding, Embeddings, LinearEmbedding, ReLUEmbedding
 from .initializer_graphs import NormalInitializer
 from .loss_graphs import BPRLoss, KLDivergenceLoss, LogisticLoss, LossGraph, MSELoss, WMRBLoss
@@ -201,6 +203,16 @@ class MatrixFactorization:
                 raise NotImplementedError(f'user_alpha / item_alpha > 0 with {name}={getattr(self, name)!r}: L2 regularisation is built for '
                                           f'the single-GPU full-batch fit and the generic loop only (set {name} back to its default)')
 
+    def _reset_fit_products(self, sparse_feature_sides):
+        """What one fit keeps for the calls after it and the next fit must not inherit (fit and fit_als share it): the sharded epoch
+        of the last fit and the per-side records embed_users / embed_items read.  The variables the reference carries from fit to
+        fit (user_linear_bias, user_relu_weight, ... - a later biased or ReLU fit starts from them) stay, and so does ``_state``,
+        whose presence says that some fit of this model ran on the engine (fit_als, which has no engine state, drops it)."""
+        self._sharded_epoch = None
+        self._sparse_feature_sides = tuple(sparse_feature_sides)
+        self._feature_weights = [None, None]   # padded engine weights of a side trained over SparseFeatures (embed_users / embed_items)
+        self._relu_sides = [None, None]        # the _engine.ReLUSide of a ReLU side trained on the engine (embed_users / embed_items)
+
     def fit(self, epochs, user_features, item_features, tf_interactions, lr=1e-2):
         """matrix_factorization.py:96-187.  Re-initialises the weights on every call, runs ``epochs``
         full-batch steps (loss -> gradient of the SUM of the per-interaction losses -> a fresh Adam
@@ -220,9 +232,7 @@ class MatrixFactorization:
             V = self.item_weight_graph.initialize_weights(self.item_aux_dim, self.n_components)
         interactions = _as_interactions(tf_interactions)
         kl = type(self.loss_graph) is KLDivergenceLoss
-        self._sparse_feature_sides = (isinstance(user_features, SparseFeatures), isinstance(item_features, SparseFeatures))
-        self._feature_weights = [None, None]   # padded engine weights of a side trained over SparseFeatures (embed_users / embed_items)
-        self._relu_sides = [None, None]        # the _engine.ReLUSide of a ReLU side trained on the engine (embed_users / embed_items)
+        self._reset_fit_products((isinstance(user_features, SparseFeatures), isinstance(item_features, SparseFeatures)))
         if (self._on_fast_path(user_features, item_features) and (not kl or self._kl_engine_allowed())
                 and self._logistic_engine_allowed() and self._bpr_engine_allowed()):
             feats = [f if sparse else None for f, sparse in zip((user_features, item_features), self._sparse_feature_sides)]
@@ -232,6 +242,81 @@ class MatrixFactorization:
         user_features, item_features = (f.to_dense(W.device) if isinstance(f, SparseFeatures) else f
                                         for f, W in ((user_features, U), (item_features, V)))
         self._fit_generic(epochs, user_features, item_features, interactions, lr, U, V)
+
+    # ------------------------------------------------------------------------------------------
+    # alternating least squares (extension: teamoflow_amd/_als.py)
+    # ------------------------------------------------------------------------------------------
+    def _refuse_unbuilt_als_forms(self, what):
+        """ALS solves fp32 tables of at most 128 components, full-batch on one GPU (or in torch without one): every other setting is
+        refused, never run as something else."""
+        if self.n_components > _als.MAX_COMPONENTS:
+            raise NotImplementedError(f'{what}: n_components={self.n_components} > {_als.MAX_COMPONENTS} - the per-row factorisation '
+                                      f'holds an r x r matrix in LDS (a conjugate-gradient form for wider models is not built)')
+        if self.factor_dtype is torch.bfloat16 and what == 'fit_als':
+            raise NotImplementedError('fit_als: factor_dtype=torch.bfloat16 - the normal equations are solved on float32 tables only')
+        if what != 'fit_als':
+            return
+        for name in ('batch_users', 'shard_items', 'data_parallel', 'user_alpha', 'item_alpha'):
+            if getattr(self, name, 0):
+                raise NotImplementedError(f'fit_als with {name}={getattr(self, name)!r}: only the single-GPU full-batch fit is built, '
+                                          f'and its regulariser is reg (set {name} back to its default)')
+
+    def fit_als(self, epochs, user_features, item_features, tf_interactions, *, reg=0.01, alpha=1.0, implicit=True):
+        """Extension (implicit's AlternatingLeastSquares; Hu, Koren and Volinsky): ``epochs`` sweeps of alternating least squares
+        instead of gradient steps - no learning rate, and converged after 10 - 20 sweeps.  Leading arguments as ``fit``.
+        implicit=True: confidence 1 + alpha |a| on every stored value a, preference 1 where a > 0 and 0 everywhere else (all
+        unstored pairs included; a stored 0 changes nothing, a stored negative value is a confident zero).  implicit=False: least
+        squares over the stored entries only, targets a.  reg (finite, > 0) is the ridge on both tables; alpha is finite and >= 0.
+        Each sweep solves every user's r x r normal equations against the item table, then every item's against the user table
+        (tmf_gram_f32 + tmf_als_solve_rows_f32 on a GPU, torch.linalg.cholesky_ex in chunks of rows without one), and appends the
+        objective both half-steps minimise to loss_history_ (teamoflow_amd/_als.py states it).
+        Both sides must be exactly LinearEmbedding over indicator features (NotImplementedError otherwise), n_components <= 128,
+        float32 tables, one GPU, full batch; ``loss_graph``, ``lr`` and ``optimizer`` are not used.  The weights are drawn from
+        user_weight_graph / item_weight_graph in the order ``fit`` draws them; only the item draw matters, because the first
+        half-step solves the users.  Leaves what ``fit`` leaves: user_embedding / item_embedding / *_trainable, so predict, the
+        rankings, the metrics, similar_items / similar_users and save / load work as after ``fit``.  A row solve that meets a
+        matrix that is not positive definite raises FloatingPointError after the last sweep.  Returns None."""
+        reg, alpha = _als.check_hyper(reg, alpha)
+        self._refuse_unbuilt_als_forms('fit_als')
+        if not (type(self.user_repr_graph) is LinearEmbedding and type(self.item_repr_graph) is LinearEmbedding
+                and is_indicator(user_features) and is_indicator(item_features)):
+            raise NotImplementedError('fit_als: both sides must be LinearEmbedding over indicator features (eye(n)); ALS on biased, '
+                                      'ReLU or SparseFeatures sides is not built')
+        n_users, n_user_features = user_features.shape
+        n_items, n_item_features = item_features.shape
+        U0 = self.user_weight_graph.initialize_weights(n_user_features, self.n_components)
+        V0 = self.item_weight_graph.initialize_weights(n_item_features, self.n_components)
+        interactions = _as_interactions(tf_interactions)
+        if tuple(interactions.shape) != (n_users, n_items):
+            raise ValueError(f'interactions of shape {tuple(interactions.shape)} for {n_users} users and {n_items} items')
+        U, V = _als.fit(self, int(epochs), n_users, n_items, interactions, U0, V0, reg, alpha, bool(implicit))
+        self._reset_fit_products((False, False))
+        self.__dict__.pop('_state', None)   # an earlier engine fit's TrainState: its tables are not this model's any more
+        self.user_embedding, self.item_embedding = U, V
+        self.user_trainable, self.item_trainable = [U], [V]
+
+    def _fold_in(self, side, interactions, reg, alpha, implicit):
+        name = ('users', 'items')[side]
+        reg, alpha = _als.check_hyper(reg, alpha)
+        self._refuse_unbuilt_als_forms(f'fold_in_{name}')
+        if self._item_sharded():
+            raise NotImplementedError(f'item-row-sharded fit: this rank holds only its item rows; fold_in_{name} needs the whole table')
+        table = getattr(self, ('item_embedding', 'user_embedding')[side], None)
+        if table is None:
+            raise ValueError(f'fold_in_{name}: the model has no fitted tables yet')
+        return _als.fold_in(table, _as_interactions(interactions), reg, alpha, bool(implicit))
+
+    def fold_in_users(self, interactions, *, reg=0.01, alpha=1.0, implicit=True):
+        """Extension (implicit's recalculate_user): the exact embeddings of users the fit has not seen, from their interactions with
+        the fitted items.  interactions: SparseInteractions [n_new, n_items] whose ROWS are the new users.  -> float32 [n_new, r]:
+        one ALS half-step (as fit_als, same reg / alpha / implicit meaning) against item_embedding, which a ``fit`` or a ``fit_als``
+        may have trained (a bfloat16 table is upcast first).  The model is not modified.  The rows feed
+        similar_users(queries=...) and _ops.predict_topk directly.  n_components > 128: NotImplementedError."""
+        return self._fold_in(0, interactions, reg, alpha, implicit)
+
+    def fold_in_items(self, interactions, *, reg=0.01, alpha=1.0, implicit=True):
+        """fold_in_users for new items: interactions [n_new, n_users], rows = the new items, solved against user_embedding."""
+        return self._fold_in(1, interactions, reg, alpha, implicit)
 
     def _report(self, epoch, loss, seconds):
         if self.verbose and (epoch + 1) % 25 == 0:
