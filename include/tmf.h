@@ -357,6 +357,23 @@ int tmf_wmrb_hinge2_ordered(const int64_t* rowptr, const float* val, const float
  * Finite for every finite score; +inf in sp gives loss inf and sigmoid 1; a NaN stays inside its user. */
 int tmf_bpr_pairs(const int64_t* rowptr, const float* val, const float* p, const float* sp, int32_t n_users, int32_t n_samples,
                   float* delta, float* D, float* loss_part, const int32_t* user_order, void* stream);
+/* WARPLoss (an extension) in the same place, same layout of every argument, + the catalog size: for the stored values > 0 of user u,
+ * t_k = fl(p[k] - 1):  s* = the first s with sp[u, s] > t_k (strict, in table order; a NaN never violates),  N = s* + 1,
+ * w = log(max(1, floor((n_items - 1) / N))) - 0 without a violator or with N > n_items - 1;  delta[k] = -w (0 for a stored value
+ * <= 0),  D[u, s*] += w,  loss_part[u] = sum_k w (1 - p[k] + sp[u, s*]); the epoch's loss is the sum of loss_part over the number
+ * of positives.  Every element of delta [nnz], D [n_users, n_samples] and loss_part [n_users] is overwritten, whatever the
+ * buffers held.  Reads no table; O(S + P log S) per user (a prefix maximum of the row and a binary search per positive), rows of
+ * any length >= 1.  n_users = 0 is legal, and so are NULL val / p / delta for a table without interactions.  No atomics; the
+ * outputs are bit-identical from run to run and do not depend on user_order (speed only: heavy users first). */
+int tmf_warp_pairs(const int64_t* rowptr, const float* val, const float* p, const float* sp, int32_t n_users, int32_t n_samples,
+                   int32_t n_items, float* delta, float* D, float* loss_part, const int32_t* user_order, void* stream);
+/* The same with sp and D in another order than the table's (the sliced pass keeps every user's samples sorted by item, and this
+ * loss depends on their order): rank[u, pos] in [0, n_samples) is the table index of the sample at place pos of user u's row - a
+ * permutation of every row, 16 bits each (n_samples <= 65536).  Trials run in table order; D[u, pos] is the weight of the sample
+ * at place pos.  The bits of tmf_warp_pairs on the rows in table order, moved to their places. */
+int tmf_warp_pairs_ranked(const int64_t* rowptr, const float* val, const float* p, const float* sp, const uint16_t* rank,
+                          int32_t n_users, int32_t n_samples, int32_t n_items, float* delta, float* D, float* loss_part,
+                          const int32_t* user_order, void* stream);
 int tmf_wmrb_gradu3_f32(const tmf_slice_lists* lists, const float* D, const float* delta, const void* V, float* part,
                         int per_slice_launches, int n_components, void* stream);
 int tmf_wmrb_gradu3_bf16(const tmf_slice_lists* lists, const float* D, const float* delta, const void* V, float* part,

@@ -8,6 +8,7 @@ What replaces what (reference paths under /root/reference/src/teamoflow/mf/):
   epoch_kl    <- matrix_factorization.py:130-176 with KLDivergenceLoss (loss_graphs.py:91-122)
   epoch_logistic: LogisticLoss (mf/loss_graphs.py; an extension - the reference has no such loss)
   epoch_wmrb(pairs='bpr'): BPRLoss (mf/loss_graphs.py; an extension): the WMRB epoch with tmf_bpr_pairs in the hinge kernel's place
+  epoch_wmrb(pairs='warp'): WARPLoss (mf/loss_graphs.py; an extension): the same epoch with tmf_warp_pairs there
   epoch_relu  <- the same loop with a ReLUEmbedding side (embedding_graphs.py:61-87)
 """
 import ctypes
@@ -494,6 +495,25 @@ class WmrbPlan:
                                self.pos_off.data_ptr(), m, S, self.n_slices, slice_begin, slice_count, item_base,
                                _lib.SLICE_N_ITEMS_STATED, int(plan.n_items))
 
+    def sample_rank(self):
+        """rank[u, pos] = the place in the model's random_ind row of the negative at place pos of the plan's row (16 bits, stored as
+        int16; the identity where the plan keeps the model's order).  WARPLoss tries a user's samples in table order: the one
+        consumer.  Built on first use, in blocks of users, and kept with the plan.  Samples of the same item may swap their
+        places: they have the same score and their weights meet in the same row of V."""
+        if getattr(self, '_rank', None) is None:
+            m, S = self.R_model.shape
+            if S > 65536:
+                raise ValueError(f'n_samples={S}: the sample ranks of a WARPLoss fit are 16 bits (n_samples <= 65536)')
+            rank = torch.empty(m, S, dtype=torch.int16, device=self.R_model.device)
+            for b in range(0, m, 1 << 16):
+                rows = self.R_model[b:b + (1 << 16)]
+                if self.sliced:
+                    rank[b:b + (1 << 16)] = torch.sort(rows, dim=1, stable=True)[1].to(torch.int16)   # wraps: the kernel reads unsigned
+                else:
+                    rank[b:b + (1 << 16)] = torch.arange(S, device=rows.device).to(torch.int16)[None, :]
+            self._rank = rank
+        return self._rank
+
     def D_in_model_order(self):
         """D[u, s] indexed like the model's random_ind (the sliced pass keeps every user's negatives sorted by item)."""
         if not self.sliced:
@@ -520,7 +540,7 @@ def wmrb_plan_for(plan, R, n_components, dtype=torch.float32, n_items=None, forc
     """The WmrbPlan a fit builds for (plan, R): the user-pass form (choose_wmrb_user_pass), the item-pass form (rows4_wanted) and the
     user blocks that go with it - ONE place for MatrixFactorization._fit_sparse, dist.fit_data_parallel and bench.py.
     n_items: the catalog size for the slice geometry when the plan's table is padded (multi-GPU: rows padded to the world size).
-    force_sliced: the sliced user pass whatever the shape (BPRLoss: the one-kernel pass has the hinge built in); the slice count
+    force_sliced: the sliced user pass whatever the shape (BPRLoss, WARPLoss: the one-kernel pass has the hinge built in); the slice count
     stays the one the shape gets."""
     m = plan.n_users
     n = plan.n_items if n_items is None else n_items
@@ -1311,34 +1331,34 @@ def _timed(prof, name, call):
 LOGISTIC_LOSSES = ('logistic', 'logistic_w')   # LogisticLoss(weighted=False) / LogisticLoss(weighted=True)
 
 
-PAIR_LOSSES = ('wmrb', 'bpr')   # the losses over the static negative table: WmrbPlan, sp / p / delta / D, denominator n_pos
+PAIR_LOSSES = ('wmrb', 'bpr', 'warp')   # the losses over the static negative table: WmrbPlan, sp / p / delta / D, denominator n_pos
 
 
 def loss_name(loss_graph):
-    """The name run_epoch knows the loss of a fit by: 'mse', 'wmrb', 'kl', 'bpr', 'logistic' or 'logistic_w' for exactly the five
-    built-in loss classes (not their subclasses: what a subclass computes is its own business, and the generic path's).  Anything
+    """The name run_epoch knows the loss of a fit by: 'mse', 'wmrb', 'kl', 'bpr', 'warp', 'logistic' or 'logistic_w' for exactly the
+    six built-in loss classes (not their subclasses: what a subclass computes is its own business, and the generic path's).  Anything
     else raises - no loss trains as another one because a chain of isinstance tests fell through."""
     from .mf import loss_graphs as L
     kind = type(loss_graph)
     if kind is L.LogisticLoss:
         return 'logistic_w' if loss_graph.weighted else 'logistic'
-    names = {L.MSELoss: 'mse', L.WMRBLoss: 'wmrb', L.KLDivergenceLoss: 'kl', L.BPRLoss: 'bpr'}
+    names = {L.MSELoss: 'mse', L.WMRBLoss: 'wmrb', L.KLDivergenceLoss: 'kl', L.BPRLoss: 'bpr', L.WARPLoss: 'warp'}
     if kind not in names:
         raise TypeError(f'{kind.__name__} is not a loss the HIP engine trains (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, '
-                        f'BPRLoss)')
+                        f'BPRLoss, WARPLoss)')
     return names[kind]
 
 
 def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM,
               user_out=None):
-    """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'bpr', 'kl', 'logistic', 'logistic_w' or 'mse' - on the state's
-    tables: the ONE place that maps a loss to its epoch.  The other arguments as in epoch_mse.
-    'bpr' is an epoch only of a state whose WmrbPlan is sliced (wmrb_plan_for(force_sliced=True)): the one-kernel user pass has the
+    """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'bpr', 'warp', 'kl', 'logistic', 'logistic_w' or 'mse' - on the
+    state's tables: the ONE place that maps a loss to its epoch.  The other arguments as in epoch_mse.
+    'bpr' and 'warp' are epochs only of a state whose WmrbPlan is sliced (wmrb_plan_for(force_sliced=True)): the one-kernel user pass has the
     hinge built in.  On any other state it is refused like a name nobody knows - never run as WMRB."""
     if loss == 'wmrb':
         epoch_wmrb(st, adam, c, loss_out, item_epi, item_out, prof, user_epi, user_out)
-    elif loss == 'bpr' and getattr(getattr(st, 'wplan', None), 'sliced', False):
-        epoch_wmrb(st, adam, 0.0, loss_out, item_epi, item_out, prof, user_epi, user_out, pairs='bpr')
+    elif loss in ('bpr', 'warp') and getattr(getattr(st, 'wplan', None), 'sliced', False):
+        epoch_wmrb(st, adam, 0.0, loss_out, item_epi, item_out, prof, user_epi, user_out, pairs=loss)
     elif loss == 'kl':
         epoch_kl(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
     elif loss in LOGISTIC_LOSSES:
@@ -1346,7 +1366,7 @@ def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=
     elif loss == 'mse':
         epoch_mse(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
     else:
-        raise ValueError(f'run_epoch: unknown loss {loss!r}' + (' on a state without a sliced WmrbPlan' if loss == 'bpr' else ''))
+        raise ValueError(f'run_epoch: unknown loss {loss!r}' + (' on a state without a sliced WmrbPlan' if loss in ('bpr', 'warp') else ''))
 
 
 def _row_pass_finish(lib, seg, slab, X_old, X_out, r, epi, adam, stream, sfx='_f32'):
@@ -1417,7 +1437,10 @@ def epoch_kl(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=Non
 
 def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, U_out=None, pairs='hinge'):
     """Sliced user pass: scores -> hinge -> gradU (+ weights into entry order) -> finish (csrc/tmf_wmrb.hip, tmf_hinge.hip).
-    pairs='bpr': tmf_bpr_pairs (csrc/tmf_bpr.hip) in the hinge kernel's place - same arguments but c, same layout of delta and D."""
+    pairs='bpr': tmf_bpr_pairs (csrc/tmf_bpr.hip) in the hinge kernel's place - same arguments but c, same layout of delta and D.
+    pairs='warp': tmf_warp_pairs_ranked (csrc/tmf_warp.hip) there - those arguments, the plan's n_items (the weight's rank
+    estimate) and WmrbPlan.sample_rank(): the one loss here that depends on the order of a user's samples tries them in the model's
+    table order, whatever order the plan keeps them in."""
     p, w, r = st.plan, st.wplan, st.r
     i32 = ctypes.c_int32
     m, S, ns = p.n_users, w.S, w.n_slices
@@ -1447,6 +1470,13 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
         _timed(prof, 'bpr_pairs', lambda: lib.tmf_bpr_pairs(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk), _lib.ptr(st.sp),
                                                             i32(m), i32(S), _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part),
                                                             _lib.ptr(w.hinge_order), s))
+    elif pairs == 'warp':
+        # sp and D are in the plan's order (every user's negatives sorted by item); the trials run in the model's table order
+        rank = w.sample_rank()
+        _timed(prof, 'warp_pairs', lambda: lib.tmf_warp_pairs_ranked(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk),
+                                                                     _lib.ptr(st.sp), _lib.ptr(rank), i32(m), i32(S), i32(p.n_items),
+                                                                     _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part),
+                                                                     _lib.ptr(w.hinge_order), s))
     else:
         _timed(prof, 'wmrb_hinge', lambda: lib.tmf_wmrb_hinge2_ordered(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk), _lib.ptr(st.sp),
                                                                 i32(m), i32(S), c, _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part),
@@ -1469,13 +1499,15 @@ def epoch_wmrb(st, adam, c, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, pro
                pairs='hinge'):
     """One WMRB epoch.  loss_out receives sum over positives of log(1 + M_k).  item_epi / user_epi as in epoch_mse.
     pairs='bpr': one BPRLoss epoch - the same scores, gathers and item pass around tmf_bpr_pairs (c is unused); loss_out receives
-    sum over positives of mean_s softplus(sp[u, s] - p_k).  Only on a sliced plan."""
+    sum over positives of mean_s softplus(sp[u, s] - p_k).  Only on a sliced plan.
+    pairs='warp': one WARPLoss epoch in the same way around tmf_warp_pairs; loss_out receives sum over positives of
+    w_k (1 - p_k + sp[u, s*_k]).  Only on a sliced plan."""
+    if pairs not in ('hinge', 'bpr', 'warp'):
+        raise ValueError(f'epoch_wmrb: pairs={pairs!r} (hinge, bpr or warp)')
+    if pairs != 'hinge' and not st.wplan.sliced:
+        raise ValueError(f'epoch_wmrb: pairs={pairs} needs the sliced user pass (wmrb_plan_for(force_sliced=True))')
     lib, p, w, r = _lib.get(), st.plan, st.wplan, st.r
     s = _lib.stream_ptr()
-    if pairs not in ('hinge', 'bpr'):
-        raise ValueError(f'epoch_wmrb: pairs={pairs!r} (hinge or bpr)')
-    if pairs == 'bpr' and not w.sliced:
-        raise ValueError('epoch_wmrb: pairs=bpr needs the sliced user pass (wmrb_plan_for(force_sliced=True))')
     if w.sliced:
         _timed(prof, 'wmrb_user_pass', lambda: _wmrb_user_pass_sliced(lib, st, adam, c, prof, user_epi, user_out, pairs))
     else:

@@ -1,7 +1,7 @@
 """Loss graphs (plug-in interface of /root/reference/src/teamoflow/mf/loss_graphs.py).
 
-``MSELoss``, ``WMRBLoss``, ``KLDivergenceLoss``, ``LogisticLoss`` and ``BPRLoss`` (extensions: the reference has no logistic loss,
-pointwise or pairwise) with ``LinearEmbedding`` over indicator features are recognised by
+``MSELoss``, ``WMRBLoss``, ``KLDivergenceLoss``, ``LogisticLoss``, ``BPRLoss`` and ``WARPLoss`` (extensions: the reference has no
+logistic loss, pointwise or pairwise, and no first-violator ranking loss) with ``LinearEmbedding`` over indicator features are recognised by
 ``MatrixFactorization.fit`` (same isinstance dispatch as matrix_factorization.py:152-162) and run as
 fused HIP kernels; ``get_loss`` below is the generic differentiable definition used when the model is
 built from other plug-ins (dense features, custom embeddings), always called by keyword like
@@ -101,3 +101,32 @@ class BPRLoss(LossGraph):
         users = tf_interactions.indices[:, 0][mask]
         pos = tf_prediction_serial[mask]
         return -torch.nn.functional.logsigmoid(pos[:, None] - tf_sample_predictions[users]).mean(dim=1)
+
+
+class WARPLoss(LossGraph):
+    """Extension (weighted approximate-rank pairwise loss, LightFM's 'warp'; not in the reference): the first-violator ranking loss
+    over the static negative table WMRBLoss samples from.  For every stored interaction k of user u with a value > 0 and score p_k,
+    the user's row sp[u, :] of sampled scores is tried in table order against the threshold t_k = p_k - 1 (rounded once in the dtype
+    of the scores): sample s violates when sp[u, s] > t_k - strictly, and a NaN on either side never does.  With s* the first
+    violator and N = s* + 1 the number of trials,
+
+        w_k = log(max(1, floor((n_items - 1) / N)))        loss_k = w_k (1 - p_k + sp[u, s*])
+
+    and loss_k = 0 where nothing violates or N > n_items - 1.  The weight is LightFM's rank estimate; it is a constant of the step
+    (computed under no_grad), so d loss_k / d p_k = -w_k and d loss_k / d sp[u, s*] = w_k.  n_samples is the cap on trials
+    (LightFM's max_sampled).  Stored values <= 0 take no part and a negative that coincides with one of the user's positives is
+    not filtered (both as in WMRBLoss)."""
+
+    def get_loss(self, tf_interactions, tf_sample_predictions, tf_prediction_serial, n_items, n_samples, predictions=None):
+        mask = tf_interactions.values > 0.0
+        users = tf_interactions.indices[:, 0][mask]
+        pos = tf_prediction_serial[mask]
+        sp = tf_sample_predictions[users]
+        with torch.no_grad():
+            violates = sp > (pos - 1.0)[:, None]
+            found = violates.any(dim=1)
+            first = violates.to(torch.uint8).argmax(dim=1)          # the first maximum: the first violator (0 where there is none)
+            rank = torch.div(int(n_items) - 1, first + 1, rounding_mode='floor').clamp(min=1)
+            w = torch.where(found, torch.log(rank.to(pos.dtype)), torch.zeros_like(pos))
+        margin = 1.0 - pos + sp.gather(1, first[:, None])[:, 0]
+        return torch.where(w > 0.0, w * margin, torch.zeros_like(pos))

@@ -3,11 +3,11 @@
 
 Dispatch (same isinstance test the reference uses at :115,:136-162): a model made of
 (``LinearEmbedding`` | ``BiasedLinearEmbedding``) x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss`` |
-``LogisticLoss`` | ``BPRLoss``)
+``LogisticLoss`` | ``BPRLoss`` | ``WARPLoss``)
 - or ``LinearEmbedding`` over ``SparseFeatures`` on either side -
 trains on the HIP engine (``_engine.py`` -> libtmf.so); for unbiased MSE / WMRB it needs a GPU - there is no CPU fallback for them.
-``LogisticLoss`` and ``BPRLoss`` (extensions) take the engine whenever there is a GPU and the generic path without one; ``BPRLoss``
-trains full-batch on one GPU only and refuses ``batch_users`` / ``shard_items`` / ``data_parallel`` with ``NotImplementedError``.
+``LogisticLoss``, ``BPRLoss`` and ``WARPLoss`` (extensions) take the engine whenever there is a GPU and the generic path without one;
+``BPRLoss`` and ``WARPLoss`` train full-batch on one GPU only and refuse ``batch_users`` / ``shard_items`` / ``data_parallel`` with ``NotImplementedError``.
 With ``relu_engine = True`` (off by default) a ``ReLUEmbedding`` side over indicator features or ``SparseFeatures`` trains there too.
 Any other combination of plug-ins (dense features, ReLU embeddings, user subclasses) trains
 through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins'
@@ -29,7 +29,7 @@ import torch
 from .. import _als, _engine, _lib, _ops
 from .embedding_graphs import BiasedLinearEmbedding, Embeddings, LinearEmbedding, ReLUEmbedding
 from .initializer_graphs import NormalInitializer
-from .loss_graphs import BPRLoss, KLDivergenceLoss, LogisticLoss, LossGraph, MSELoss, WMRBLoss
+from .loss_graphs import BPRLoss, KLDivergenceLoss, LogisticLoss, LossGraph, MSELoss, WARPLoss, WMRBLoss
 from .sparse import IndicatorFeatures, SparseFeatures, SparseInteractions, default_device, is_indicator
 from .utils import gather_matrix_indices, random_sampler, random_sampler_device
 
@@ -40,7 +40,7 @@ GRAPH_MAX_WORK = 20_000_000    # interactions + sampled scores per epoch below w
 
 
 class SampleTableMissing(AttributeError):
-    """WMRB and BPR need the static negative table: build the model with generate_sample=True
+    """WMRB, BPR and WARP need the static negative table: build the model with generate_sample=True
     (the reference fails with AttributeError inside gather_matrix_indices, matrix_factorization.py:153)."""
 
 
@@ -132,7 +132,7 @@ class MatrixFactorization:
         relu = getattr(self, 'relu_engine', False) and 5 * self.n_components <= 1024
         linear = (LinearEmbedding, ReLUEmbedding) if relu else (LinearEmbedding,)
         # a side is an engine side as Linear / BiasedLinear over indicator features, or as Linear over SparseFeatures with entries
-        if not (type(self.loss_graph) in (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, BPRLoss)
+        if not (type(self.loss_graph) in (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, BPRLoss, WARPLoss)
                 and all((kind in linear and f.nnz > 0) if sparse else
                         (kind in linear + (BiasedLinearEmbedding,) and is_indicator(f))
                         for (kind, f), sparse in zip(sides, featured))):
@@ -165,18 +165,20 @@ class MatrixFactorization:
         return type(self.loss_graph) is not LogisticLoss or torch.cuda.is_available()
 
     def _bpr_engine_allowed(self):
-        """BPRLoss (an extension, with a generic form) takes the engine whenever there is a GPU and the generic path without one."""
-        return type(self.loss_graph) is not BPRLoss or torch.cuda.is_available()
+        """BPRLoss and WARPLoss (extensions, with a generic form) take the engine whenever there is a GPU and the generic path
+        without one."""
+        return type(self.loss_graph) not in (BPRLoss, WARPLoss) or torch.cuda.is_available()
 
     def _refuse_unbuilt_bpr_forms(self):
-        """BPRLoss trains full-batch on one GPU (or through the generic loop): the mini-batch, item-sharded and data-parallel fits have
-        call sites of their own for the pair step, which do not exist - such a fit is refused, never run as another loss or densely."""
-        if type(self.loss_graph) is not BPRLoss:
+        """BPRLoss and WARPLoss train full-batch on one GPU (or through the generic loop): the mini-batch, item-sharded and
+        data-parallel fits have call sites of their own for the pair step, which do not exist - such a fit is refused, never run as
+        another loss or densely."""
+        if type(self.loss_graph) not in (BPRLoss, WARPLoss):
             return
         for name in ('batch_users', 'shard_items', 'data_parallel'):
             if getattr(self, name, 0):
-                raise NotImplementedError(f'BPRLoss with {name}={getattr(self, name)!r}: only the single-GPU full-batch fit is built for '
-                                          f'this loss (set {name} back to its default)')
+                raise NotImplementedError(f'{type(self.loss_graph).__name__} with {name}={getattr(self, name)!r}: only the single-GPU '
+                                          f'full-batch fit is built for this loss (set {name} back to its default)')
 
     def _alphas(self):
         """(user_alpha, item_alpha) as floats, checked: negative or non-finite raises ValueError."""
@@ -365,8 +367,8 @@ class MatrixFactorization:
         return True
 
     def _sparse_state(self, loss, n_users, n_items, interactions, U0, V0, dev, user_feat=None, item_feat=None):
-        """(TrainState, c) of a single-GPU full-batch fit: the interaction plan, for WMRB and BPR the checked negative table and its
-        plan (BPR: always the sliced user pass), for WMRB c = n_items / n_samples, and the starting bias of a BiasedLinearEmbedding
+        """(TrainState, c) of a single-GPU full-batch fit: the interaction plan, for WMRB, BPR and WARP the checked negative table and its
+        plan (BPR, WARP: always the sliced user pass), for WMRB c = n_items / n_samples, and the starting bias of a BiasedLinearEmbedding
         side.  (None, 0.0) for KL with an empty class."""
         wmrb, kl = loss in _engine.PAIR_LOSSES, loss == 'kl'
         plan = _engine.InteractionPlan(interactions.indices, interactions.values, n_users, n_items,
@@ -382,7 +384,9 @@ class MatrixFactorization:
                 raise IndexError('random_ind holds item ids outside [0, n_items)')
             if loss == 'wmrb':
                 c = self.n_items / self.n_samples  # constructor ints, true division (:167)
-            wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype, force_sliced=loss == 'bpr')
+            wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype, force_sliced=loss != 'wmrb')
+            if loss == 'warp':
+                wplan.sample_rank()   # WARP tries the samples in the table's order: built here, before any epoch is captured
         r = self.n_components
         # a biased side starts from the bias an earlier fit left on the model, as in the reference (:139-146), else from zeros
         bias0 = [None if type(graph) is not BiasedLinearEmbedding else torch.zeros(r) if kept is None else kept
@@ -538,7 +542,7 @@ class MatrixFactorization:
             self._keep_aux_variables()
             predictions = user_embedding @ item_embedding.T
             tf_sample_predictions = tf_prediction_serial = None
-            if isinstance(self.loss_graph, (WMRBLoss, BPRLoss)):
+            if isinstance(self.loss_graph, (WMRBLoss, BPRLoss, WARPLoss)):
                 if random_ind is None:
                     raise SampleTableMissing(f'{type(self.loss_graph).__name__} needs generate_sample=True (random_ind is None)')
                 tf_sample_predictions = torch.gather(predictions, 1, random_ind.to(torch.int64))
