@@ -9,7 +9,8 @@ What replaces what (reference paths under /root/reference/src/teamoflow/mf/):
   epoch_logistic: LogisticLoss (mf/loss_graphs.py; an extension - the reference has no such loss)
   epoch_wmrb(pairs='bpr'): BPRLoss (mf/loss_graphs.py; an extension): the WMRB epoch with tmf_bpr_pairs in the hinge kernel's place
   epoch_wmrb(pairs='warp'): WARPLoss (mf/loss_graphs.py; an extension): the same epoch with tmf_warp_pairs there
-  epoch_relu  <- the same loop with a ReLUEmbedding side (embedding_graphs.py:61-87)
+  epoch_sides <- the same loop with plug-in sides: any loss above, then the step of every side that is an object (TrainState.sides:
+                 PlainL2Side, BiasSide, FeatureSide, ReLUSide <- embedding_graphs.py:30-87)
 """
 import ctypes
 import os
@@ -890,7 +891,10 @@ class TrainState:
             self.V, self.V_nxt = V_tables
         self.bias_v = None if item_bias is None else BiasSide(self.V, item_bias, self.r)
         self.plan, self.wplan = plan, wplan
-        self.l2, self.l2_G = [0.0, 0.0], [None, None]   # set_l2: l2 = 2 alpha of (user, item) side; the gradient table of a penalised plain side
+        # (user, item): the side object that steps the table after the passes - None = a plain unpenalised side, stepped by the passes'
+        # own fused fresh-Adam epilogue into the second buffer (set_l2 puts a PlainL2Side there) - and l2 = 2 alpha of the side
+        self.sides = [self.relu_u or self.feat_u or self.bias_u, self.relu_v or self.feat_v or self.bias_v]
+        self.l2 = [0.0, 0.0]
         need = dict(slab=max(plan.seg_u.n_slab, plan.seg_i.n_slab if plan.seg_i else 0,
                              wplan.seg_e.n_slab if wplan is not None and wplan.seg_e is not None else 0,
                              wplan.vrows.n_slab if wplan is not None and wplan.vrows is not None else 0,
@@ -980,27 +984,25 @@ class TrainState:
     def set_l2(self, user_alpha=0.0, item_alpha=0.0):
         """L2 regularisation alpha ||W||_F^2 of either side's weight matrix (0 = none: nothing changes for that side).  A penalised
         side steps from g' = g + l2 w, l2 = 2 alpha in fp32, by the _l2 twin of its table step; for that it emits its raw gradient
-        (TMF_EPI_GRAD) where it ran the fused fresh-Adam epilogue.  A plain side gets a gradient table in its second buffer's place
-        and steps in place (no swap); a side over sparse features likewise for its weights; a biased side has its table already."""
-        sides = ((user_alpha, self.feat_u, self.bias_u, self.U, 'U_nxt'), (item_alpha, self.feat_v, self.bias_v, self.V, 'V_nxt'))
-        for k, (alpha, feat, bias, W, nxt) in enumerate(sides):
+        (TMF_EPI_GRAD) where it ran the fused fresh-Adam epilogue.  A plain side becomes a PlainL2Side: a gradient table in its second
+        buffer's place and a step in place (no swap); what a structured side changes is its own set_l2."""
+        for k, alpha in enumerate((user_alpha, item_alpha)):
             l2 = ctypes.c_float(2.0 * float(alpha)).value
             if not (0.0 <= l2 < float('inf')):
                 raise ValueError(f'alpha={alpha!r} of the {("user", "item")[k]} side is negative or not finite')
             if l2 == 0.0:
                 continue
-            if self.relu_u is not None or self.relu_v is not None:   # epoch_relu knows no penalised side
-                raise NotImplementedError('L2 regularisation next to a ReLU side on the engine is not built')
-            self.l2[k] = l2
-            if feat is not None:
-                feat.l2, feat.GW, feat.W_nxt = l2, torch.empty_like(feat.W), None
-            elif bias is not None:
-                bias.l2 = l2
-            else:
+            for side in self.sides:   # a ReLU side refuses it for the side opposite too
+                if isinstance(side, ReLUSide):
+                    side.set_l2(l2)
+            if self.sides[k] is None:
+                nxt = ('U_nxt', 'V_nxt')[k]
                 if getattr(self, nxt) is None:
                     raise NotImplementedError('L2 regularisation of a table that several states step is not built')
                 setattr(self, nxt, None)   # stepped in place from now on: the gradient table takes the second buffer's place
-                self.l2_G[k] = torch.empty(W.shape[0], self.ld, dtype=torch.float32, device=W.device)
+                self.sides[k] = PlainL2Side((self.U, self.V)[k], self.r, self.sfx)
+            self.sides[k].set_l2(l2)
+            self.l2[k] = l2
 
     def swap(self):
         if self.U_nxt is not None:
@@ -1032,61 +1034,39 @@ class BiasSide:
         self.part_rows = int(lib.tmf_bias_colsum_part_rows(rows))
         self.part = torch.empty(self.part_rows, ld, dtype=torch.float64, device=E.device)
 
+    def set_l2(self, l2):
+        self.l2 = l2
 
-def bias_update(side, E, adam, prof=None, tag=''):
-    """The step of one biased side from its gradient table side.G (filled by this epoch's pass): column sums -> bias step -> row
-    update, which also rebuilds E = W + b in place.  Stream-ordered, nothing allocated, no host scalars: graph-capturable.
-    tag: prefix of the three span names under ``prof`` (KernelTimer)."""
-    lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
-    rows = E.shape[0]
-    _timed(prof, tag + 'bias_colsum', lambda: lib.tmf_bias_colsum_f32(P(side.G), rows, side.r, P(side.part), side.part_rows, None, s))
-    _timed(prof, tag + 'bias_adam', lambda: lib.tmf_bias_adam_f32(P(side.part), side.part_rows, P(side.b), P(side.g_b), side.r, adam, s))
-    if side.l2:   # the weights are penalised, the bias never: its step above saw the raw gradient
-        _timed(prof, tag + 'adam_bias_rows_l2', lambda: lib.tmf_adam_bias_rows_l2_f32(P(side.W), P(side.G), P(side.b), P(E), rows, side.r,
-                                                                                      adam, side.l2, s))
-        return
-    _timed(prof, tag + 'adam_bias_rows', lambda: lib.tmf_adam_bias_rows_f32(P(side.W), P(side.G), P(side.b), P(E), rows, side.r, adam, s))
-
-
-def _plain_epi(st, k):
-    """(epilogue, output table) of the pass of a PLAIN side k (0 = user, 1 = item): the fused fresh-Adam step into the second buffer,
-    or, penalised (TrainState.set_l2), the raw gradient into the side's gradient table."""
-    return (_lib.EPI_GRAD, st.l2_G[k]) if st.l2_G[k] is not None else (_lib.EPI_ADAM, None)
+    def step(self, E, slab, adam, prof=None, tag=''):
+        """From the gradient table G (filled by this epoch's pass): column sums -> bias step -> row update, which also rebuilds
+        E = W + b in place.  Stream-ordered, nothing allocated, no host scalars: graph-capturable."""
+        lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
+        rows = E.shape[0]
+        _timed(prof, tag + 'bias_colsum', lambda: lib.tmf_bias_colsum_f32(P(self.G), rows, self.r, P(self.part), self.part_rows, None, s))
+        _timed(prof, tag + 'bias_adam', lambda: lib.tmf_bias_adam_f32(P(self.part), self.part_rows, P(self.b), P(self.g_b), self.r, adam, s))
+        if self.l2:   # the weights are penalised, the bias never: its step above saw the raw gradient
+            _timed(prof, tag + 'adam_bias_rows_l2', lambda: lib.tmf_adam_bias_rows_l2_f32(P(self.W), P(self.G), P(self.b), P(E), rows,
+                                                                                          self.r, adam, self.l2, s))
+            return
+        _timed(prof, tag + 'adam_bias_rows', lambda: lib.tmf_adam_bias_rows_f32(P(self.W), P(self.G), P(self.b), P(E), rows, self.r, adam, s))
 
 
-def plain_l2_update(st, adam, prof=None):
-    """The in-place step W = fresh-Adam(W, G + l2 W) of every penalised plain side from its gradient table (filled by this epoch's
-    pass; both passes have read the pre-update tables by then).  Stream-ordered, no host scalars: graph-capturable."""
-    lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
-    for k, (W, tag) in enumerate(((st.U, 'user_'), (st.V, 'item_'))):
-        if st.l2_G[k] is not None:
-            step = getattr(lib, 'tmf_adam_fresh_rows_l2' + st.sfx)
-            _timed(prof, tag + 'adam_rows_l2', lambda: step(P(W), P(st.l2_G[k]), W.shape[0], st.r, adam, st.l2[k], s))
+class PlainL2Side:
+    """A plain side whose table is penalised (TrainState.set_l2): the gradient table G [rows, ld] the passes fill under TMF_EPI_GRAD
+    in the second buffer's place, and l2 = 2 alpha in fp32.  The TrainState table of the side is the variable itself."""
 
+    def __init__(self, W, r, sfx):
+        self.r, self.sfx, self.l2 = int(r), sfx, 0.0
+        self.G = torch.empty(W.shape[0], W.shape[1], dtype=torch.float32, device=W.device)
 
-def epoch_plain_l2(st, adam, loss_out, loss='mse', c=0.0, prof=None):
-    """One epoch of a state of two plain sides of which at least one is penalised: the loss's own epoch, a penalised side emitting its
-    raw gradient where the other keeps the fused epilogue; then the regularised steps in place and the swap of an unpenalised side."""
-    (ue, uo), (ie, io) = _plain_epi(st, 0), _plain_epi(st, 1)
-    run_epoch(st, adam, loss_out, loss, c, ie, io, prof, ue, uo)
-    plain_l2_update(st, adam, prof)
-    st.swap()
+    def set_l2(self, l2):
+        self.l2 = l2
 
-
-def epoch_biased(st, adam, loss_out, loss='mse', c=0.0, prof=None):
-    """One epoch of a state with at least one biased side: the loss's own epoch on the effective tables, a biased side emitting
-    its raw gradient (TMF_EPI_GRAD) where an unbiased one keeps the fused fresh-Adam epilogue into its second buffer; then the
-    bias and row updates of the biased sides (both passes have read the pre-update tables by then) and the swap of the others.
-    A penalised plain side (TrainState.set_l2) emits its raw gradient too and steps in place (plain_l2_update)."""
-    ue, uo = (_lib.EPI_GRAD, st.bias_u.G) if st.bias_u is not None else _plain_epi(st, 0)
-    ie, io = (_lib.EPI_GRAD, st.bias_v.G) if st.bias_v is not None else _plain_epi(st, 1)
-    run_epoch(st, adam, loss_out, loss, c, ie, io, prof, ue, uo)
-    if st.bias_u is not None:
-        bias_update(st.bias_u, st.U, adam, prof, 'user_')
-    if st.bias_v is not None:
-        bias_update(st.bias_v, st.V, adam, prof, 'item_')
-    plain_l2_update(st, adam, prof)
-    st.swap()
+    def step(self, E, slab, adam, prof=None, tag=''):
+        """E = fresh-Adam(E, G + l2 E) in place.  Stream-ordered, no host scalars: graph-capturable."""
+        lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
+        step = getattr(lib, 'tmf_adam_fresh_rows_l2' + self.sfx)
+        _timed(prof, tag + 'adam_rows_l2', lambda: step(P(E), P(self.G), E.shape[0], self.r, adam, self.l2, s))
 
 
 class FeatureSide:
@@ -1106,7 +1086,32 @@ class FeatureSide:
         self.n_slab = max(self.plan.seg_u.n_slab, self.plan.seg_i.n_slab)
         self.W, self.W_nxt = W0, torch.empty_like(W0)
         self.G = torch.empty(rows, W0.shape[1], dtype=torch.float32, device=dev)
-        self.l2, self.GW = 0.0, None   # TrainState.set_l2: l2 > 0 = the weights step in place from GW [n_features, ld] (no W_nxt)
+        self.l2, self.GW = 0.0, None   # set_l2: l2 > 0 = the weights step in place from GW [n_features, ld] (no W_nxt)
+
+    def set_l2(self, l2):
+        self.l2, self.GW, self.W_nxt = l2, torch.empty_like(self.W), None
+
+    def step(self, E, slab, adam, prof=None, tag=''):
+        """The step of the weights from G (filled by this epoch's pass), then the rebuilt E = F W."""
+        _timed(prof, tag + 'feat_backward', lambda: self._backward(slab, adam))
+        _timed(prof, tag + 'feat_forward', lambda: feature_forward(self.plan, self.W, E, slab, self.r))
+
+    def _backward(self, slab, adam):
+        """W_nxt[f] = fresh_adam(W[f], sum_i x_if G[i]) over the CSC lists (a feature no row carries keeps its weights), then the swap.
+        With penalised weights (l2 > 0): the sums as a table of their own, then the regularised step in place and no swap."""
+        lib, s, P, p = _lib.get(), _lib.stream_ptr(), _lib.ptr, self.plan
+        if self.l2:
+            # penalised weights: dW = F^T G into GW (a feature no row carries gets a zero row), then W = fresh-Adam(W, dW + l2 W) in
+            # place over EVERY feature - one no row carries decays, its penalty gradient is not zero
+            _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(self.G), None, P(self.GW), P(slab),
+                                             self.r, _lib.EPI_GRAD, adam, s), lib)
+            _row_pass_finish(lib, p.seg_i, slab, None, self.GW, self.r, _lib.EPI_GRAD, adam, s)
+            _lib.check(lib.tmf_adam_fresh_rows_l2_f32(P(self.W), P(self.GW), self.W.shape[0], self.r, adam, self.l2, s), lib)
+            return
+        _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(self.G), P(self.W), P(self.W_nxt), P(slab),
+                                         self.r, _lib.EPI_ADAM, adam, s), lib)
+        _row_pass_finish(lib, p.seg_i, slab, self.W, self.W_nxt, self.r, _lib.EPI_ADAM, adam, s)
+        self.W, self.W_nxt = self.W_nxt, self.W
 
 
 def feature_forward(plan, W, E, slab, r):
@@ -1127,45 +1132,6 @@ def embed_features(F, W, r, chunk=DEFAULT_CHUNK):
     slab = torch.empty(max(plan.seg_u.n_slab, 1), W.shape[1], dtype=torch.float32, device=W.device)
     feature_forward(plan, W, E, slab, r)
     return E
-
-
-def feature_backward(side, slab, adam):
-    """W_nxt[f] = fresh_adam(W[f], sum_i x_if G[i]) over the CSC lists (a feature no row carries keeps its weights), then the swap.
-    With penalised weights (side.l2 > 0): the sums as a table of their own, then the regularised step in place and no swap."""
-    lib, s, P, p = _lib.get(), _lib.stream_ptr(), _lib.ptr, side.plan
-    if side.l2:
-        # penalised weights: dW = F^T G into GW (a feature no row carries gets a zero row), then W = fresh-Adam(W, dW + l2 W) in
-        # place over EVERY feature - one no row carries decays, its penalty gradient is not zero
-        _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(side.G), None, P(side.GW), P(slab),
-                                         side.r, _lib.EPI_GRAD, adam, s), lib)
-        _row_pass_finish(lib, p.seg_i, slab, None, side.GW, side.r, _lib.EPI_GRAD, adam, s)
-        _lib.check(lib.tmf_adam_fresh_rows_l2_f32(P(side.W), P(side.GW), side.W.shape[0], side.r, adam, side.l2, s), lib)
-        return
-    _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(side.G), P(side.W), P(side.W_nxt), P(slab),
-                                     side.r, _lib.EPI_ADAM, adam, s), lib)
-    _row_pass_finish(lib, p.seg_i, slab, side.W, side.W_nxt, side.r, _lib.EPI_ADAM, adam, s)
-    side.W, side.W_nxt = side.W_nxt, side.W
-
-
-def epoch_featured(st, adam, loss_out, loss='mse', c=0.0, prof=None):
-    """One epoch of a state with at least one side over sparse features, after epoch_biased: the loss's own epoch on the effective
-    tables, a featured (or biased) side emitting its raw gradient (TMF_EPI_GRAD) where a plain one keeps the fused fresh-Adam
-    epilogue; then, for every featured side, the step of its weights from G and the rebuilt E = F W (both passes of the epoch
-    have read the pre-update tables by then), the updates of a biased side, the in-place step of a penalised plain side
-    (TrainState.set_l2) and the swap of the other plain ones.
-    Stream-ordered, nothing allocated, no host reads, no atomics: graph-capturable and bit-reproducible."""
-    sides = [(st.feat_u, st.bias_u, st.U, 'user_'), (st.feat_v, st.bias_v, st.V, 'item_')]
-    (ue, uo), (ie, io) = [(_lib.EPI_GRAD, (f or b).G) if (f or b) is not None else _plain_epi(st, k)
-                          for k, (f, b, _, _) in enumerate(sides)]
-    run_epoch(st, adam, loss_out, loss, c, ie, io, prof, ue, uo)
-    for feat, bias, E, tag in sides:
-        if feat is not None:
-            _timed(prof, tag + 'feat_backward', lambda: feature_backward(feat, st.slab, adam))
-            _timed(prof, tag + 'feat_forward', lambda: feature_forward(feat.plan, feat.W, E, st.slab, feat.r))
-        elif bias is not None:
-            bias_update(bias, E, adam, prof, tag)
-    plain_l2_update(st, adam, prof)
-    st.swap()
 
 
 class ReLUSide:
@@ -1213,6 +1179,36 @@ class ReLUSide:
         self.bias_part_rows = int(lib.tmf_bias_colsum_part_rows(self.rows))
         self.bias_part = torch.empty(self.bias_part_rows, self.ld_aux, dtype=torch.float64, device=dev)
 
+    def set_l2(self, l2):
+        raise NotImplementedError('L2 regularisation next to a ReLU side on the engine is not built')
+
+    def step(self, E, slab, adam, prof=None, tag=''):
+        """From the gradient table G (filled by this epoch's pass).  Every read of the pre-update W and b comes before their steps:
+        the partials of dW = H^T G and dZ = (G W^T) . mask first, then W, then b from the column sums of dZ, then Wr from F^T dZ
+        over the CSC lists (a feature no row carries keeps its weights); last the rebuilt Z = F Wr and E = relu(Z + b) W.
+        Stream-ordered, nothing allocated, no host scalars, no atomics: graph-capturable and bit-reproducible."""
+        lib, s, P, p = _lib.get(), _lib.stream_ptr(), _lib.ptr, self.plan
+        rows, aux, r = self.rows, self.aux, self.r
+        _timed(prof, tag + 'relu_dweights', lambda: lib.tmf_relu_dweights_f32(P(self.Z), P(self.b), P(self.G), P(self.part),
+                                                                              self.part_rows, rows, aux, r, s))
+        _timed(prof, tag + 'relu_dhidden', lambda: lib.tmf_relu_dhidden_f32(P(self.G), P(self.W), P(self.Z), P(self.b), P(self.dZ),
+                                                                            rows, aux, r, s))
+        _timed(prof, tag + 'relu_adam_weights', lambda: lib.tmf_relu_adam_weights_f32(P(self.part), self.part_rows, P(self.W),
+                                                                                      P(self.W_nxt), None, aux, r, adam, s))
+        self.W, self.W_nxt = self.W_nxt, self.W
+        _timed(prof, tag + 'relu_bias_colsum', lambda: lib.tmf_bias_colsum_f32(P(self.dZ), rows, aux, P(self.bias_part),
+                                                                               self.bias_part_rows, None, s))
+        _timed(prof, tag + 'relu_bias_adam', lambda: lib.tmf_bias_adam_f32(P(self.bias_part), self.bias_part_rows, P(self.b),
+                                                                           P(self.g_b), aux, adam, s))
+
+        def hidden_backward():
+            _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(self.dZ), P(self.Wr), P(self.Wr_nxt),
+                                             P(slab), aux, _lib.EPI_ADAM, adam, s), lib)
+            _row_pass_finish(lib, p.seg_i, slab, self.Wr, self.Wr_nxt, aux, _lib.EPI_ADAM, adam, s)
+            self.Wr, self.Wr_nxt = self.Wr_nxt, self.Wr
+        _timed(prof, tag + 'relu_feat_backward', hidden_backward)
+        relu_forward(self, E, slab, prof, tag)
+
 
 def relu_forward(side, E, slab, prof=None, tag=''):
     """E = relu(F Wr + b) W from the side's current variables: the pre-activations over the CSR lists, then tmf_relu_embed_f32."""
@@ -1233,51 +1229,17 @@ def embed_relu(F, side, chunk=DEFAULT_CHUNK):
     return E
 
 
-def relu_update(side, E, slab, adam, prof=None, tag=''):
-    """The step of one ReLU side from its gradient table side.G (filled by this epoch's pass).  Every read of the pre-update W and
-    b comes before their steps: the partials of dW = H^T G and dZ = (G W^T) . mask first, then W, then b from the column sums of
-    dZ, then Wr from F^T dZ over the CSC lists (a feature no row carries keeps its weights); last the rebuilt Z = F Wr and
-    E = relu(Z + b) W.  Stream-ordered, nothing allocated, no host scalars, no atomics: graph-capturable and bit-reproducible.
-    tag: prefix of the span names under ``prof`` (KernelTimer)."""
-    lib, s, P, p = _lib.get(), _lib.stream_ptr(), _lib.ptr, side.plan
-    rows, aux, r = side.rows, side.aux, side.r
-    _timed(prof, tag + 'relu_dweights', lambda: lib.tmf_relu_dweights_f32(P(side.Z), P(side.b), P(side.G), P(side.part),
-                                                                          side.part_rows, rows, aux, r, s))
-    _timed(prof, tag + 'relu_dhidden', lambda: lib.tmf_relu_dhidden_f32(P(side.G), P(side.W), P(side.Z), P(side.b), P(side.dZ), rows,
-                                                                        aux, r, s))
-    _timed(prof, tag + 'relu_adam_weights', lambda: lib.tmf_relu_adam_weights_f32(P(side.part), side.part_rows, P(side.W),
-                                                                                  P(side.W_nxt), None, aux, r, adam, s))
-    side.W, side.W_nxt = side.W_nxt, side.W
-    _timed(prof, tag + 'relu_bias_colsum', lambda: lib.tmf_bias_colsum_f32(P(side.dZ), rows, aux, P(side.bias_part),
-                                                                           side.bias_part_rows, None, s))
-    _timed(prof, tag + 'relu_bias_adam', lambda: lib.tmf_bias_adam_f32(P(side.bias_part), side.bias_part_rows, P(side.b), P(side.g_b),
-                                                                       aux, adam, s))
-
-    def hidden_backward():
-        _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(side.dZ), P(side.Wr), P(side.Wr_nxt), P(slab),
-                                         aux, _lib.EPI_ADAM, adam, s), lib)
-        _row_pass_finish(lib, p.seg_i, slab, side.Wr, side.Wr_nxt, aux, _lib.EPI_ADAM, adam, s)
-        side.Wr, side.Wr_nxt = side.Wr_nxt, side.Wr
-    _timed(prof, tag + 'relu_feat_backward', hidden_backward)
-    relu_forward(side, E, slab, prof, tag)
-
-
-def epoch_relu(st, adam, loss_out, loss='mse', c=0.0, prof=None):
-    """One epoch of a state with at least one ReLU side, after epoch_featured: the loss's own epoch on the effective tables, every
-    ReLU, featured or biased side emitting its raw gradient (TMF_EPI_GRAD) where a plain one keeps the fused fresh-Adam epilogue;
-    then, side by side, relu_update, the steps of a featured or biased side, and the swap of the plain ones."""
-    sides = [(st.relu_u, st.feat_u, st.bias_u, st.U, 'user_'), (st.relu_v, st.feat_v, st.bias_v, st.V, 'item_')]
-    (ue, uo), (ie, io) = [(_lib.EPI_GRAD, (x or f or b).G) if (x or f or b) is not None else (_lib.EPI_ADAM, None)
-                          for x, f, b, _, _ in sides]
+def epoch_sides(st, adam, loss_out, loss='mse', c=0.0, prof=None):
+    """One epoch of a state, whatever its sides (TrainState.sides): the loss's own epoch on the effective tables, every side that is
+    an object emitting its raw gradient into its G (TMF_EPI_GRAD) where a plain unpenalised one keeps the fused fresh-Adam epilogue
+    into its second buffer; then, user side first, the step of every such side (both passes have read the pre-update tables by
+    then) and the swap of the others.
+    Stream-ordered, nothing allocated, no host reads, no atomics: graph-capturable and bit-reproducible."""
+    (ue, uo), (ie, io) = [(_lib.EPI_ADAM, None) if side is None else (_lib.EPI_GRAD, side.G) for side in st.sides]
     run_epoch(st, adam, loss_out, loss, c, ie, io, prof, ue, uo)
-    for relu, feat, bias, E, tag in sides:
-        if relu is not None:
-            relu_update(relu, E, st.slab, adam, prof, tag)
-        elif feat is not None:
-            _timed(prof, tag + 'feat_backward', lambda: feature_backward(feat, st.slab, adam))
-            _timed(prof, tag + 'feat_forward', lambda: feature_forward(feat.plan, feat.W, E, st.slab, feat.r))
-        elif bias is not None:
-            bias_update(bias, E, adam, prof, tag)
+    for side, E, tag in zip(st.sides, (st.U, st.V), ('user_', 'item_')):
+        if side is not None:
+            side.step(E, st.slab, adam, prof, tag)
     st.swap()
 
 
@@ -1375,23 +1337,32 @@ def _row_pass_finish(lib, seg, slab, X_old, X_out, r, epi, adam, stream, sfx='_f
                                             _lib.ptr(slab), _lib.ptr(X_old), _lib.ptr(X_out), r, epi, adam, stream), lib)
 
 
+def _list_passes(st, adam, entry, span, user_slot, item_slot, tail, loss_out, item_epi, item_out, prof, user_epi, user_out):
+    """The two list passes of the pointwise losses, both reading the pre-update tables: the user pass over the CSR lists, then the
+    item pass over the CSC lists, each finished by tmf_combine_rows for the cut rows.  entry: the pass's entry point (+ the
+    state's type suffix); span: prefix of the two span names; user_slot / item_slot: what the pass gets in its loss_part argument
+    (None: nothing to write); tail: its arguments behind ``adam``; loss_out: where the user pass's per-segment loss sums (the
+    state's loss_part) are added up, None = they are not."""
+    lib, p, r, s, P = _lib.get(), st.plan, st.r, _lib.stream_ptr(), _lib.ptr
+    run = getattr(lib, entry + st.sfx)
+    U_out = st.U_nxt if user_out is None else user_out
+    _timed(prof, span + '_user_pass', lambda: run(p.seg_u.cstruct(), P(p.col_u), P(p.val_u), P(st.U), P(st.V), P(U_out), P(st.slab),
+                                                  P(user_slot), r, user_epi, adam, *tail, s))
+    _row_pass_finish(lib, p.seg_u, st.slab, st.U, U_out, r, user_epi, adam, s, st.sfx)
+    if loss_out is not None:
+        _lib.check(lib.tmf_sum_f32(P(st.loss_part), p.seg_u.nseg, P(loss_out), s), lib)
+    V_out = st.V_nxt if item_out is None else item_out
+    _timed(prof, span + '_item_pass', lambda: run(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(st.V), P(st.U), P(V_out), P(st.slab),
+                                                  P(item_slot), r, item_epi, adam, *tail, s))
+    _row_pass_finish(lib, p.seg_i, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
+
+
 def epoch_mse(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM, user_out=None):
     """One MSE epoch: user pass (+loss), item pass; both read the pre-update tables.
     loss_out: 1-element fp64 device tensor receiving sum_k (a_k - p_k)^2.
     item_epi / user_epi = EPI_GRAD write the raw fp32 gradient into item_out / user_out instead of the updated table
     (multi-GPU; optimisers other than the reference's)."""
-    lib, p, r = _lib.get(), st.plan, st.r
-    s = _lib.stream_ptr()
-    U_out = st.U_nxt if user_out is None else user_out
-    mse_pass = getattr(lib, 'tmf_mse_pass' + st.sfx)
-    _timed(prof, 'mse_user_pass', lambda: mse_pass(p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U), _lib.ptr(st.V),
-                                                   _lib.ptr(U_out), _lib.ptr(st.slab), _lib.ptr(st.loss_part), r, user_epi, adam, s))
-    _row_pass_finish(lib, p.seg_u, st.slab, st.U, U_out, r, user_epi, adam, s, st.sfx)
-    _lib.check(lib.tmf_sum_f32(_lib.ptr(st.loss_part), p.seg_u.nseg, _lib.ptr(loss_out), s), lib)
-    V_out = st.V_nxt if item_out is None else item_out
-    _timed(prof, 'mse_item_pass', lambda: mse_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(st.V), _lib.ptr(st.U),
-                                                   _lib.ptr(V_out), _lib.ptr(st.slab), None, r, item_epi, adam, s))
-    _row_pass_finish(lib, p.seg_i, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
+    _list_passes(st, adam, 'tmf_mse_pass', 'mse', st.loss_part, None, (), loss_out, item_epi, item_out, prof, user_epi, user_out)
 
 
 def epoch_logistic(st, adam, loss_out, weighted=False, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM,
@@ -1399,20 +1370,8 @@ def epoch_logistic(st, adam, loss_out, weighted=False, item_epi=_lib.EPI_ADAM, i
     """One LogisticLoss epoch: epoch_mse with tmf_logistic_pass in place of tmf_mse_pass - user pass (+loss), item pass (no
     loss, no logarithm); both read the pre-update tables.  loss_out receives sum_k w_k log(1 + exp(-y_k p_k)), y_k = +1 where the
     stored value is > 0, else -1, w_k = |value| if ``weighted`` else 1.  item_epi / user_epi as in epoch_mse."""
-    lib, p, r = _lib.get(), st.plan, st.r
-    s, wt = _lib.stream_ptr(), int(bool(weighted))
-    U_out = st.U_nxt if user_out is None else user_out
-    lg_pass = getattr(lib, 'tmf_logistic_pass' + st.sfx)
-    _timed(prof, 'logistic_user_pass', lambda: lg_pass(p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U),
-                                                       _lib.ptr(st.V), _lib.ptr(U_out), _lib.ptr(st.slab), _lib.ptr(st.loss_part), r,
-                                                       user_epi, adam, wt, s))
-    _row_pass_finish(lib, p.seg_u, st.slab, st.U, U_out, r, user_epi, adam, s, st.sfx)
-    _lib.check(lib.tmf_sum_f32(_lib.ptr(st.loss_part), p.seg_u.nseg, _lib.ptr(loss_out), s), lib)
-    V_out = st.V_nxt if item_out is None else item_out
-    _timed(prof, 'logistic_item_pass', lambda: lg_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(st.V),
-                                                       _lib.ptr(st.U), _lib.ptr(V_out), _lib.ptr(st.slab), None, r, item_epi, adam,
-                                                       wt, s))
-    _row_pass_finish(lib, p.seg_i, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
+    _list_passes(st, adam, 'tmf_logistic_pass', 'logistic', st.loss_part, None, (int(bool(weighted)),), loss_out, item_epi, item_out,
+                 prof, user_epi, user_out)
 
 
 def epoch_kl(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM, user_out=None):
@@ -1421,18 +1380,10 @@ def epoch_kl(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=Non
     loss_out: 1-element fp64 device tensor receiving the epoch's loss (a scalar).  item_epi / user_epi as in epoch_mse."""
     lib, p, r = _lib.get(), st.plan, st.r
     s = _lib.stream_ptr()
-    kl_pass = getattr(lib, 'tmf_kl_pass' + st.sfx)
     _timed(prof, 'kl_moments', lambda: getattr(lib, 'tmf_kl_moments' + st.sfx)(
         p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(st.kl_part), r, s))
     _timed(prof, 'kl_coeffs', lambda: lib.tmf_kl_coeffs(_lib.ptr(st.kl_part), p.seg_u.nseg, _lib.ptr(loss_out), _lib.ptr(st.kl_coef), s))
-    U_out = st.U_nxt if user_out is None else user_out
-    _timed(prof, 'kl_user_pass', lambda: kl_pass(p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U), _lib.ptr(st.V),
-                                          _lib.ptr(U_out), _lib.ptr(st.slab), _lib.ptr(st.kl_coef), r, user_epi, adam, s))
-    _row_pass_finish(lib, p.seg_u, st.slab, st.U, U_out, r, user_epi, adam, s, st.sfx)
-    V_out = st.V_nxt if item_out is None else item_out
-    _timed(prof, 'kl_item_pass', lambda: kl_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(st.V), _lib.ptr(st.U),
-                                          _lib.ptr(V_out), _lib.ptr(st.slab), _lib.ptr(st.kl_coef), r, item_epi, adam, s))
-    _row_pass_finish(lib, p.seg_i, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
+    _list_passes(st, adam, 'tmf_kl_pass', 'kl', st.kl_coef, st.kl_coef, (), None, item_epi, item_out, prof, user_epi, user_out)
 
 
 def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, U_out=None, pairs='hinge'):

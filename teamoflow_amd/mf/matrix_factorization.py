@@ -113,7 +113,7 @@ class MatrixFactorization:
         # 'fresh_adam') builds a new optimizer every epoch (:176), i.e. every step is Adam's first step.
         self.optimizer = 'fresh_adam'
         # extension, OFF by default: True = a ReLUEmbedding side over eye() or SparseFeatures trains on the HIP engine
-        # (_engine.ReLUSide / epoch_relu) where a biased side would; False = the generic path, as before
+        # (_engine.ReLUSide / epoch_sides) where a biased side would; False = the generic path, as before
         self.relu_engine = False
         # extension, OFF by default (the reference has no regularisation): the objective whose gradient a fit takes gains
         # user_alpha ||W_user||_F^2 + item_alpha ||W_item||_F^2 over the sides' weight matrices (never a bias); loss_history_ stays
@@ -416,25 +416,12 @@ class MatrixFactorization:
         if self.optimizer not in ('fresh_adam', 'adam'):
             raise ValueError(f"optimizer={self.optimizer!r}: 'fresh_adam' (the reference's behaviour) or 'adam'")
         if self.optimizer == 'fresh_adam':
-            if st.relu_u is not None or st.relu_v is not None:
-                return lambda epoch, out: _engine.epoch_relu(st, adam, out, loss, c)
-            if st.feat_u is not None or st.feat_v is not None:
-                return lambda epoch, out: _engine.epoch_featured(st, adam, out, loss, c)
-            if st.bias_u is not None or st.bias_v is not None:
-                return lambda epoch, out: _engine.epoch_biased(st, adam, out, loss, c)
-
-            if any(st.l2):   # a penalised plain side: its raw gradient, then the regularised step in place
-                return lambda epoch, out: _engine.epoch_plain_l2(st, adam, out, loss, c)
-
-            def fresh(epoch, out):
-                _engine.run_epoch(st, adam, out, loss, c)
-                st.swap()
-            return fresh
+            return lambda epoch, out: _engine.epoch_sides(st, adam, out, loss, c)
         if self.factor_dtype is not torch.float32:
             raise ValueError("optimizer='adam' (persistent moments) needs float32 factor tables")
         lib = _lib.get()
-        # a penalised side has its gradient table already (TrainState.set_l2)
-        gU, gV = (torch.empty_like(W) if G is None else G for W, G in zip((st.U, st.V), st.l2_G))
+        # a penalised side has its gradient table already (TrainState.set_l2); only plain sides get here
+        gU, gV = (torch.empty_like(W) if side is None else side.G for W, side in zip((st.U, st.V), st.sides))
         sides = [(W, G, torch.zeros_like(W), torch.zeros_like(W), l2)
                  for W, G, l2 in ((st.U, gU, st.l2[0]), (st.V, gV, st.l2[1]))]   # table, gradient, m, v, l2 = 2 alpha
 

@@ -1,5 +1,5 @@
 """BiasedLinearEmbedding over indicator features on the sparse HIP engine (tmf_bias_colsum_f32 / tmf_bias_adam_f32 /
-tmf_adam_bias_rows_f32, _engine.epoch_biased) against oracle.dense_ref.fit_dense_plugins - the reference loop on the dense
+tmf_adam_bias_rows_f32, _engine.BiasSide / epoch_sides) against oracle.dense_ref.fit_dense_plugins - the reference loop on the dense
 [m, n] scores, fine at these sizes.  The problems are test_biased_cpu.biased_problem's; that file also shows, on the reference
 alone, that the tolerances used here hold for the fp32 oracle itself and why no test looks at a WMRB item bias: it cancels
 analytically, so the reference steps it on rounding noise.  A whole WMRB fit therefore compares the raw item weights, the loss

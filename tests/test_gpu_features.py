@@ -1,4 +1,4 @@
-"""LinearEmbedding over SparseFeatures on the sparse HIP engine (tmf_feat_pass_f32, _engine.FeatureSide / epoch_featured) against
+"""LinearEmbedding over SparseFeatures on the sparse HIP engine (tmf_feat_pass_f32, _engine.FeatureSide / epoch_sides) against
 NumPy through the C ABI and against oracle.dense_ref.fit_dense_plugins over F.to_dense() - the reference loop on dense features
 and the dense [m, n] scores, fine at these sizes.  The problems are test_features_cpu.featured_problem's; that file also shows,
 on the reference alone, that the tolerances used here hold for the fp32 oracle itself, why whole trajectories use the hybrid
@@ -382,7 +382,7 @@ def test_span_names_of_a_featured_epoch(tm):
                        {'item_feat_backward', 'item_feat_forward', 'user_bias_colsum', 'user_bias_adam', 'user_adam_bias_rows'})):
         st = tm.E.TrainState(p['U0'] if 'user_bias' in kw else p['Wu0'], p['Wv0'], plan, 16, **kw)
         prof = tm.E.KernelTimer()
-        tm.E.epoch_featured(st, adam, loss, 'mse', prof=prof)
+        tm.E.epoch_sides(st, adam, loss, 'mse', prof=prof)
         torch.cuda.synchronize()
         assert set(prof.spans) == names | {'mse_user_pass', 'mse_item_pass'}
         assert all(b is not None for spans in prof.spans.values() for _, b in spans) and float(loss) > 0

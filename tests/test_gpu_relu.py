@@ -1,4 +1,4 @@
-"""ReLUEmbedding on the sparse HIP engine (csrc/tmf_relu.hip, _engine.ReLUSide / epoch_relu; opt-in through ``relu_engine``): the
+"""ReLUEmbedding on the sparse HIP engine (csrc/tmf_relu.hip, _engine.ReLUSide / epoch_sides; opt-in through ``relu_engine``): the
 four kernels through the C ABI against fp64 NumPy, and fits against oracle.dense_ref.fit_dense_plugins with 'relu' sides - the
 reference loop on dense features and the dense [m, n] scores, fine at these sizes.  The problems are test_relu_cpu.relu_problem's;
 that file also shows, on the reference alone, that the tolerances used here hold for the fp32 oracle itself, that the hidden units
@@ -516,7 +516,7 @@ def test_span_names_of_a_relu_epoch(tm):
                       {'item_' + x for x in names} | {'user_bias_colsum', 'user_bias_adam', 'user_adam_bias_rows'})):
         st = tm.E.TrainState(p['relu_Wu'] if 'user_relu' in kw else p['U0'], p['relu_Wv'], plan, 16, **kw)
         prof = tm.E.KernelTimer()
-        tm.E.epoch_relu(st, adam, loss, 'mse', prof=prof)
+        tm.E.epoch_sides(st, adam, loss, 'mse', prof=prof)
         torch.cuda.synchronize()
         assert set(prof.spans) == want | {'mse_user_pass', 'mse_item_pass'}
         assert all(b is not None for spans in prof.spans.values() for _, b in spans) and float(loss) > 0

@@ -1,5 +1,6 @@
 """The KernelTimer span names of every epoch - what bench.py and tools/time_*.py read - pinned as exact sets, and
 _engine.run_epoch against the direct epoch_* call: same loss and same tables, bit for bit, from equal starting tables.
+_engine.epoch_sides over every pair of side forms: the span names in launch order.
 96 users x 64 items, r = 16, S = 8, ~600 interactions of which user 0 has 300 (a row cut into three segments at chunk = 128)."""
 import pytest
 import torch
@@ -75,12 +76,113 @@ def test_span_names_and_run_epoch(eng, prob, monkeypatch, loss, sliced, names):
 def test_span_names_of_a_biased_epoch(eng, prob):
     from teamoflow_amd import _lib
     grad = dict(item_epi=_lib.EPI_GRAD, user_epi=_lib.EPI_GRAD)
-    a = run(eng, state(eng, prob, 'mse', biased=True), lambda st, adam, out, prof: eng.epoch_biased(st, adam, out, 'mse', prof=prof))
+    a = run(eng, state(eng, prob, 'mse', biased=True), lambda st, adam, out, prof: eng.epoch_sides(st, adam, out, 'mse', prof=prof))
     assert a[0] == MSE | BIAS
-    # the passes inside: run_epoch and epoch_mse write the same loss and gradient tables as epoch_biased read them from
+    # the passes inside: run_epoch and epoch_mse write the same loss and gradient tables as epoch_sides read them from
     b = run(eng, state(eng, prob, 'mse', biased=True), lambda st, adam, out, prof: eng.epoch_mse(
         st, adam, out, item_out=st.bias_v.G, user_out=st.bias_u.G, prof=prof, **grad))
     d = run(eng, state(eng, prob, 'mse', biased=True), lambda st, adam, out, prof: eng.run_epoch(
         st, adam, out, 'mse', item_out=st.bias_v.G, user_out=st.bias_u.G, prof=prof, **grad))
     assert b[0] == d[0] == MSE and same(b, d)
     assert torch.equal(a[1], b[1]) and torch.equal(a[2][2], b[2][2]) and torch.equal(a[2][5], b[2][5])   # loss, user G, item G
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# epoch_sides: every ordered pair of side forms
+# ------------------------------------------------------------------------------------------------------------------------
+N_FEATURES, ALPHA = 24, 0.01
+RELU_NAMES = ['relu_dweights', 'relu_dhidden', 'relu_adam_weights', 'relu_bias_colsum', 'relu_bias_adam', 'relu_feat_backward',
+              'relu_feat_forward', 'relu_embed']
+# form -> (kind of side, penalised, its span names in launch order)
+FORMS = {'plain': ('plain', False, []),
+         'plain_l2': ('plain', True, ['adam_rows_l2']),
+         'biased': ('bias', False, ['bias_colsum', 'bias_adam', 'adam_bias_rows']),
+         'biased_l2': ('bias', True, ['bias_colsum', 'bias_adam', 'adam_bias_rows_l2']),
+         'featured': ('feat', False, ['feat_backward', 'feat_forward']),
+         'featured_l2': ('feat', True, ['feat_backward', 'feat_forward']),
+         'relu': ('relu', False, RELU_NAMES)}
+
+
+def features(rows, seed):
+    """[rows, 24] sparse features, two to three entries per row; row 0 has 300 entries, row 2 none.  The side's lists are cut at the
+    engine's own chunk of 1024 entries, whatever the chunk of the interaction plan, so that row 0 stays one segment: row 1 has 1100
+    entries, the row whose CSR list IS cut into two."""
+    from teamoflow_amd.mf.sparse import SparseFeatures
+    g = torch.Generator().manual_seed(seed)
+    per_row = torch.randint(2, 4, (rows,), generator=g)
+    per_row[0], per_row[1], per_row[2] = 300, 1100, 0
+    row = torch.repeat_interleave(torch.arange(rows), per_row)
+    col = torch.randint(0, N_FEATURES, (row.numel(),), generator=g)
+    return SparseFeatures(torch.stack([row, col], 1), torch.randn(row.numel(), generator=g), (rows, N_FEATURES), device='cuda')
+
+
+@pytest.fixture(scope='module')
+def sides_prob(eng, prob):
+    """What the 49 states share and leave unchanged: the interaction plan, the feature matrices and the start values of every form."""
+    g = torch.Generator().manual_seed(12)
+    plan = eng.InteractionPlan(prob['idx'], prob['val'], M, N, chunk=CHUNK, csc=True)
+    assert plan.seg_u.n_long >= 1 and int(plan.rowptr_u[1]) == 300    # user 0's row is cut
+    out = dict(plan=plan)
+    for side, rows, X0 in (('user', M, prob['U0']), ('item', N, prob['V0'])):
+        F = features(rows, 13 + rows)
+        out[side] = dict(rows=rows, X0=X0, F=F, W0=0.3 * torch.randn(N_FEATURES, R_, generator=g),
+                         relu_W0=0.3 * torch.randn(5 * R_, R_, generator=g), relu_Wr0=torch.randn(rows, 5 * R_, generator=g),
+                         relu_b0=0.1 * torch.randn(5 * R_, generator=g))
+    return out
+
+
+def sides_state(eng, sp, user_form, item_form):
+    """The state of (user form, item form), before set_l2."""
+    tables, kw = [], {}
+    for side, form in (('user', user_form), ('item', item_form)):
+        kind, d = FORMS[form][0], sp[side]
+        tables.append({'plain': d['X0'], 'bias': d['X0'], 'feat': d['W0'], 'relu': d['relu_W0']}[kind])
+        if kind == 'bias':
+            kw[side + '_bias'] = torch.zeros(R_)
+        elif kind == 'feat':
+            kw[side + '_feat'] = d['F']
+        elif kind == 'relu':
+            kw[side + '_relu'] = dict(F=None, Wr0=d['relu_Wr0'], b0=d['relu_b0'])   # indicator features
+    return eng.TrainState(tables[0], tables[1], sp['plan'], R_, **kw)
+
+
+def test_epoch_sides_over_every_pair_of_forms(eng, sides_prob):
+    """One epoch_sides of each of the 7 x 7 (user form, item form) states: the ordered first occurrences of the span names are the two
+    passes, then the user side's step, then the item side's; L2 next to a ReLU side is refused by set_l2.  For (plain penalised,
+    featured) - the one pair in which a launch moved when the per-form epoch functions became epoch_sides: the penalised plain side
+    used to step after the structured ones - the old sequence by hand leaves the same bits."""
+    from teamoflow_amd import _lib
+    adam, ran, refused, compared = eng.adam_constants(LR), 0, 0, 0
+    for user_form, (user_kind, user_l2, user_names) in FORMS.items():
+        for item_form, (item_kind, item_l2, item_names) in FORMS.items():
+            what = (user_form, item_form)
+            st = sides_state(eng, sides_prob, user_form, item_form)
+            alphas = (ALPHA if user_l2 else 0.0, ALPHA if item_l2 else 0.0)
+            if 'relu' in (user_kind, item_kind) and any(alphas):
+                with pytest.raises(NotImplementedError, match='L2 regularisation next to a ReLU side'):
+                    st.set_l2(*alphas)
+                refused += 1
+                continue
+            if any(alphas):
+                st.set_l2(*alphas)
+            prof, loss = eng.KernelTimer(), torch.zeros(1, dtype=torch.float64, device='cuda')
+            eng.epoch_sides(st, adam, loss, 'mse', prof=prof)
+            torch.cuda.synchronize()
+            assert list(prof.spans) == ['mse_user_pass', 'mse_item_pass'] + ['user_' + x for x in user_names] + \
+                ['item_' + x for x in item_names], what
+            assert all(b is not None for spans in prof.spans.values() for _, b in spans) and float(loss) > 0, what
+            ran += 1
+            if what == ('plain_l2', 'featured'):
+                old = sides_state(eng, sides_prob, user_form, item_form)
+                old.set_l2(*alphas)
+                old_loss = torch.zeros(1, dtype=torch.float64, device='cuda')
+                eng.run_epoch(old, adam, old_loss, 'mse', 0.0, _lib.EPI_GRAD, old.sides[1].G, None, _lib.EPI_GRAD, old.sides[0].G)
+                old.sides[1].step(old.V, old.slab, adam, None, 'item_')
+                old.sides[0].step(old.U, old.slab, adam, None, 'user_')
+                old.swap()
+                torch.cuda.synchronize()
+                assert st.U_nxt is None and st.feat_v is st.sides[1] and bool(st.U.isfinite().all())
+                assert torch.equal(st.U, old.U) and torch.equal(st.V, old.V) and torch.equal(st.feat_v.W, old.feat_v.W)
+                assert torch.equal(loss, old_loss)
+                compared += 1
+    assert (ran, refused, compared) == (43, 6, 1)   # ReLU beside one of the three penalised forms, on either side: 6 of the 49

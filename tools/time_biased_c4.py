@@ -86,11 +86,11 @@ def child_mse(args):
     if args.child == 'biased':
         zero = torch.zeros(args.r)
         sb = _engine.TrainState(U0, V0, plan, args.r, user_bias=zero, item_bias=zero)
-        res['biased_epoch_ms'] = timed_epochs(torch, lambda e: _engine.epoch_biased(sb, adam, loss, 'mse'), args.epochs, args.warmup)
+        res['biased_epoch_ms'] = timed_epochs(torch, lambda e: _engine.epoch_sides(sb, adam, loss, 'mse'), args.epochs, args.warmup)
         res['biased_loss_after'] = float(loss)
         prof = _engine.KernelTimer()
         for e in range(args.epochs):
-            _engine.epoch_biased(sb, adam, loss, 'mse', prof=prof)
+            _engine.epoch_sides(sb, adam, loss, 'mse', prof=prof)
         torch.cuda.synchronize()
         res['bias_kernels'] = spans(prof, sb)
         res['biased_passes_ms'] = {k: prof.mean_ms(k) for k in ('mse_user_pass', 'mse_item_pass')}
@@ -135,7 +135,7 @@ def child_wmrb(args):
     del st
     zero = torch.zeros(args.r)
     sb = _engine.TrainState(U0, V0, plan, args.r, wplan, user_bias=zero, item_bias=zero)
-    res['wmrb_biased_epoch_ms'] = timed_epochs(torch, lambda e: _engine.epoch_biased(sb, adam, loss, 'wmrb', c), args.wmrb_epochs, 2)
+    res['wmrb_biased_epoch_ms'] = timed_epochs(torch, lambda e: _engine.epoch_sides(sb, adam, loss, 'wmrb', c), args.wmrb_epochs, 2)
     res['ratio'] = res['wmrb_biased_epoch_ms'] / res['wmrb_epoch_ms']
     print(json.dumps(res), flush=True)
 

@@ -79,7 +79,7 @@ def child_c4(args):
                    feature_bytes=4 * ld * sum(2 * F.nnz + 2 * F.shape[1] + F.shape[0] for F in (Fu, Fv)))
 
         def epoch(e, prof=None):
-            _engine.epoch_featured(st, adam, loss, 'mse', prof=prof)
+            _engine.epoch_sides(st, adam, loss, 'mse', prof=prof)
         res['hybrid_epoch_ms'] = timed_epochs(torch, epoch, args.epochs, args.warmup)
         res['loss_after'] = float(loss)
         prof = _engine.KernelTimer()

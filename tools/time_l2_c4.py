@@ -92,7 +92,7 @@ def child(args):
         st.set_l2(args.alpha, args.alpha)
 
         def l2(e, prof=None):
-            _engine.epoch_plain_l2(st, adam, loss, 'mse', prof=prof)
+            _engine.epoch_sides(st, adam, loss, 'mse', prof=prof)
         res['l2_epoch_ms'] = timed(torch, l2, args.epochs, args.warmup)
         res['l2_loss_after'] = float(loss)
         prof = _engine.KernelTimer()

@@ -72,11 +72,11 @@ def child_relu(args):
                                                                  b0=torch.zeros(aux, device=dev)))
     res = dict(nnz=plan.nnz, device=torch.cuda.get_device_name(0), library=os.path.basename(_lib.LIB_PATH),
                part_rows=st.relu_u.part_rows, ld_aux=st.relu_u.ld_aux)
-    res['relu_epoch_ms'] = timed(torch, lambda: _engine.epoch_relu(st, adam, loss, 'mse'), args.epochs, args.warmup)
+    res['relu_epoch_ms'] = timed(torch, lambda: _engine.epoch_sides(st, adam, loss, 'mse'), args.epochs, args.warmup)
     res['relu_loss_after'] = float(loss)
     prof = _engine.KernelTimer()
     for _ in range(args.epochs):
-        _engine.epoch_relu(st, adam, loss, 'mse', prof=prof)
+        _engine.epoch_sides(st, adam, loss, 'mse', prof=prof)
     torch.cuda.synchronize()
     res['spans_ms'] = {k: prof.mean_ms(k) for k in ('mse_user_pass', 'mse_item_pass') + tuple('user_' + x for x in SPANS)}
     res['units_on'] = float(((st.relu_u.Z[:4096, :aux] + st.relu_u.b[:aux]) > 0).float().mean())
