@@ -706,8 +706,8 @@ int tmf_unit_rows_bf16(const void* T, int64_t n_rows, int r, int64_t ldt, const 
                        int64_t ldo, float* norms, void* stream);
 
 /* EXTENSION (the reference trains by gradient steps only): alternating least squares - implicit feedback after Hu, Koren and
- * Volinsky, and plain least squares over the stored entries.  Two entry points; fit_als / fold_in_users / fold_in_items are built on
- * them.  TMF_VERSION stays 203, as for the other entry points added since: nothing that existed changes.
+ * Volinsky, and plain least squares over the stored entries.  fit_als / fold_in_users / fold_in_items are built on these entry
+ * points.  TMF_VERSION stays 203, as for the other entry points added since: nothing that existed changes.
  *
  * G = T^T T, [r, r] fp32 (G[i * ldg + j]), r in [1, 128].  Blocks of rows give partial sums, which are added in block order: no
  * atomics, so reruns are bit-identical, and G is exactly symmetric.  Only columns [0, r) of T are read.  T 16-byte aligned,
@@ -716,6 +716,10 @@ int tmf_unit_rows_bf16(const void* T, int64_t n_rows, int r, int64_t ldt, const 
 size_t tmf_gram_workspace_bytes(int64_t n_rows, int r);
 int tmf_gram_f32(const float* T, int64_t n_rows, int r, int64_t ldt, float* G, int64_t ldg, void* workspace, size_t workspace_bytes,
                  void* stream);
+/* The same contract for r in [1, 256] (the width the conjugate-gradient form takes); tmf_gram_f32 keeps its range and its bits. */
+size_t tmf_gram_wide_workspace_bytes(int64_t n_rows, int r);
+int tmf_gram_wide_f32(const float* T, int64_t n_rows, int r, int64_t ldt, float* G, int64_t ldg, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 /* One ALS half-step for q rows of a CSR (rowptr int64, col int32: ids of rows of Y; w, t: per-entry weight and target).  Row
  * `row` = ids[p], or p when ids == NULL, p < q, gets the solution of
@@ -733,10 +737,28 @@ int tmf_gram_f32(const float* T, int64_t n_rows, int r, int64_t ldt, float* G, i
  * TMF_E_INVALID before any launch.  q == 0: TMF_OK without a launch.  ids, col and rowptr are the caller's to check (device memory).
  * All row and entry offsets are 64-bit.
  * KNOWN LIMIT: one workgroup walks a row's entries serially, so a row with millions of entries serialises its workgroup; splitting
- * such rows into partial normal matrices is a follow-up, as is a conjugate-gradient form for r > 128. */
+ * such rows into partial normal matrices is a follow-up.  Wider models take the conjugate-gradient form below. */
 int tmf_als_solve_rows_f32(const float* Y, int64_t n_other, int r, int64_t ldy, const float* G0, int64_t ldg, const int64_t* rowptr,
                            const int32_t* col, const float* w, const float* t, float reg, const int32_t* ids, int64_t q, float* X,
                            int64_t ldx, int32_t* n_failed, void* stream);
+
+/* The same half-step by cg_steps steps of conjugate gradients per row, r in [1, 256], cg_steps in [1, 32]; A is never formed
+ * (A v = G0 v + reg v + sum_k w[k] (y_k . v) y_k).  teamoflow_amd/_als.py states the iteration: x starts from X0[row * ldx0 ...]
+ * (X0 == NULL: zeros), stops early once res . res <= max(1e-14 b . b, 1e-30), and a row whose p . A p is not a positive finite
+ * number fails as above (x = 0, *n_failed += 1).  A row without entries gets x = 0 whatever X0 held.
+ * X0 == X with ldx0 == ldx (in place) is legal iff ids names no row twice - the caller's duty; otherwise X0 and X must not overlap.
+ * Everything else as tmf_als_solve_rows_f32: columns [0, r) of a named row get the result and [r, ldx) exactly zero, rows not named
+ * are untouched, only columns [0, r) of the gathered rows of Y and of the rows of X0 are read, only the lower triangle of G0 is read.
+ * Arithmetic: fp32, every sum in a fixed order that depends on the row alone - 32 rows share a workgroup and the fp32 MFMA that
+ * applies G0, but a row's x is a function of its entries, Y, G0, reg, its x0 and cg_steps only: bit-identical whichever launch,
+ * position in ids or neighbours in the batch.
+ * Y, X and X0 16-byte aligned; ldy, ldx (and ldx0 with X0) >= r and multiples of 4; ldg >= r with G0; reg finite and > 0: otherwise
+ * TMF_E_INVALID before any launch.  q == 0: TMF_OK without a launch.
+ * KNOWN LIMIT: a row of 1024 entries or more is walked by its whole workgroup, one such row at a time and once per application of
+ * A (cg_steps + 1 times), so a row with millions of entries still serialises that workgroup. */
+int tmf_als_cg_rows_f32(const float* Y, int64_t n_other, int r, int64_t ldy, const float* G0, int64_t ldg, const int64_t* rowptr,
+                        const int32_t* col, const float* w, const float* t, float reg, const int32_t* ids, int64_t q, const float* X0,
+                        int64_t ldx0, float* X, int64_t ldx, int cg_steps, int32_t* n_failed, void* stream);
 
 #ifdef __cplusplus
 }

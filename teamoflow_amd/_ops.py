@@ -777,8 +777,11 @@ def reciprocal_rank_from_ranks(rowptr, ranks, n_items):
     return (1.0 / (1.0 + best.to(torch.float64))).to(torch.float32), counts
 
 
-# ---- alternating least squares (tmf_gram_f32 + tmf_als_solve_rows_f32: implicit's ALS and recalculate_user) ----
-ALS_MAX_COMPONENTS = 128   # include/tmf.h: the per-row factorisation holds the packed triangle of an r x r matrix in LDS
+# ---- alternating least squares (tmf_gram_f32 + tmf_als_solve_rows_f32 / tmf_als_cg_rows_f32: implicit's ALS and recalculate_user) ----
+ALS_MAX_COMPONENTS = 128      # include/tmf.h: the per-row factorisation holds the packed triangle of an r x r matrix in LDS
+ALS_CG_MAX_COMPONENTS = 256   # include/tmf.h: the conjugate-gradient form never forms the matrix
+ALS_CG_MAX_STEPS = 32
+ALS_CG_BATCH, ALS_CG_LONG_ROW = 32, 1024   # tmf_als_cg.hip: rows per workgroup, and the entries from which a whole workgroup walks a row
 
 
 def _als_reg(reg):
@@ -789,31 +792,29 @@ def _als_reg(reg):
 
 
 def gram(table):
-    """table^T table of a [n, r] fp32 table (any layout), r <= 128 -> [r, r] float32.  Fixed summation order: exactly symmetric, and
-    bit-identical from run to run (tmf_gram_f32)."""
+    """table^T table of a [n, r] fp32 table (any layout), r <= 256 -> [r, r] float32.  Fixed summation order: exactly symmetric, and
+    bit-identical from run to run (tmf_gram_f32; tmf_gram_wide_f32 for r > 128 only, so the bits at r <= 128 are tmf_gram_f32's)."""
     table = _table_2d(table, 'table')
-    if not 1 <= table.shape[1] <= ALS_MAX_COMPONENTS:
-        raise ValueError(f'gram: width {table.shape[1]} outside [1, {ALS_MAX_COMPONENTS}]')
+    if not 1 <= table.shape[1] <= ALS_CG_MAX_COMPONENTS:
+        raise ValueError(f'gram: width {table.shape[1]} outside [1, {ALS_CG_MAX_COMPONENTS}]')
     lib = _lib.get()
     T, n, r, ldt = _operand(table)
     G = torch.empty(r, r, dtype=torch.float32, device=T.device)
-    ws = torch.empty(lib.tmf_gram_workspace_bytes(n, r), dtype=torch.uint8, device=T.device)
-    _lib.check(lib.tmf_gram_f32(_lib.ptr(T), n, r, ldt, _lib.ptr(G), r, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), lib)
+    size, run = ((lib.tmf_gram_workspace_bytes, lib.tmf_gram_f32) if r <= ALS_MAX_COMPONENTS
+                 else (lib.tmf_gram_wide_workspace_bytes, lib.tmf_gram_wide_f32))
+    ws = torch.empty(size(n, r), dtype=torch.uint8, device=T.device)
+    _lib.check(run(_lib.ptr(T), n, r, ldt, _lib.ptr(G), r, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), lib)
     return G
 
 
-def als_solve_rows(Y, rowptr, col, w, t, reg, G0=None, ids=None, out=None, n_failed=None, check=True):
-    """One ALS half-step (tmf_als_solve_rows_f32): for the rows of the CSR (rowptr int64 [n_rows + 1], col: row ids of Y, w / t the
-    per-entry weights and targets) the solutions of (G0 + reg I + sum w y y^T) x = sum t y -> (X, n_failed).  X is the [n_rows, r]
-    view of a [n_rows, padded_ld(r)] table: ``out`` (such a view, written in place) or a fresh one of zeros.  ids: only these rows
-    are solved (any order, repeats allowed) and the others keep what X held.  n_failed: int32 [1] on the device, counting the rows
-    whose matrix was not positive definite (their x is zeros); pass the previous call's to keep counting.  check=False skips the id
-    and CSR checks (a caller that has made them once)."""
+def _als_row_operands(what, max_r, Y, rowptr, col, w, t, reg, G0, ids, out, n_failed, check):
+    """The checks and device operands als_solve_rows and als_cg_rows share -> dict(reg, Y, n_other, r, ldy, g0, ldg, rowptr, col, w, t,
+    ids, q, out, ldx, n_failed, n_rows)."""
     reg = _als_reg(reg)
     Y = _table_2d(Y, 'Y')
     n_other, r = Y.shape
-    if not 1 <= r <= ALS_MAX_COMPONENTS:
-        raise ValueError(f'als_solve_rows: width {r} outside [1, {ALS_MAX_COMPONENTS}]')
+    if not 1 <= r <= max_r:
+        raise ValueError(f'{what}: width {r} outside [1, {max_r}]')
     rowptr = torch.as_tensor(rowptr).reshape(-1)
     n_rows = rowptr.numel() - 1
     if n_rows < 0:
@@ -827,7 +828,6 @@ def als_solve_rows(Y, rowptr, col, w, t, reg, G0=None, ids=None, out=None, n_fai
             raise ValueError('rowptr is not a CSR row pointer over the entries given')
     if ids is not None:
         ids = _row_ids(ids, n_rows) if check else torch.as_tensor(ids).reshape(-1)
-    lib = _lib.get()
     Yt, _, _, ldy = _operand(Y)
     dev = Yt.device
     rowptr = _cuda(rowptr, torch.int64).contiguous()
@@ -851,10 +851,63 @@ def als_solve_rows(Y, rowptr, col, w, t, reg, G0=None, ids=None, out=None, n_fai
         n_failed = torch.zeros(1, dtype=torch.int32, device=dev)
     q = n_rows if ids is None else ids.numel()
     ldx = max(out.stride(0), r)   # a view of at most one row may state any stride
-    _lib.check(lib.tmf_als_solve_rows_f32(_lib.ptr(Yt), n_other, r, ldy, _lib.ptr(g0), ldg, _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(w),
-                                          _lib.ptr(t), reg, _lib.ptr(ids), q, _lib.ptr(out), ldx, _lib.ptr(n_failed),
+    return dict(reg=reg, Y=Yt, n_other=n_other, r=r, ldy=ldy, g0=g0, ldg=ldg, rowptr=rowptr, col=col, w=w, t=t, ids=ids, q=q, out=out,
+                ldx=ldx, n_failed=n_failed, n_rows=n_rows)
+
+
+def als_solve_rows(Y, rowptr, col, w, t, reg, G0=None, ids=None, out=None, n_failed=None, check=True):
+    """One ALS half-step (tmf_als_solve_rows_f32): for the rows of the CSR (rowptr int64 [n_rows + 1], col: row ids of Y, w / t the
+    per-entry weights and targets) the solutions of (G0 + reg I + sum w y y^T) x = sum t y -> (X, n_failed).  X is the [n_rows, r]
+    view of a [n_rows, padded_ld(r)] table: ``out`` (such a view, written in place) or a fresh one of zeros.  ids: only these rows
+    are solved (any order, repeats allowed) and the others keep what X held.  n_failed: int32 [1] on the device, counting the rows
+    whose matrix was not positive definite (their x is zeros); pass the previous call's to keep counting.  check=False skips the id
+    and CSR checks (a caller that has made them once)."""
+    o = _als_row_operands('als_solve_rows', ALS_MAX_COMPONENTS, Y, rowptr, col, w, t, reg, G0, ids, out, n_failed, check)
+    lib = _lib.get()
+    _lib.check(lib.tmf_als_solve_rows_f32(_lib.ptr(o['Y']), o['n_other'], o['r'], o['ldy'], _lib.ptr(o['g0']), o['ldg'],
+                                          _lib.ptr(o['rowptr']), _lib.ptr(o['col']), _lib.ptr(o['w']), _lib.ptr(o['t']), o['reg'],
+                                          _lib.ptr(o['ids']), o['q'], _lib.ptr(o['out']), o['ldx'], _lib.ptr(o['n_failed']),
                                           _lib.stream_ptr()), lib)
-    return out, n_failed
+    return o['out'], o['n_failed']
+
+
+def als_cg_rows(Y, rowptr, col, w, t, reg, G0=None, ids=None, x0=None, out=None, n_failed=None, cg_steps=3, check=True):
+    """als_solve_rows by ``cg_steps`` conjugate-gradient steps per row instead of a factorisation (tmf_als_cg_rows_f32; _als.py states
+    the iteration), for widths up to 256.  x0: the [n_rows, r] float32 starting values (None: zeros) - a table of its own, or ``out``
+    itself (in place), which needs ids that name no row twice (checked with check=True).  A row fails (x = 0, n_failed += 1) where
+    p^T A p is not a positive finite number."""
+    cg_steps = int(cg_steps)
+    if not 1 <= cg_steps <= ALS_CG_MAX_STEPS:
+        raise ValueError(f'als_cg_rows: cg_steps={cg_steps} outside [1, {ALS_CG_MAX_STEPS}]')
+    o = _als_row_operands('als_cg_rows', ALS_CG_MAX_COMPONENTS, Y, rowptr, col, w, t, reg, G0, ids, out, n_failed, check)
+    lib = _lib.get()
+    r, n_rows, X = o['r'], o['n_rows'], o['out']
+    ldx = o['ldx']
+    if ldx % 4:
+        raise ValueError(f'als_cg_rows: the row stride of out ({ldx}) must be a multiple of 4')
+    x0t, ldx0 = None, 0
+    if x0 is not None:
+        if not (torch.is_tensor(x0) and tuple(x0.shape) == (n_rows, r)):
+            raise ValueError(f'x0 must be a [{n_rows}, {r}] tensor')
+        in_place = x0.is_cuda and x0.dtype == torch.float32 and x0.data_ptr() == X.data_ptr() and (n_rows <= 1 or x0.stride() == X.stride())
+        if in_place:
+            if check and o['ids'] is not None and torch.unique(o['ids']).numel() != o['ids'].numel():
+                raise ValueError('als_cg_rows: in place (x0 is out) ids must not name a row twice')
+            x0t, ldx0 = X, ldx
+        else:
+            x0t, _, _, ldx0 = _operand(_table_2d(x0, 'x0'))
+            if n_rows and _overlap(x0t, n_rows, ldx0, X, ldx):
+                raise ValueError('als_cg_rows: x0 and out overlap without being the same view')
+    _lib.check(lib.tmf_als_cg_rows_f32(_lib.ptr(o['Y']), o['n_other'], r, o['ldy'], _lib.ptr(o['g0']), o['ldg'], _lib.ptr(o['rowptr']),
+                                       _lib.ptr(o['col']), _lib.ptr(o['w']), _lib.ptr(o['t']), o['reg'], _lib.ptr(o['ids']), o['q'],
+                                       _lib.ptr(x0t), ldx0, _lib.ptr(X), ldx, cg_steps, _lib.ptr(o['n_failed']), _lib.stream_ptr()), lib)
+    return X, o['n_failed']
+
+
+def _overlap(a, n_rows, lda, b, ldb):
+    """Whether the byte ranges of two float32 row tables of n_rows rows intersect."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + 4 * n_rows * ldb and b0 < a0 + 4 * n_rows * lda
 
 
 def pair_scores(A, B, pair_a, pair_b):

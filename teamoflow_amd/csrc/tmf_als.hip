@@ -21,6 +21,7 @@
 //
 // tmf_gram_f32 - G = T^T T: blocks of rows give partial [r, r] sums (8 x 8 register tiles, rows staged in LDS), a second kernel adds
 // the partials in block order.  No atomics; element (i, j) and (j, i) run the same chain on commuted products, so G is exactly symmetric.
+// tmf_gram_wide_f32 - the same for r <= 256: the rows are staged 256 wide and blockIdx.y names one of the four 128 x 128 quadrants.
 #include <math.h>
 
 #include "tmf_common.h"
@@ -35,21 +36,6 @@ constexpr int ALS_MAX_R = 128;
 typedef float als_f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }   // packed lower triangle, row-major
-
-// Columns [4 ch, 4 ch + 4) of a row of r floats: whole chunks as one 16-byte load, the last partial chunk element by element, columns
-// at or beyond r as zeros WITHOUT being read.
-__device__ __forceinline__ float4 load_row_chunk(const float* __restrict__ row, int ch, int r) {
-    const int c0 = 4 * ch;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c0 + 4 <= r) {
-        v = *reinterpret_cast<const float4*>(row + c0);
-    } else if (c0 < r) {
-        v.x = row[c0];
-        if (c0 + 1 < r) v.y = row[c0 + 1];
-        if (c0 + 2 < r) v.z = row[c0 + 2];
-    }
-    return v;
-}
 
 // 1 / sqrt(d) for a positive finite d: v_rsq_f32 and one Newton step - a fixed instruction sequence (the same bits for the same d
 // on every thread), a handful of dependent instructions where an IEEE square root and division are some sixty, and this value stands
@@ -297,7 +283,8 @@ __global__ __launch_bounds__(ALS_THREADS) void k_als_solve_rows(const float* __r
 // ---------------------------------------------------------------------------------------------
 constexpr int GRAM_THREADS = 256;
 constexpr int GRAM_ROWS = 32;          // rows staged at a time
-constexpr int GRAM_WIDTH = ALS_MAX_R;  // staged width (zero-padded)
+constexpr int GRAM_WIDTH = ALS_MAX_R;  // staged width (zero-padded); tmf_gram_wide_f32 stages twice that
+constexpr int GRAM_WIDE_MAX_R = 2 * GRAM_WIDTH;
 constexpr int GRAM_MAX_BLOCKS = 512;
 
 inline int64_t gram_rows_per_block(int64_t n_rows) {
@@ -310,22 +297,26 @@ inline int64_t gram_blocks(int64_t n_rows) {
     return (n_rows + per - 1) / per;
 }
 
-// Block b sums rows [b per, (b + 1) per) in row order into part[b][r][r]; thread (ty, tx) holds the 8 x 8 tile at (8 ty, 8 tx).
+// Block b sums rows [b per, (b + 1) per) in row order into part[b][r][r]; thread (ty, tx) holds the 8 x 8 tile at (i0, j0) =
+// (8 ty, 8 tx) + 128 (qi, qj), (qi, qj) the quadrant blockIdx.y names (WIDTH = 128: the only one).
+template <int WIDTH>
 __global__ __launch_bounds__(GRAM_THREADS) void k_gram_partial(const float* __restrict__ T, int64_t n_rows, int r, int64_t ldt,
                                                                int64_t per, float* __restrict__ part) {
-    __shared__ __attribute__((aligned(16))) float Ts[GRAM_ROWS][GRAM_WIDTH];
+    constexpr int Q = WIDTH / GRAM_WIDTH;   // quadrants per side
+    __shared__ __attribute__((aligned(16))) float Ts[GRAM_ROWS][WIDTH];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int i0 = 8 * ty + GRAM_WIDTH * ((int)blockIdx.y / Q), j0 = 8 * tx + GRAM_WIDTH * ((int)blockIdx.y % Q);
     const int64_t lo = (int64_t)blockIdx.x * per;
     const int64_t hi = lo + per < n_rows ? lo + per : n_rows;
-    const bool works = 8 * ty < r && 8 * tx < r;
+    const bool works = i0 < r && j0 < r;
     float acc[8][8];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
     for (int64_t base = lo; base < hi; base += GRAM_ROWS) {
-        for (int idx = tid; idx < GRAM_ROWS * (GRAM_WIDTH / 4); idx += GRAM_THREADS) {
-            const int k = idx / (GRAM_WIDTH / 4), c = idx % (GRAM_WIDTH / 4);
+        for (int idx = tid; idx < GRAM_ROWS * (WIDTH / 4); idx += GRAM_THREADS) {
+            const int k = idx / (WIDTH / 4), c = idx % (WIDTH / 4);
             const int64_t row = base + k;
             const float4 v = row < hi ? load_row_chunk(T + row * ldt, c, r) : make_float4(0.f, 0.f, 0.f, 0.f);
             *reinterpret_cast<float4*>(&Ts[k][4 * c]) = v;
@@ -336,8 +327,8 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_gram_partial(const float* __re
                 float x[8], y[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
-                    x[i] = Ts[k][8 * ty + i];
-                    y[i] = Ts[k][8 * tx + i];
+                    x[i] = Ts[k][i0 + i];
+                    y[i] = Ts[k][j0 + i];
                 }
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
@@ -353,7 +344,7 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_gram_partial(const float* __re
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const int gi = 8 * ty + i, gj = 8 * tx + j;
+                const int gi = i0 + i, gj = j0 + j;
                 if (gi < r && gj < r) out[gi * r + gj] = acc[i][j];
             }
     }
@@ -370,37 +361,54 @@ __global__ __launch_bounds__(GRAM_THREADS) void k_gram_combine(const float* __re
 
 inline bool als_reg_valid(float reg) { return reg > 0.f && reg <= 3.402823466e38f; }   // NaN fails the comparison
 
-}  // namespace tmf
-
-using namespace tmf;
-
-extern "C" size_t tmf_gram_workspace_bytes(int64_t n_rows, int r) {
-    if (r < 1 || r > ALS_MAX_R) return 0;
+// tmf_gram_f32 (WIDTH = 128) and tmf_gram_wide_f32 (WIDTH = 256)
+template <int WIDTH>
+size_t gram_workspace_bytes(int64_t n_rows, int r) {
+    if (r < 1 || r > WIDTH) return 0;
     const int64_t blocks = gram_blocks(n_rows);
     return (size_t)(blocks > 0 ? blocks : 1) * (size_t)r * (size_t)r * sizeof(float);
 }
 
-extern "C" int tmf_gram_f32(const float* T, int64_t n_rows, int r, int64_t ldt, float* G, int64_t ldg, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-    const char* what = "tmf_gram_f32";
-    TMF_REQUIRE(r >= 1 && r <= ALS_MAX_R, "%s: r = %d outside [1, %d]", what, r, ALS_MAX_R);
+template <int WIDTH>
+int gram(const char* what, const float* T, int64_t n_rows, int r, int64_t ldt, float* G, int64_t ldg, void* workspace,
+         size_t workspace_bytes, void* stream) {
+    TMF_REQUIRE(r >= 1 && r <= WIDTH, "%s: r = %d outside [1, %d]", what, r, WIDTH);
     TMF_REQUIRE(n_rows >= 0, "%s: n_rows = %lld", what, (long long)n_rows);
     TMF_REQUIRE(ldt >= r && ldt % 4 == 0, "%s: ldt = %lld must be >= r = %d and a multiple of 4", what, (long long)ldt, r);
     TMF_REQUIRE(ldg >= r, "%s: ldg = %lld must be >= r = %d", what, (long long)ldg, r);
     TMF_REQUIRE(G && (uintptr_t)G % 4 == 0, "%s: G is required", what);
     TMF_REQUIRE(n_rows == 0 || (T && (uintptr_t)T % 16 == 0), "%s: T must be 16-byte aligned", what);
-    TMF_REQUIRE(workspace && (uintptr_t)workspace % 4 == 0 && workspace_bytes >= tmf_gram_workspace_bytes(n_rows, r),
-                "%s: workspace of %zu bytes, %zu needed", what, workspace_bytes, tmf_gram_workspace_bytes(n_rows, r));
+    TMF_REQUIRE(workspace && (uintptr_t)workspace % 4 == 0 && workspace_bytes >= gram_workspace_bytes<WIDTH>(n_rows, r),
+                "%s: workspace of %zu bytes, %zu needed", what, workspace_bytes, gram_workspace_bytes<WIDTH>(n_rows, r));
     const int64_t blocks = gram_blocks(n_rows);
     if (blocks > 0) {
-        hipLaunchKernelGGL(k_gram_partial, dim3((unsigned)blocks), dim3(GRAM_THREADS), 0, (hipStream_t)stream, T, n_rows, r, ldt,
-                           gram_rows_per_block(n_rows), static_cast<float*>(workspace));
+        constexpr int Q = WIDTH / GRAM_WIDTH;
+        hipLaunchKernelGGL(k_gram_partial<WIDTH>, dim3((unsigned)blocks, Q * Q), dim3(GRAM_THREADS), 0, (hipStream_t)stream, T, n_rows, r,
+                           ldt, gram_rows_per_block(n_rows), static_cast<float*>(workspace));
         const int rc = check_launch(what);
         if (rc != TMF_OK) return rc;
     }
     hipLaunchKernelGGL(k_gram_combine, dim3((unsigned)((r * r + GRAM_THREADS - 1) / GRAM_THREADS)), dim3(GRAM_THREADS), 0,
                        (hipStream_t)stream, static_cast<const float*>(workspace), blocks, r, G, ldg);
     return check_launch(what);
+}
+
+}  // namespace tmf
+
+using namespace tmf;
+
+extern "C" size_t tmf_gram_workspace_bytes(int64_t n_rows, int r) { return gram_workspace_bytes<GRAM_WIDTH>(n_rows, r); }
+
+extern "C" int tmf_gram_f32(const float* T, int64_t n_rows, int r, int64_t ldt, float* G, int64_t ldg, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    return gram<GRAM_WIDTH>("tmf_gram_f32", T, n_rows, r, ldt, G, ldg, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t tmf_gram_wide_workspace_bytes(int64_t n_rows, int r) { return gram_workspace_bytes<GRAM_WIDE_MAX_R>(n_rows, r); }
+
+extern "C" int tmf_gram_wide_f32(const float* T, int64_t n_rows, int r, int64_t ldt, float* G, int64_t ldg, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    return gram<GRAM_WIDE_MAX_R>("tmf_gram_wide_f32", T, n_rows, r, ldt, G, ldg, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tmf_als_solve_rows_f32(const float* Y, int64_t n_other, int r, int64_t ldy, const float* G0, int64_t ldg,

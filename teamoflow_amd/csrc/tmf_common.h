@@ -169,6 +169,21 @@ __device__ __forceinline__ float4 load_f4_nt(const float* p) {
     return make_float4(t[0], t[1], t[2], t[3]);
 }
 
+// Columns [4 ch, 4 ch + 4) of a row of r floats: whole chunks as one 16-byte load, the last partial chunk element by element, columns
+// at or beyond r as zeros WITHOUT being read.
+__device__ __forceinline__ float4 load_row_chunk(const float* __restrict__ row, int ch, int r) {
+    const int c0 = 4 * ch;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c0 + 4 <= r) {
+        v = *reinterpret_cast<const float4*>(row + c0);
+    } else if (c0 < r) {
+        v.x = row[c0];
+        if (c0 + 1 < r) v.y = row[c0 + 1];
+        if (c0 + 2 < r) v.z = row[c0 + 2];
+    }
+    return v;
+}
+
 template <int G, int NV>
 __device__ __forceinline__ void load_row(Frag<NV>& f, const float* __restrict__ T, int64_t row, int g) {
     const float4* p = reinterpret_cast<const float4*>(T + row * (int64_t)(4 * G * NV)) + g;

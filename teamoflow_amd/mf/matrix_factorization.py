@@ -248,12 +248,15 @@ class MatrixFactorization:
     # ------------------------------------------------------------------------------------------
     # alternating least squares (extension: teamoflow_amd/_als.py)
     # ------------------------------------------------------------------------------------------
-    def _refuse_unbuilt_als_forms(self, what):
-        """ALS solves fp32 tables of at most 128 components, full-batch on one GPU (or in torch without one): every other setting is
-        refused, never run as something else."""
-        if self.n_components > _als.MAX_COMPONENTS:
+    def _refuse_unbuilt_als_forms(self, what, solver='cholesky'):
+        """ALS solves fp32 tables of at most 128 components (solver='cg': 256), full-batch on one GPU (or in torch without one): every
+        other setting is refused, never run as something else."""
+        if solver == 'cg' and self.n_components > _als.CG_MAX_COMPONENTS:
+            raise NotImplementedError(f"{what}: n_components={self.n_components} > {_als.CG_MAX_COMPONENTS} - the conjugate-gradient "
+                                      f'kernel holds a row in the registers of eight lanes; wider models are not built')
+        if solver != 'cg' and self.n_components > _als.MAX_COMPONENTS:
             raise NotImplementedError(f'{what}: n_components={self.n_components} > {_als.MAX_COMPONENTS} - the per-row factorisation '
-                                      f'holds an r x r matrix in LDS (a conjugate-gradient form for wider models is not built)')
+                                      f"holds an r x r matrix in LDS; solver='cg' takes up to {_als.CG_MAX_COMPONENTS} components")
         if self.factor_dtype is torch.bfloat16 and what == 'fit_als':
             raise NotImplementedError('fit_als: factor_dtype=torch.bfloat16 - the normal equations are solved on float32 tables only')
         if what != 'fit_als':
@@ -263,7 +266,8 @@ class MatrixFactorization:
                 raise NotImplementedError(f'fit_als with {name}={getattr(self, name)!r}: only the single-GPU full-batch fit is built, '
                                           f'and its regulariser is reg (set {name} back to its default)')
 
-    def fit_als(self, epochs, user_features, item_features, tf_interactions, *, reg=0.01, alpha=1.0, implicit=True):
+    def fit_als(self, epochs, user_features, item_features, tf_interactions, *, reg=0.01, alpha=1.0, implicit=True,
+                solver='cholesky', cg_steps=3):
         """Extension (implicit's AlternatingLeastSquares; Hu, Koren and Volinsky): ``epochs`` sweeps of alternating least squares
         instead of gradient steps - no learning rate, and converged after 10 - 20 sweeps.  Leading arguments as ``fit``.
         implicit=True: confidence 1 + alpha |a| on every stored value a, preference 1 where a > 0 and 0 everywhere else (all
@@ -272,14 +276,19 @@ class MatrixFactorization:
         Each sweep solves every user's r x r normal equations against the item table, then every item's against the user table
         (tmf_gram_f32 + tmf_als_solve_rows_f32 on a GPU, torch.linalg.cholesky_ex in chunks of rows without one), and appends the
         objective both half-steps minimise to loss_history_ (teamoflow_amd/_als.py states it).
-        Both sides must be exactly LinearEmbedding over indicator features (NotImplementedError otherwise), n_components <= 128,
-        float32 tables, one GPU, full batch; ``loss_graph``, ``lr`` and ``optimizer`` are not used.  The weights are drawn from
-        user_weight_graph / item_weight_graph in the order ``fit`` draws them; only the item draw matters, because the first
-        half-step solves the users.  Leaves what ``fit`` leaves: user_embedding / item_embedding / *_trainable, so predict, the
+        solver='cg' (implicit's use_cg=True): every row takes ``cg_steps`` (1 - 32) conjugate-gradient steps from its current value
+        instead of an exact solve (tmf_als_cg_rows_f32; teamoflow_amd/_als.py states the iteration) - several times fewer flops per
+        sweep, n_components up to 256, and a sweep no longer minimises exactly, so expect a few sweeps more.
+        Both sides must be exactly LinearEmbedding over indicator features (NotImplementedError otherwise), n_components <= 128
+        (solver='cg': 256), float32 tables, one GPU, full batch; ``loss_graph``, ``lr`` and ``optimizer`` are not used.  The weights
+        are drawn from user_weight_graph / item_weight_graph in the order ``fit`` draws them.  With solver='cholesky' only the item
+        draw matters, because the first half-step solves the users exactly; with solver='cg' the user draw matters too: the first
+        user half-step starts from it.  Leaves what ``fit`` leaves: user_embedding / item_embedding / *_trainable, so predict, the
         rankings, the metrics, similar_items / similar_users and save / load work as after ``fit``.  A row solve that meets a
         matrix that is not positive definite raises FloatingPointError after the last sweep.  Returns None."""
         reg, alpha = _als.check_hyper(reg, alpha)
-        self._refuse_unbuilt_als_forms('fit_als')
+        solver, cg_steps = _als.check_solver(solver, cg_steps)
+        self._refuse_unbuilt_als_forms('fit_als', solver)
         if not (type(self.user_repr_graph) is LinearEmbedding and type(self.item_repr_graph) is LinearEmbedding
                 and is_indicator(user_features) and is_indicator(item_features)):
             raise NotImplementedError('fit_als: both sides must be LinearEmbedding over indicator features (eye(n)); ALS on biased, '
@@ -291,34 +300,36 @@ class MatrixFactorization:
         interactions = _as_interactions(tf_interactions)
         if tuple(interactions.shape) != (n_users, n_items):
             raise ValueError(f'interactions of shape {tuple(interactions.shape)} for {n_users} users and {n_items} items')
-        U, V = _als.fit(self, int(epochs), n_users, n_items, interactions, U0, V0, reg, alpha, bool(implicit))
+        U, V = _als.fit(self, int(epochs), n_users, n_items, interactions, U0, V0, reg, alpha, bool(implicit), solver, cg_steps)
         self._reset_fit_products((False, False))
         self.__dict__.pop('_state', None)   # an earlier engine fit's TrainState: its tables are not this model's any more
         self.user_embedding, self.item_embedding = U, V
         self.user_trainable, self.item_trainable = [U], [V]
 
-    def _fold_in(self, side, interactions, reg, alpha, implicit):
+    def _fold_in(self, side, interactions, reg, alpha, implicit, solver, cg_steps):
         name = ('users', 'items')[side]
         reg, alpha = _als.check_hyper(reg, alpha)
-        self._refuse_unbuilt_als_forms(f'fold_in_{name}')
+        solver, cg_steps = _als.check_solver(solver, cg_steps)
+        self._refuse_unbuilt_als_forms(f'fold_in_{name}', solver)
         if self._item_sharded():
             raise NotImplementedError(f'item-row-sharded fit: this rank holds only its item rows; fold_in_{name} needs the whole table')
         table = getattr(self, ('item_embedding', 'user_embedding')[side], None)
         if table is None:
             raise ValueError(f'fold_in_{name}: the model has no fitted tables yet')
-        return _als.fold_in(table, _as_interactions(interactions), reg, alpha, bool(implicit))
+        return _als.fold_in(table, _as_interactions(interactions), reg, alpha, bool(implicit), solver, cg_steps)
 
-    def fold_in_users(self, interactions, *, reg=0.01, alpha=1.0, implicit=True):
+    def fold_in_users(self, interactions, *, reg=0.01, alpha=1.0, implicit=True, solver='cholesky', cg_steps=3):
         """Extension (implicit's recalculate_user): the exact embeddings of users the fit has not seen, from their interactions with
         the fitted items.  interactions: SparseInteractions [n_new, n_items] whose ROWS are the new users.  -> float32 [n_new, r]:
         one ALS half-step (as fit_als, same reg / alpha / implicit meaning) against item_embedding, which a ``fit`` or a ``fit_als``
         may have trained (a bfloat16 table is upcast first).  The model is not modified.  The rows feed
-        similar_users(queries=...) and _ops.predict_topk directly.  n_components > 128: NotImplementedError."""
-        return self._fold_in(0, interactions, reg, alpha, implicit)
+        similar_users(queries=...) and _ops.predict_topk directly.  solver='cg': ``cg_steps`` conjugate-gradient steps from zeros
+        instead of the exact solve (as fit_als).  n_components > 128 (solver='cg': 256): NotImplementedError."""
+        return self._fold_in(0, interactions, reg, alpha, implicit, solver, cg_steps)
 
-    def fold_in_items(self, interactions, *, reg=0.01, alpha=1.0, implicit=True):
+    def fold_in_items(self, interactions, *, reg=0.01, alpha=1.0, implicit=True, solver='cholesky', cg_steps=3):
         """fold_in_users for new items: interactions [n_new, n_users], rows = the new items, solved against user_embedding."""
-        return self._fold_in(1, interactions, reg, alpha, implicit)
+        return self._fold_in(1, interactions, reg, alpha, implicit, solver, cg_steps)
 
     def _report(self, epoch, loss, seconds):
         if self.verbose and (epoch + 1) % 25 == 0:
