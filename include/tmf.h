@@ -760,6 +760,27 @@ int tmf_als_cg_rows_f32(const float* Y, int64_t n_other, int r, int64_t ldy, con
                         const int32_t* col, const float* w, const float* t, float reg, const int32_t* ids, int64_t q, const float* X0,
                         int64_t ldx0, float* X, int64_t ldx, int cg_steps, int32_t* n_failed, void* stream);
 
+/* EXTENSION (the reference draws its negative table once, on the host): the table of a resampling fit, drawn on the device in one
+ * launch.  TMF_VERSION stays 203: nothing that existed changes.
+ *
+ * R[i, :] (int32 [n_users, n_samples], row-major, every element written and nothing else) = n_samples DISTINCT items of
+ * [0, n_items) in random order for user u = user_offset + i: a function of (seed, u) alone, so blocks of users drawn by separate
+ * calls are the rows of one table, and a second call gives the same bits.  It is exactly the table
+ * teamoflow_amd/mf/utils.py random_sampler_device draws on its rejection branch, which is the definition:
+ *   hash(a, b, c) = mix(mix(mix(a + (2 seed + 1) * 0x9E3779B97F4A7C15) ^ (b * 0xD6E8FEB86659FD93 + 0xA0761D6478BD642F))
+ *                       ^ (c * 0xE7037ED1A0B428DB + 0x8EBC6AF09C88C6E3)),   mix = splitmix64's finaliser, all 64-bit wrapping;
+ *   below(h) = (h >> 11) mod n_items  (logical shift: a 53-bit value);
+ *   row[pos] = below(hash(u, pos, 2)), sorted ascending; then for rnd = 3 .. 66, while the row holds an element equal to its left
+ *   neighbour: each such element, at place pos of the sorted row, becomes below(hash(u, pos, rnd)), and the row is sorted again;
+ *   R[i, j] = row[ord[j]], ord = the places pos < n_samples ordered by (hash(u, pos, 0) >> 1, pos) ascending.
+ * A row that still holds a repeat when round 66 begins stores a non-zero value to *failed (int32, device memory, zeroed by the
+ * caller; a plain store, no atomic) - at 2 n_samples == n_items, the hardest case, rows settle within about 20 rounds.
+ * tmf_sample_rows_supported: 1 <= n_samples <= 4096 (the row is sorted in LDS) and 2 n_samples <= n_items; the call returns
+ * TMF_E_INVALID before any launch otherwise, for n_users < 0, user_offset < 0 or a null pointer.  n_users == 0: TMF_OK, no launch. */
+int tmf_sample_rows_supported(int32_t n_items, int32_t n_samples);
+int tmf_sample_rows(int32_t n_items, int64_t n_users, int32_t n_samples, int64_t seed, int64_t user_offset, int32_t* R,
+                    int32_t* failed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

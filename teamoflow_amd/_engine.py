@@ -478,6 +478,13 @@ class WmrbPlan:
         self.D = self.wbuf[nnz:].view(m, S)
         self._lists = None
         self.s5 = self.s6 = self.s7 = None   # Scores5Plan / Scores6Plan / Scores7Plan, built by the TrainState that wants that scores kernel (scores5_wanted ...)
+        self.route = None   # wmrb_plan_for's keyword arguments where it built this plan: TrainState.set_negatives builds the next one alike
+
+    def release(self):
+        """Drops every index structure (entry lists, sorted table, weights, score streams, slice lists, ranks) whoever still holds the
+        plan object: TrainState.set_negatives frees the old plan before it builds the next."""
+        for name in list(vars(self)):
+            setattr(self, name, None)
 
     def lists(self, plan):
         """tmf_slice_lists of the sliced pass (kept alive with the plan)."""
@@ -555,7 +562,9 @@ def wmrb_plan_for(plan, R, n_components, dtype=torch.float32, n_items=None, forc
         ns = int(max(1, -(-n * row_bytes(n_components, dtype) // GRADU4_SLICE_BYTES)))
     rows4 = rows4_wanted(n_components, dtype, plan, R)
     C = rows5_user_chunks(m, n_components, dtype) if rows4 else default_user_chunks(m, _lib.padded_ld(n_components), n_items=plan.n_items)
-    return WmrbPlan(plan, R, user_chunks=C, item_slices=ns, n_components=n_components, sliced=sliced, rows4=rows4)
+    wplan = WmrbPlan(plan, R, user_chunks=C, item_slices=ns, n_components=n_components, sliced=sliced, rows4=rows4)
+    wplan.route = dict(n_items=n_items, force_sliced=bool(force_sliced))
+    return wplan
 
 
 def scores6_wanted(plan, wplan, n_components, dtype=torch.float32):
@@ -895,13 +904,38 @@ class TrainState:
         # own fused fresh-Adam epilogue into the second buffer (set_l2 puts a PlainL2Side there) - and l2 = 2 alpha of the side
         self.sides = [self.relu_u or self.feat_u or self.bias_u, self.relu_v or self.feat_v or self.bias_v]
         self.l2 = [0.0, 0.0]
-        need = dict(slab=max(plan.seg_u.n_slab, plan.seg_i.n_slab if plan.seg_i else 0,
-                             wplan.seg_e.n_slab if wplan is not None and wplan.seg_e is not None else 0,
-                             wplan.vrows.n_slab if wplan is not None and wplan.vrows is not None else 0,
-                             *(f.n_slab for f in (self.feat_u, self.feat_v) if f is not None), 1) * self.ld,
-                    loss_part=max(plan.seg_u.nseg, plan.n_users, 1))
-        # the list passes of a ReLU side run at width aux: the one slab holds rows of max(ld(r), ld(aux)) floats
-        need['slab'] = max([need['slab']] + [f.n_slab * f.ld_aux for f in (self.relu_u, self.relu_v) if f is not None])
+        # slab floats whatever the negative table: the interaction lists and the sides' lists; the list passes of a ReLU side run at
+        # width aux, so the one slab holds rows of max(ld(r), ld(aux)) floats
+        self._slab_fixed = max([max(plan.seg_u.n_slab, plan.seg_i.n_slab if plan.seg_i else 0,
+                                    *(f.n_slab for f in (self.feat_u, self.feat_v) if f is not None), 1) * self.ld]
+                               + [f.n_slab * f.ld_aux for f in (self.relu_u, self.relu_v) if f is not None])
+        need = dict(slab=self._slab_fixed, loss_part=max(plan.seg_u.nseg, plan.n_users, 1))
+        need.update(self._adopt_wplan())
+        self._need = need
+        self._bufs = None   # the scratch buffers where they are this state's own: set_negatives may replace one
+        if scratch is None:
+            bufs = {k: torch.zeros(v, dtype=torch.float32, device=dev) if k == 'loss_part'
+                    else torch.empty(v, dtype=torch.float32, device=dev) for k, v in need.items()}
+            self._bind(bufs)
+            if V_tables is None:
+                self._bufs = bufs
+        else:
+            scratch.setdefault('states', []).append(self)
+        for side, E in ((self.feat_u, self.U), (self.feat_v, self.V)):   # the initial E = F W0 (the slab is bound by now)
+            if side is not None:
+                feature_forward(side.plan, side.W, E, self.slab, self.r)
+        for side, E in ((self.relu_u, self.U), (self.relu_v, self.V)):   # likewise E = relu(F Wr0 + b0) W0
+            if side is not None:
+                relu_forward(side, E, self.slab)
+
+    def _adopt_wplan(self):
+        """Everything the state derives from its WmrbPlan (``self.wplan``; None: nothing): the form of gradU, the scores plans the
+        sliced pass wants, the launch sizes and sync words of the row-stationary passes.  -> the scratch sizes that depend on the plan
+        (``slab`` always; ``sp`` / ``pk`` / ``part`` of the sliced pass).  __init__ and set_negatives both come through here."""
+        plan, wplan, dtype, dev = self.plan, self.wplan, self.dtype, self.plan.col_u.device
+        need = dict(slab=max(self._slab_fixed,
+                             (wplan.seg_e.n_slab if wplan is not None and wplan.seg_e is not None else 0) * self.ld,
+                             (wplan.vrows.n_slab if wplan is not None and wplan.vrows is not None else 0) * self.ld))
         self.row_stationary = False
         if wplan is not None and wplan.sliced:
             m, S = wplan.R.shape
@@ -951,18 +985,43 @@ class TrainState:
             n_work = wplan.vrows.n_vrows if wplan.vrows is not None else plan.n_items
             nb = L.tmf_wsum_rows4_workspace_bytes(n_work, wplan.user_chunks, self.rows4_per_launch)
             self.rows4_sync = torch.zeros(max(nb // 4, 1), dtype=torch.int32, device=dev)
+        return need
+
+    def set_negatives(self, R):
+        """Another negative table (int32 [n_users, n_samples], the shape of the one it replaces) for a live state: the WmrbPlan is
+        rebuilt by the route that built it (wmrb_plan_for, same force_sliced; with the sample ranks when the old plan had them -
+        WARPLoss) and everything derived from it again by _adopt_wplan.  The tables, the side objects, l2, the gradient tables and
+        moments of persistent Adam and the InteractionPlan are not touched.  The old plan - its entry lists, score streams, slice
+        lists and ranks - is dropped BEFORE the new one is built, so the peak stays that of building the state.  ``sp`` / ``pk`` /
+        ``part`` keep their sizes (m, S and nnz do not change); the slab grows when the new lists need more, and the sync words are
+        allocated and zeroed again.  A graph captured over this state holds the old plan's pointers: capture after, not across."""
+        if self._bufs is None:
+            raise NotImplementedError('set_negatives on a state that shares its scratch (scratch= / V_tables=: the mini-batch fit) is '
+                                      'not built')
+        old = self.wplan
+        if old is None or old.route is None:
+            raise ValueError('set_negatives needs a state whose WmrbPlan was built by wmrb_plan_for')
+        R = torch.as_tensor(R).to(device=self.plan.col_u.device, dtype=torch.int32).contiguous()
+        if tuple(R.shape) != tuple(old.R_model.shape):
+            raise ValueError(f'the new table has shape {tuple(R.shape)}, the one it replaces {tuple(old.R_model.shape)}')
+        route, ranked = old.route, getattr(old, '_rank', None) is not None
+        self.wplan = None
+        self.sp = self.pk = self.part = None
+        for name in ('g4_sync', 'rows4_sync'):
+            self.__dict__.pop(name, None)
+        old.release()
+        del old
+        self.wplan = wmrb_plan_for(self.plan, R, self.r, self.dtype, **route)
+        if ranked:
+            self.wplan.sample_rank()
+        need = dict(self._need)
+        need.update(self._adopt_wplan())
+        if need['slab'] > self._bufs['slab'].numel():
+            self._bufs['slab'] = None
+            self.slab = None
+            self._bufs['slab'] = torch.empty(need['slab'], dtype=torch.float32, device=R.device)
         self._need = need
-        if scratch is None:
-            self._bind({k: torch.zeros(v, dtype=torch.float32, device=dev) if k == 'loss_part'
-                        else torch.empty(v, dtype=torch.float32, device=dev) for k, v in need.items()})
-        else:
-            scratch.setdefault('states', []).append(self)
-        for side, E in ((self.feat_u, self.U), (self.feat_v, self.V)):   # the initial E = F W0 (the slab is bound by now)
-            if side is not None:
-                feature_forward(side.plan, side.W, E, self.slab, self.r)
-        for side, E in ((self.relu_u, self.U), (self.relu_v, self.V)):   # likewise E = relu(F Wr0 + b0) W0
-            if side is not None:
-                relu_forward(side, E, self.slab)
+        self._bind(self._bufs)
 
     def _bind(self, bufs):
         """Views of the (possibly shared, larger) flat fp32 scratch buffers in this state's shapes."""

@@ -174,6 +174,8 @@ _BASE_SIGNATURES = {
     'tmf_gram_wide_workspace_bytes': (_SZ, [_L, _I]),
     'tmf_gram_wide_f32': (_I, [_P, _L, _I, _L, _P, _L, _P, _SZ, _P]),
     'tmf_als_cg_rows_f32': (_I, [_P, _L, _I, _L, _P, _L, _P, _P, _P, _P, _F, _P, _L, _P, _L, _P, _L, _I, _P, _P]),
+    'tmf_sample_rows_supported': (_I, [_I32, _I32]),
+    'tmf_sample_rows': (_I, [_I32, _L, _I32, _L, _L, _P, _P, _P]),
 }
 
 SIGNATURES.update(_BASE_SIGNATURES)

@@ -920,3 +920,40 @@ def pair_scores(A, B, pair_a, pair_b):
         _lib.check(lib.tmf_pair_scores_f32(_lib.ptr(At), _lib.ptr(Bt), r, lda, ldb, _lib.ptr(pair_a), _lib.ptr(pair_b), pair_a.numel(),
                                            _lib.ptr(out), _lib.stream_ptr()), lib)
     return out
+
+
+def sample_negatives(n_items, n_users, n_samples, seed=0, device=None, user_offset=0, out=None):
+    """int32 [n_users, n_samples]: rows user_offset .. user_offset + n_users of the negative table of ``seed`` - exactly the table
+    mf.utils.random_sampler_device draws (its definition), by one launch of tmf_sample_rows where the kernel takes the shape
+    (tmf_sample_rows_supported: 2 n_samples <= n_items, n_samples within its LDS bound) and the device is a GPU, and by the torch
+    function otherwise (most of the catalog per row, longer rows, the CPU): the same bits either way.  out: a contiguous int32
+    [n_users, n_samples] tensor on the device to draw into."""
+    from .mf.sparse import default_device
+    from .mf.utils import random_sampler_device
+    n_items, n_users, n_samples, seed, user_offset = int(n_items), int(n_users), int(n_samples), int(seed), int(user_offset)
+    device = default_device() if device is None else torch.device(device)
+    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.int32 and tuple(out.shape) == (n_users, n_samples)
+                                and out.is_contiguous() and out.device.type == device.type):
+        raise ValueError(f'out must be a contiguous int32 [{n_users}, {n_samples}] tensor on {device}')
+    if n_samples > n_items:
+        raise ValueError("Cannot take a larger sample than population when 'replace=False'")
+    if n_users < 0 or user_offset < 0:
+        raise ValueError(f'n_users={n_users}, user_offset={user_offset}: negative')
+    native = device.type == 'cuda' and 0 < n_items < 2 ** 31 and n_samples < 2 ** 31 and \
+        _lib.load_library().tmf_sample_rows_supported(n_items, n_samples)
+    if not native:
+        R = random_sampler_device(n_items, n_users, n_samples, seed=seed, device=device, user_offset=user_offset)
+        if out is None:
+            return R
+        out.copy_(R)
+        return out
+    lib = _lib.get()
+    seed = (seed + 2 ** 63) % 2 ** 64 - 2 ** 63   # the low 64 bits, as the torch function's wrapping arithmetic sees the seed
+    with torch.cuda.device(out.device if out is not None else device):
+        R = torch.empty(n_users, n_samples, dtype=torch.int32, device=device) if out is None else out
+        failed = torch.zeros(1, dtype=torch.int32, device=R.device)
+        _lib.check(lib.tmf_sample_rows(n_items, n_users, n_samples, seed, user_offset, _lib.ptr(R), _lib.ptr(failed), _lib.stream_ptr()),
+                   lib)
+        if n_users and int(failed):
+            raise RuntimeError('could not draw distinct samples')
+    return R

@@ -121,6 +121,15 @@ class MatrixFactorization:
         # interactions per row
         self.user_alpha = 0.0
         self.item_alpha = 0.0
+        # extension, OFF by default (the reference trains on ONE negative table): k > 0 = a fit of WMRBLoss, BPRLoss or WARPLoss trains
+        # epoch e on the table of round j = e // k - round 0 on random_ind as it stands, round j >= 1 on
+        # _ops.sample_negatives(n_items, n_users, n_samples of random_ind, seed=sample_seed + j) (LightFM and implicit draw fresh
+        # negatives every step).  random_ind itself is never changed, so every fit starts again from round 0.  Losses that read no
+        # table (MSE, KL, Logistic) are not affected.  Full-batch on one GPU, or the generic loop
+        self.resample_every = 0
+        self.sample_seed = 0
+        self.resample_rounds_ = 0     # tables the last fit trained on, round 0's included (0: its loss reads no table)
+        self.resample_seconds_ = 0.0  # time the last fit spent drawing tables and rebuilding their plans (part of fit_seconds_)
 
     # ------------------------------------------------------------------------------------------
     # training
@@ -205,6 +214,30 @@ class MatrixFactorization:
                 raise NotImplementedError(f'user_alpha / item_alpha > 0 with {name}={getattr(self, name)!r}: L2 regularisation is built for '
                                           f'the single-GPU full-batch fit and the generic loop only (set {name} back to its default)')
 
+    def _resample_setting(self):
+        """(resample_every, sample_seed) as ints, checked (ValueError: negative or not an integer) - resample_every as 0 for a loss that
+        reads no negative table - and the forms that own their plans elsewhere refused: the mini-batch, item-sharded and data-parallel
+        fits build one WmrbPlan per batch, window or rank and have no place where another table could enter."""
+        out = []
+        for name in ('resample_every', 'sample_seed'):
+            v = getattr(self, name, 0)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or (name == 'resample_every' and v < 0):
+                raise ValueError(f'{name}={v!r}: an integer' + (' >= 0 (0 = never resample)' if name == 'resample_every' else ''))
+            out.append(int(v))
+        if not isinstance(self.loss_graph, (WMRBLoss, BPRLoss, WARPLoss)):
+            return 0, out[1]
+        if out[0]:
+            for name in ('batch_users', 'shard_items', 'data_parallel'):
+                if getattr(self, name, 0):
+                    raise NotImplementedError(f'resample_every={out[0]} with {name}={getattr(self, name)!r}: the negative table is resampled '
+                                              f'in the single-GPU full-batch fit and the generic loop only (set {name} back to its default)')
+        return tuple(out)
+
+    def _draw_round(self, j, n_items, n_users, dev):
+        """The table of round j >= 1 (int32, on dev): a function of (sample_seed + j, shape) alone."""
+        S = int(torch.as_tensor(self.random_ind).shape[1])
+        return _ops.sample_negatives(n_items, n_users, S, seed=self._resample_setting()[1] + j, device=dev)
+
     def _reset_fit_products(self, sparse_feature_sides):
         """What one fit keeps for the calls after it and the next fit must not inherit (fit and fit_als share it): the sharded epoch
         of the last fit and the per-side records embed_users / embed_items read.  The variables the reference carries from fit to
@@ -222,6 +255,8 @@ class MatrixFactorization:
         self._refuse_unbuilt_bpr_forms()   # before any weight is drawn or plan built
         alphas = self._alphas()
         self._refuse_unbuilt_l2_forms(alphas)
+        self._resample_setting()
+        self.resample_rounds_, self.resample_seconds_ = 0, 0.0
         n_users, n_user_features = user_features.shape
         n_items, n_item_features = item_features.shape
         if not isinstance(self.user_repr_graph, ReLUEmbedding):
@@ -372,7 +407,15 @@ class MatrixFactorization:
         work = st.plan.nnz + (st.plan.n_users * st.wplan.S if loss in _engine.PAIR_LOSSES else 0)
         G = min(epochs - epochs % 2, GRAPH_EPOCHS)
         use_graph = G >= 4 and work <= GRAPH_MAX_WORK and os.environ.get('TMF_NO_GRAPH') is None and self.optimizer != 'adam'
-        sums = self._run_epochs(step, epochs, G if use_graph else 0, denom, dev, t_plan).cpu().numpy()
+        every = self._resample_setting()[0]   # 0 for a loss that reads no table
+        self.resample_rounds_ = int(loss in _engine.PAIR_LOSSES)
+        resample = None
+        if every and epochs > every:   # more than one round: no graph (a captured graph holds the plan's pointers)
+            use_graph = False
+
+            def resample(j):   # round j's table into the live state; the tables, sides, moments and the interaction plan stay
+                st.set_negatives(self._draw_round(j, n_items, n_users, dev))
+        sums = self._run_epochs(step, epochs, G if use_graph else 0, denom, dev, t_plan, every, resample).cpu().numpy()
         self.loss_history_ = (sums / denom if denom else np.full(epochs, np.nan)).tolist()
         self._publish_sparse(st)
         return True
@@ -448,8 +491,10 @@ class MatrixFactorization:
                                                        self.n_components, a, _lib.stream_ptr()), lib)
         return persistent
 
-    def _run_epochs(self, step, epochs, G, denom, dev, t_plan):
-        """step(epoch, out) for every epoch (G > 0: replays of one hipGraph of G epochs, then the rest), reports and timings.  -> loss sums."""
+    def _run_epochs(self, step, epochs, G, denom, dev, t_plan, every=0, resample=None):
+        """step(epoch, out) for every epoch (G > 0: replays of one hipGraph of G epochs, then the rest), reports and timings.  -> loss sums.
+        resample (with G = 0): resample(j) is called before the first epoch of every round j = epoch // every >= 1, between synchronisations;
+        its time goes to resample_seconds_ (and, like everything in the loop, to fit_seconds_)."""
         loss_sums = torch.zeros(max(epochs, 1), dtype=torch.float64, device=dev)
         torch.cuda.synchronize(dev)
         t0 = timeit.default_timer()
@@ -479,6 +524,13 @@ class MatrixFactorization:
                     if t_now is not None:
                         t_prev = t_now
         for epoch in range(done, epochs):
+            if resample is not None and epoch and epoch % every == 0:
+                torch.cuda.synchronize(dev)
+                t_draw = timeit.default_timer()
+                resample(epoch // every)
+                torch.cuda.synchronize(dev)
+                self.resample_seconds_ += timeit.default_timer() - t_draw
+                self.resample_rounds_ += 1
             step(epoch, loss_sums[epoch:epoch + 1])
             if self.verbose and (epoch + 1) % 25 == 0:
                 loss = float(loss_sums[epoch]) / denom if denom else float('nan')  # syncs
@@ -529,8 +581,16 @@ class MatrixFactorization:
         cumulative_time = 0.0
         random_ind = None if self.random_ind is None else torch.as_tensor(self.random_ind).to(dev)
         user_alpha, item_alpha = self._alphas()
+        every = self._resample_setting()[0]
+        self.resample_rounds_ = int(isinstance(self.loss_graph, (WMRBLoss, BPRLoss, WARPLoss)) and random_ind is not None)
         for epoch in range(epochs):
             start = timeit.default_timer()
+            if every and epoch and epoch % every == 0 and random_ind is not None:   # round epoch // every: its own table, random_ind stays
+                random_ind = self._draw_round(epoch // every, item_features.shape[0], user_features.shape[0], dev)
+                if dev.type == 'cuda':
+                    torch.cuda.synchronize(dev)
+                self.resample_seconds_ += timeit.default_timer() - start
+                self.resample_rounds_ += 1
             user_embedding, self.user_trainable = self.user_repr_graph.get_repr(
                 features=user_features, weights=U, relu_weight=self.user_relu_weight, relu_bias=self.user_relu_bias,
                 linear_bias=self.user_linear_bias)
@@ -994,6 +1054,7 @@ def _save_to_disk(model, path, include_samples=True, allow_pickle=False):
             'factor_dtype': str(model.factor_dtype).replace('torch.', ''),
             'optimizer': getattr(model, 'optimizer', 'fresh_adam'),
             'user_alpha': float(getattr(model, 'user_alpha', 0.0)), 'item_alpha': float(getattr(model, 'item_alpha', 0.0)),
+            'resample_every': int(getattr(model, 'resample_every', 0)), 'sample_seed': int(getattr(model, 'sample_seed', 0)),
             'loss_history': [float(x) for x in (getattr(model, 'loss_history_', []) or [])],
             'random_ind': (torch.as_tensor(model.random_ind).cpu() if include_samples and model.random_ind is not None else None)}
     torch.save(blob, path)
@@ -1016,6 +1077,7 @@ def _load_from_disk(cls, path, device=None, allow_pickle=False):
     model.factor_dtype = dt
     model.optimizer = blob.get('optimizer', 'fresh_adam')
     model.user_alpha, model.item_alpha = float(blob.get('user_alpha', 0.0)), float(blob.get('item_alpha', 0.0))
+    model.resample_every, model.sample_seed = int(blob.get('resample_every', 0)), int(blob.get('sample_seed', 0))
     for name in ('user_embedding', 'item_embedding'):
         t = blob[name]
         setattr(model, name, None if t is None else t.to(device=dev, dtype=dt))
