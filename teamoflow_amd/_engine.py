@@ -1370,6 +1370,31 @@ def loss_name(loss_graph):
     return names[kind]
 
 
+def form_loss(model, form, optimizer_text):
+    """loss_name at the door of a fit that is a form of its own (``form``: 'mini-batch', 'multi-GPU'): such a fit steps by the
+    reference's fresh Adam only (ValueError(optimizer_text)) and has no KLDivergenceLoss."""
+    if getattr(model, 'optimizer', 'fresh_adam') != 'fresh_adam':
+        raise ValueError(optimizer_text)
+    loss = loss_name(model.loss_graph)
+    if loss == 'kl':
+        raise ValueError(f'KLDivergenceLoss has no {form} form (its moments are global)')
+    return loss
+
+
+def checked_negatives(random_ind, n_rows, n_items, device, rows=None):
+    """The negative table as a WmrbPlan reads it - int32, contiguous, on ``device`` - once it is [n_rows, n_samples] (ValueError) with
+    ids in [0, n_items) (IndexError).  rows = (b, e): only that block of rows is moved and range-checked (a rank's users)."""
+    R = torch.as_tensor(random_ind)
+    if R.dim() != 2 or R.shape[0] != n_rows:
+        raise ValueError(f'random_ind has shape {tuple(R.shape)}, expected [{n_rows}, n_samples]')
+    if rows is not None:
+        R = R[rows[0]:rows[1]]
+    R = R.to(device=device, dtype=torch.int32).contiguous()
+    if R.numel() and (int(R.min()) < 0 or int(R.max()) >= n_items):
+        raise IndexError('random_ind holds item ids outside [0, n_items)')
+    return R
+
+
 def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM,
               user_out=None):
     """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'bpr', 'warp', 'kl', 'logistic', 'logistic_w' or 'mse' - on the

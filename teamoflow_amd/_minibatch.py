@@ -17,12 +17,9 @@ from . import _engine, _lib
 
 def fit_minibatch(model, epochs, n_users, n_items, interactions, lr, U0, V0, batch_users):
     dev = interactions.device
-    loss = _engine.loss_name(model.loss_graph)
-    if loss == 'kl':
-        raise ValueError('KLDivergenceLoss has no mini-batch form (its moments are global)')
+    loss = _engine.form_loss(model, 'mini-batch',
+                             "batch_users needs optimizer='fresh_adam' (every batch step is the reference's first Adam step)")
     wmrb = loss == 'wmrb'
-    if getattr(model, 'optimizer', 'fresh_adam') != 'fresh_adam':
-        raise ValueError("batch_users needs optimizer='fresh_adam' (every batch step is the reference's first Adam step)")
     B = int(batch_users)
     if B <= 0:
         raise ValueError(f'batch_users={batch_users}')
@@ -30,13 +27,7 @@ def fit_minibatch(model, epochs, n_users, n_items, interactions, lr, U0, V0, bat
     r, dtype = model.n_components, model.factor_dtype
     ld = _lib.padded_ld(r, dtype)
     u = interactions.indices[:, 0]
-    R = None
-    if wmrb:
-        R = torch.as_tensor(model.random_ind).to(device=dev, dtype=torch.int32).contiguous()
-        if R.dim() != 2 or R.shape[0] != n_users:
-            raise ValueError(f'random_ind has shape {tuple(R.shape)}, expected [{n_users}, n_samples]')
-        if R.numel() and (int(R.min()) < 0 or int(R.max()) >= n_items):
-            raise IndexError('random_ind holds item ids outside [0, n_items)')
+    R = _engine.checked_negatives(model.random_ind, n_users, n_items, dev) if wmrb else None
     c = model.n_items / model.n_samples if wmrb else 0.0
     U0 = torch.as_tensor(U0).detach()
     V = torch.zeros(n_items, ld, dtype=dtype, device=dev)

@@ -45,6 +45,31 @@ def padded_rows(n, world_size):
     return (n + world_size - 1) // world_size * world_size
 
 
+OPTIMIZER_TEXT = "the multi-GPU fits implement the reference's optimiser only (optimizer='fresh_adam')"
+
+
+def rank_user_block(model, interactions, n_users, world, rank, per_user_cost):
+    """(b, e, idx, val): the users [b, e) rank ``rank`` of ``world`` trains and their interactions, user ids relative to b, in the
+    input's order.  From global inputs the block is ``partition_users``' (balanced by interactions + per_user_cost); with
+    ``model.local_users = (b, e)`` the inputs are this block's already and come back as they are.  No process group is read."""
+    local = getattr(model, 'local_users', None)
+    if local is not None:
+        return int(local[0]), int(local[1]), interactions.indices, interactions.values
+    u = interactions.indices[:, 0]
+    rowptr = _engine._excl_cumsum(torch.bincount(u, minlength=n_users))
+    bounds = partition_users(rowptr, world, per_user_cost=per_user_cost)
+    b, e = bounds[rank], bounds[rank + 1]
+    idx, val = _engine.take_interactions(interactions.indices, interactions.values, (u >= b) & (u < e), user_offset=b)
+    return b, e, idx, val
+
+
+def rank_negatives(model, b, e, n_users, n_items, dev):
+    """Rows [b, e) of the checked negative table, on dev: cut from the global table, or with local_users the block's own table as it is."""
+    if getattr(model, 'local_users', None) is not None:
+        return _engine.checked_negatives(model.random_ind, e - b, n_items, dev)
+    return _engine.checked_negatives(model.random_ind, n_users, n_items, dev, rows=(b, e))
+
+
 class HipBackend:
     """Local compute of one rank on the HIP engine.  ``st`` is an _engine.TrainState whose V tables
     have n_pad rows (rows >= n_items have no interactions and stay zero)."""
@@ -345,39 +370,20 @@ def fit_item_sharded(model, epochs, n_users, n_items, interactions, lr, U0, V0, 
     import timeit
     from ._windowed import WindowedHipBackend, window_geometry
     t_plan = timeit.default_timer()
-    if getattr(model, 'optimizer', 'fresh_adam') != 'fresh_adam':
-        raise ValueError("the multi-GPU fits implement the reference's optimiser only (optimizer='fresh_adam')")
+    loss = _engine.form_loss(model, 'multi-GPU', OPTIMIZER_TEXT)
     world, rank = _world(group)
     dev = interactions.device
-    loss = _engine.loss_name(model.loss_graph)
-    if loss == 'kl':
-        raise ValueError('KLDivergenceLoss has no multi-GPU form (its moments are global)')
     wmrb = loss == 'wmrb'
     T = world * max(1, int(windows_per_rank))
     r, dtype = model.n_components, model.factor_dtype
     ld = _lib.padded_ld(r, dtype)
     rows, _, n_pad = window_geometry(n_items, T, ld, 2 if dtype is torch.bfloat16 else 4, world)
     local = getattr(model, 'local_users', None)
-    if local is not None:
-        b, e = int(local[0]), int(local[1])
-        idx, val = interactions.indices, interactions.values
-    else:
-        u = interactions.indices[:, 0]
-        rowptr = _engine._excl_cumsum(torch.bincount(u, minlength=n_users))
-        S = int(model.random_ind.shape[1]) if wmrb else 0
-        bounds = partition_users(rowptr, world, per_user_cost=S)
-        b, e = bounds[rank], bounds[rank + 1]
-        keep = (u >= b) & (u < e)
-        idx, val = _engine.take_interactions(interactions.indices, interactions.values, keep, user_offset=b)
+    S = int(model.random_ind.shape[1]) if wmrb and local is None else 0   # a WMRB user also costs its negatives
+    b, e, idx, val = rank_user_block(model, interactions, n_users, world, rank, S)
     R, c = None, 0.0
     if wmrb:
-        Rall = torch.as_tensor(model.random_ind)
-        want_rows = e - b if local is not None else n_users
-        if Rall.dim() != 2 or Rall.shape[0] != want_rows:
-            raise ValueError(f'random_ind has shape {tuple(Rall.shape)}, expected [{want_rows}, n_samples]')
-        R = (Rall if local is not None else Rall[b:e]).to(device=dev, dtype=torch.int32).contiguous()
-        if R.numel() and (int(R.min()) < 0 or int(R.max()) >= n_items):
-            raise IndexError('random_ind holds item ids outside [0, n_items)')
+        R = rank_negatives(model, b, e, n_users, n_items, dev)
         c = model.n_items / model.n_samples
     mine = owned_item_rows(rows, T, world, rank, dev)          # global ids of the owned rows of the padded catalog
     blocks = owned_blocks(rows, T, world, rank, n_items)       # the same as slices: (local row, global row, count) per window
@@ -478,40 +484,21 @@ def fit_data_parallel(model, epochs, n_users, n_items, interactions, lr, U0, V0,
     ``model.random_ind`` and the user initialiser's rows are then this block's and nothing global is touched.
     On return the model holds ``item_embedding`` (replicated), ``user_embedding`` = this rank's block,
     ``user_block`` = (begin, end); ``gather_user_embedding(model)`` assembles the full table."""
-    if getattr(model, 'optimizer', 'fresh_adam') != 'fresh_adam':
-        raise ValueError("the multi-GPU fits implement the reference's optimiser only (optimizer='fresh_adam')")
+    loss = _engine.form_loss(model, 'multi-GPU', OPTIMIZER_TEXT)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     dev = interactions.device
-    loss = _engine.loss_name(model.loss_graph)
-    if loss == 'kl':
-        raise ValueError('KLDivergenceLoss has no multi-GPU form (its moments are global)')
     wmrb = loss == 'wmrb'
     local = getattr(model, 'local_users', None)
-    if local is not None:
-        b, e = int(local[0]), int(local[1])
-        idx, val = interactions.indices, interactions.values
-        if tuple(torch.as_tensor(U0).shape)[0] != e - b:
-            raise ValueError(f'local_users = {local}: the user initialiser must return the {e - b} rows of this block')
-    else:
-        u = interactions.indices[:, 0]
-        rowptr = _engine._excl_cumsum(torch.bincount(u, minlength=n_users))
-        S = int(model.random_ind.shape[1]) if wmrb else 0
-        bounds = partition_users(rowptr, world, per_user_cost=S)
-        b, e = bounds[rank], bounds[rank + 1]
-        keep = (u >= b) & (u < e)
-        idx, val = _engine.take_interactions(interactions.indices, interactions.values, keep, user_offset=b)
+    S = int(model.random_ind.shape[1]) if wmrb and local is None else 0   # a WMRB user also costs its negatives
+    b, e, idx, val = rank_user_block(model, interactions, n_users, world, rank, S)
+    if local is not None and tuple(torch.as_tensor(U0).shape)[0] != e - b:
+        raise ValueError(f'local_users = {local}: the user initialiser must return the {e - b} rows of this block')
     n_pad = padded_rows(n_items, world)
     plan = _engine.InteractionPlan(idx, val, e - b, n_pad, user_chunks=1 if wmrb else _engine.mse_user_chunks(), csc=not wmrb)
     ld = _lib.padded_ld(model.n_components, model.factor_dtype)
     wplan, c = None, 0.0
     if wmrb:
-        Rall = torch.as_tensor(model.random_ind)
-        want_rows = e - b if local is not None else n_users
-        if Rall.dim() != 2 or Rall.shape[0] != want_rows:
-            raise ValueError(f'random_ind has shape {tuple(Rall.shape)}, expected [{want_rows}, n_samples]')
-        R = (Rall if local is not None else Rall[b:e]).to(device=dev, dtype=torch.int32).contiguous()
-        if R.numel() and (int(R.min()) < 0 or int(R.max()) >= n_items):
-            raise IndexError('random_ind holds item ids outside [0, n_items)')
+        R = rank_negatives(model, b, e, n_users, n_items, dev)
         c = model.n_items / model.n_samples
         wplan = _engine.wmrb_plan_for(plan, R, model.n_components, model.factor_dtype)
     V0p = torch.zeros(n_pad, model.n_components, dtype=torch.float32, device=dev)

@@ -1,19 +1,15 @@
 """``MatrixFactorization`` with the class surface of
 /root/reference/src/teamoflow/mf/matrix_factorization.py:23-475, computed sparsely on MI355X.
 
-Dispatch (same isinstance test the reference uses at :115,:136-162): a model made of
+Dispatch (``MatrixFactorization._route``; same isinstance test the reference uses at :115,:136-162): a model made of
 (``LinearEmbedding`` | ``BiasedLinearEmbedding``) x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss`` |
-``LogisticLoss`` | ``BPRLoss`` | ``WARPLoss``)
-- or ``LinearEmbedding`` over ``SparseFeatures`` on either side -
-trains on the HIP engine (``_engine.py`` -> libtmf.so); for unbiased MSE / WMRB it needs a GPU - there is no CPU fallback for them.
-``LogisticLoss``, ``BPRLoss`` and ``WARPLoss`` (extensions) take the engine whenever there is a GPU and the generic path without one;
-``BPRLoss`` and ``WARPLoss`` train full-batch on one GPU only and refuse ``batch_users`` / ``shard_items`` / ``data_parallel`` with ``NotImplementedError``.
-With ``relu_engine = True`` (off by default) a ``ReLUEmbedding`` side over indicator features or ``SparseFeatures`` trains there too.
-Any other combination of plug-ins (dense features, ReLU embeddings, user subclasses) trains
-through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins'
-own ``get_repr`` / ``get_loss`` - and so does KL without a GPU, with ``batch_users`` / ``shard_items`` /
-``data_parallel`` set, or on a table with an empty class, and a biased side without a GPU, with those settings, with bf16 factor
-storage or with ``optimizer='adam'`` - the settings under which a side over ``SparseFeatures`` is handed over as a dense matrix too.
+``LogisticLoss`` | ``BPRLoss`` | ``WARPLoss``) - or ``LinearEmbedding`` over ``SparseFeatures`` on either side, or with ``relu_engine = True``
+(off by default) a ``ReLUEmbedding`` side over either - trains on the HIP engine (``_engine.py`` -> libtmf.so); for unbiased MSE / WMRB it
+needs a GPU - there is no CPU fallback for them.  Any other combination of plug-ins (dense features, ReLU embeddings, user subclasses)
+trains through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins' own ``get_repr`` /
+``get_loss`` - and so does KL on a table with an empty class.  Which settings (no GPU, ``batch_users``, ``shard_items``, ``data_parallel``,
+bf16 storage, ``optimizer='adam'``) keep an engine model on the engine, hand it to the generic loop (a side over ``SparseFeatures`` then
+as a dense matrix) or are refused with ``NotImplementedError`` is the table ``ROUTES`` below.
 ``user_alpha`` / ``item_alpha`` > 0 (extensions, off by default) add ``alpha ||W_side||_F^2`` to the objective on either path: on the engine
 through the ``_l2`` twins of the table steps (``_engine.TrainState.set_l2``), in the generic loop as a term of the differentiated sum.
 ``fit_als`` (an extension) trains the same tables by alternating least squares instead of gradient steps, and ``fold_in_users`` /
@@ -37,6 +33,36 @@ PREDICT_CHUNK_BYTES = 2 << 30  # users are scored in blocks of at most this many
 HOST_SAMPLER_MAX_WORK = 2_000_000_000  # n_users * n_items above which generate_sample=True samples on the device
 GRAPH_EPOCHS = 50              # epochs captured per hipGraph on launch-bound problems
 GRAPH_MAX_WORK = 20_000_000    # interactions + sampled scores per epoch below which fit() uses graphs
+
+# What trains where (DESIGN.md prints this table; MatrixFactorization._route reads it).  A row is a feature of a fit, a column a
+# setting that leaves the single-GPU full-batch fp32 fresh-Adam fit: 'ok' = the engine has that form, 'generic' = fit() trains
+# through _fit_generic, 'refuse' = NotImplementedError before any weight is drawn or plan built.
+ENGINE_LOSSES = (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, BPRLoss, WARPLoss)   # exactly these types, no subclass
+_SETTINGS = {   # column -> (the attribute a refusal names, has the model left its default?), in the order refusals are met
+    'relu_engine': ('relu_engine', lambda m: getattr(m, 'relu_engine', 0)     # counts beside a ReLUEmbedding side only
+                    and ReLUEmbedding in (type(m.user_repr_graph), type(m.item_repr_graph))),
+    'batch_users': ('batch_users', lambda m: getattr(m, 'batch_users', 0)),
+    'shard_items': ('shard_items', lambda m: getattr(m, 'shard_items', 0)),
+    'data_parallel set': ('data_parallel', lambda m: getattr(m, 'data_parallel', 0)),      # the attribute, with or without ranks
+    'data_parallel active': ('data_parallel', lambda m: m._data_parallel_active()),        # more than one rank, or 'force'
+    'bf16': ('factor_dtype', lambda m: m.factor_dtype is not torch.float32),
+    'adam': ('optimizer', lambda m: m.optimizer != 'fresh_adam'),
+    'no GPU': (None, lambda m: not torch.cuda.is_available()),
+}
+ROUTES = {feature: dict(zip(_SETTINGS, row.split(), strict=True)) for feature, row in {
+    # feature     relu_engine  batch_users  shard_items  dp set   dp active  bf16     adam     no GPU
+    'kl':        'ok           generic      generic      ok       generic    ok       ok       generic',   # KLDivergenceLoss
+    'pair':      'ok           refuse       refuse       refuse   refuse     ok       ok       generic',   # BPRLoss, WARPLoss
+    'logistic':  'ok           ok           ok           ok       ok         ok       ok       generic',   # LogisticLoss
+    'side':      'ok           generic      generic      ok       generic    generic  generic  generic',   # biased, SparseFeatures, ReLU
+    'l2':        'refuse       refuse       refuse       refuse   refuse     ok       ok       ok',        # user_alpha / item_alpha > 0
+    'resample':  'ok           refuse       refuse       refuse   refuse     ok       ok       ok',        # resample_every on a table loss
+    'als':       'ok           refuse       refuse       refuse   refuse     refuse   ok       ok',        # fit_als
+}.items()}
+_BUILT = {'pair': 'only the single-GPU full-batch fit is built for this loss',
+          'l2': 'L2 regularisation is built for the single-GPU full-batch fit and the generic loop only',
+          'resample': 'the negative table is resampled in the single-GPU full-batch fit and the generic loop only',
+          'als': 'only the single-GPU full-batch fit is built, and its regulariser is reg'}   # how a refusal ends, per feature
 
 
 class SampleTableMissing(AttributeError):
@@ -134,60 +160,61 @@ class MatrixFactorization:
     # ------------------------------------------------------------------------------------------
     # training
     # ------------------------------------------------------------------------------------------
-    def _on_fast_path(self, user_features, item_features):
-        sides = ((type(self.user_repr_graph), user_features), (type(self.item_repr_graph), item_features))
-        featured = [isinstance(f, SparseFeatures) for _, f in sides]
-        # with relu_engine also exactly ReLUEmbedding, over either kind of features, while its aux width 5 r fits a table row
-        relu = getattr(self, 'relu_engine', False) and 5 * self.n_components <= 1024
-        linear = (LinearEmbedding, ReLUEmbedding) if relu else (LinearEmbedding,)
-        # a side is an engine side as Linear / BiasedLinear over indicator features, or as Linear over SparseFeatures with entries
-        if not (type(self.loss_graph) in (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, BPRLoss, WARPLoss)
-                and all((kind in linear and f.nnz > 0) if sparse else
-                        (kind in linear + (BiasedLinearEmbedding,) and is_indicator(f))
-                        for (kind, f), sparse in zip(sides, featured))):
-            return False
-        kinds = [k for k, _ in sides]
-        return not (any(featured) or BiasedLinearEmbedding in kinds or ReLUEmbedding in kinds) or self._sided_engine_allowed()
-
-    def _sided_engine_allowed(self):
-        """A BiasedLinearEmbedding side, and a side over SparseFeatures, train on the engine as float32 tables with the reference's
-        fresh-Adam step, full-batch on one GPU; anything else keeps the generic path."""
-        return (torch.cuda.is_available() and self.factor_dtype is torch.float32 and self.optimizer == 'fresh_adam'
-                and not getattr(self, 'batch_users', 0) and not getattr(self, 'shard_items', 0) and not self._data_parallel_active())
-
-    def _biased_engine_allowed(self):
-        return self._sided_engine_allowed()
-
     def _data_parallel_active(self):
         return bool(self.data_parallel and torch.distributed.is_available() and torch.distributed.is_initialized()
                     and torch.distributed.get_world_size() > 1 or (self.data_parallel == 'force'))
 
-    def _kl_engine_allowed(self):
-        """KLDivergenceLoss has no CPU, mini-batch, item-sharded or data-parallel form on the engine (its moments are global):
-        those settings, which the generic path ignores for KL, keep the generic path."""
-        return (torch.cuda.is_available() and not getattr(self, 'batch_users', 0) and not getattr(self, 'shard_items', 0)
-                and not self._data_parallel_active())
-
-    def _logistic_engine_allowed(self):
-        """LogisticLoss (an extension, with a generic form) takes the engine whenever there is a GPU, in every training form MSE
-        has, and the generic path without one - MSE and WMRB have no CPU form and fail there."""
-        return type(self.loss_graph) is not LogisticLoss or torch.cuda.is_available()
-
-    def _bpr_engine_allowed(self):
-        """BPRLoss and WARPLoss (extensions, with a generic form) take the engine whenever there is a GPU and the generic path
-        without one."""
-        return type(self.loss_graph) not in (BPRLoss, WARPLoss) or torch.cuda.is_available()
-
-    def _refuse_unbuilt_bpr_forms(self):
-        """BPRLoss and WARPLoss train full-batch on one GPU (or through the generic loop): the mini-batch, item-sharded and
-        data-parallel fits have call sites of their own for the pair step, which do not exist - such a fit is refused, never run as
-        another loss or densely."""
-        if type(self.loss_graph) not in (BPRLoss, WARPLoss):
-            return
-        for name in ('batch_users', 'shard_items', 'data_parallel'):
+    def _answer(self, feature, what=None, also=()):
+        """'engine', or 'generic' / NotImplementedError for the first setting, in ROUTES' column order, that this model has left the
+        default of and ``feature`` has no engine form for.  what: a refusal's name for the feature; also: attributes refused when set."""
+        def refuse(name):
+            raise NotImplementedError(f'{what} with {name}={getattr(self, name)!r}: {_BUILT[feature]} (set {name} back to its default)')
+        for setting, (name, left) in _SETTINGS.items():
+            answer = ROUTES[feature][setting]
+            if answer != 'ok' and left(self):
+                return 'generic' if answer == 'generic' else refuse(name)
+        for name in also:
             if getattr(self, name, 0):
-                raise NotImplementedError(f'{type(self.loss_graph).__name__} with {name}={getattr(self, name)!r}: only the single-GPU '
-                                          f'full-batch fit is built for this loss (set {name} back to its default)')
+                refuse(name)
+        return 'engine'
+
+    def _route(self, user_features, item_features):
+        """'engine' | 'generic': the trainer of this fit, after the refusals (NotImplementedError; ValueError for a bad user_alpha /
+        item_alpha / resample_every / sample_seed) - the one place that decides either, from ROUTES.  Nothing is drawn or built here.
+        The engine takes exactly the ENGINE_LOSSES over sides that are exactly LinearEmbedding / BiasedLinearEmbedding over indicator
+        features or LinearEmbedding over SparseFeatures with entries (with relu_engine also exactly ReLUEmbedding over either, while
+        its aux width 5 r fits a table row) when no feature of the fit answers 'generic'.  Unbiased MSE / WMRB have no row in ROUTES:
+        every setting is a form of theirs, and without a GPU they fail in _fit_sparse - there is no CPU fallback."""
+        loss, kinds = type(self.loss_graph), (type(self.user_repr_graph), type(self.item_repr_graph))
+        # the refusals, in the order a model that meets several has always met them
+        answers = [self._answer('pair', loss.__name__)] if loss in (BPRLoss, WARPLoss) else []
+        if any(self._alphas()):
+            self._answer('l2', 'user_alpha / item_alpha > 0')
+        every = self._resample_setting()[0]
+        if every:
+            self._answer('resample', f'resample_every={every}')
+        relu = getattr(self, 'relu_engine', False) and 5 * self.n_components <= 1024
+        linear = (LinearEmbedding, ReLUEmbedding) if relu else (LinearEmbedding,)
+        featured = [isinstance(f, SparseFeatures) for f in (user_features, item_features)]
+        if not (loss in ENGINE_LOSSES
+                and all((kind in linear and f.nnz > 0) if sparse else (kind in linear + (BiasedLinearEmbedding,) and is_indicator(f))
+                        for kind, f, sparse in zip(kinds, (user_features, item_features), featured))):
+            return 'generic'
+        structured = any(featured) or BiasedLinearEmbedding in kinds or ReLUEmbedding in kinds
+        answers += [self._answer(feature) for feature, there in (('kl', loss is KLDivergenceLoss), ('logistic', loss is LogisticLoss),
+                                                                 ('side', structured)) if there]
+        return 'generic' if 'generic' in answers else 'engine'
+
+    def _engine_form(self):
+        """Which fit _fit_sparse runs: 'batch_users' | 'shard_items' | 'data_parallel' | 'full'.  The forms exclude each other:
+        batch_users beside either of the others is a ValueError, raised as before when the engine fit starts."""
+        if getattr(self, 'batch_users', 0):
+            if getattr(self, 'shard_items', 0) or self.data_parallel:
+                raise ValueError('batch_users cannot be combined with shard_items / data_parallel')
+            return 'batch_users'
+        if getattr(self, 'shard_items', 0):
+            return 'shard_items'
+        return 'data_parallel' if self._data_parallel_active() else 'full'
 
     def _alphas(self):
         """(user_alpha, item_alpha) as floats, checked: negative or non-finite raises ValueError."""
@@ -202,22 +229,9 @@ class MatrixFactorization:
             out.append(a)
         return tuple(out)
 
-    def _refuse_unbuilt_l2_forms(self, alphas):
-        """A penalised side trains full-batch on one GPU through the table steps' _l2 twins, or through the generic loop.  The ReLU
-        engine, the mini-batch, item-sharded and data-parallel fits have update sites of their own that know no penalty: such a fit
-        is refused - never run unregularised."""
-        if not any(alphas):
-            return
-        relu_side = ReLUEmbedding in (type(self.user_repr_graph), type(self.item_repr_graph))
-        for name in ('relu_engine', 'batch_users', 'shard_items', 'data_parallel'):
-            if getattr(self, name, 0) and (name != 'relu_engine' or relu_side):
-                raise NotImplementedError(f'user_alpha / item_alpha > 0 with {name}={getattr(self, name)!r}: L2 regularisation is built for '
-                                          f'the single-GPU full-batch fit and the generic loop only (set {name} back to its default)')
-
     def _resample_setting(self):
         """(resample_every, sample_seed) as ints, checked (ValueError: negative or not an integer) - resample_every as 0 for a loss that
-        reads no negative table - and the forms that own their plans elsewhere refused: the mini-batch, item-sharded and data-parallel
-        fits build one WmrbPlan per batch, window or rank and have no place where another table could enter."""
+        reads no negative table.  The forms that cannot resample are refused by _route (ROUTES['resample'])."""
         out = []
         for name in ('resample_every', 'sample_seed'):
             v = getattr(self, name, 0)
@@ -226,11 +240,6 @@ class MatrixFactorization:
             out.append(int(v))
         if not isinstance(self.loss_graph, (WMRBLoss, BPRLoss, WARPLoss)):
             return 0, out[1]
-        if out[0]:
-            for name in ('batch_users', 'shard_items', 'data_parallel'):
-                if getattr(self, name, 0):
-                    raise NotImplementedError(f'resample_every={out[0]} with {name}={getattr(self, name)!r}: the negative table is resampled '
-                                              f'in the single-GPU full-batch fit and the generic loop only (set {name} back to its default)')
         return tuple(out)
 
     def _draw_round(self, j, n_items, n_users, dev):
@@ -252,10 +261,7 @@ class MatrixFactorization:
         """matrix_factorization.py:96-187.  Re-initialises the weights on every call, runs ``epochs``
         full-batch steps (loss -> gradient of the SUM of the per-interaction losses -> a fresh Adam
         step), then stores user_embedding / item_embedding / *_trainable.  Returns None."""
-        self._refuse_unbuilt_bpr_forms()   # before any weight is drawn or plan built
-        alphas = self._alphas()
-        self._refuse_unbuilt_l2_forms(alphas)
-        self._resample_setting()
+        route = self._route(user_features, item_features)   # and the refusals: before any weight is drawn or plan built
         self.resample_rounds_, self.resample_seconds_ = 0, 0.0
         n_users, n_user_features = user_features.shape
         n_items, n_item_features = item_features.shape
@@ -268,10 +274,8 @@ class MatrixFactorization:
         else:
             V = self.item_weight_graph.initialize_weights(self.item_aux_dim, self.n_components)
         interactions = _as_interactions(tf_interactions)
-        kl = type(self.loss_graph) is KLDivergenceLoss
         self._reset_fit_products((isinstance(user_features, SparseFeatures), isinstance(item_features, SparseFeatures)))
-        if (self._on_fast_path(user_features, item_features) and (not kl or self._kl_engine_allowed())
-                and self._logistic_engine_allowed() and self._bpr_engine_allowed()):
+        if route == 'engine':
             feats = [f if sparse else None for f, sparse in zip((user_features, item_features), self._sparse_feature_sides)]
             if self._fit_sparse(epochs, n_users, n_items, interactions, lr, U, V, *feats):
                 return
@@ -283,9 +287,8 @@ class MatrixFactorization:
     # ------------------------------------------------------------------------------------------
     # alternating least squares (extension: teamoflow_amd/_als.py)
     # ------------------------------------------------------------------------------------------
-    def _refuse_unbuilt_als_forms(self, what, solver='cholesky'):
-        """ALS solves fp32 tables of at most 128 components (solver='cg': 256), full-batch on one GPU (or in torch without one): every
-        other setting is refused, never run as something else."""
+    def _check_als_kernel(self, what, solver='cholesky'):
+        """ALS solves fp32 tables of at most 128 components (solver='cg': 256): the row-solve kernels' limits (forms: ROUTES['als'])."""
         if solver == 'cg' and self.n_components > _als.CG_MAX_COMPONENTS:
             raise NotImplementedError(f"{what}: n_components={self.n_components} > {_als.CG_MAX_COMPONENTS} - the conjugate-gradient "
                                       f'kernel holds a row in the registers of eight lanes; wider models are not built')
@@ -294,12 +297,6 @@ class MatrixFactorization:
                                       f"holds an r x r matrix in LDS; solver='cg' takes up to {_als.CG_MAX_COMPONENTS} components")
         if self.factor_dtype is torch.bfloat16 and what == 'fit_als':
             raise NotImplementedError('fit_als: factor_dtype=torch.bfloat16 - the normal equations are solved on float32 tables only')
-        if what != 'fit_als':
-            return
-        for name in ('batch_users', 'shard_items', 'data_parallel', 'user_alpha', 'item_alpha'):
-            if getattr(self, name, 0):
-                raise NotImplementedError(f'fit_als with {name}={getattr(self, name)!r}: only the single-GPU full-batch fit is built, '
-                                          f'and its regulariser is reg (set {name} back to its default)')
 
     def fit_als(self, epochs, user_features, item_features, tf_interactions, *, reg=0.01, alpha=1.0, implicit=True,
                 solver='cholesky', cg_steps=3):
@@ -323,7 +320,9 @@ class MatrixFactorization:
         matrix that is not positive definite raises FloatingPointError after the last sweep.  Returns None."""
         reg, alpha = _als.check_hyper(reg, alpha)
         solver, cg_steps = _als.check_solver(solver, cg_steps)
-        self._refuse_unbuilt_als_forms('fit_als', solver)
+        self._check_als_kernel('fit_als', solver)
+        # full-batch on one GPU (or in torch without one): every other form is refused, and so is the L2 of fit() - ALS has reg
+        self._answer('als', 'fit_als', also=('user_alpha', 'item_alpha'))
         if not (type(self.user_repr_graph) is LinearEmbedding and type(self.item_repr_graph) is LinearEmbedding
                 and is_indicator(user_features) and is_indicator(item_features)):
             raise NotImplementedError('fit_als: both sides must be LinearEmbedding over indicator features (eye(n)); ALS on biased, '
@@ -345,7 +344,7 @@ class MatrixFactorization:
         name = ('users', 'items')[side]
         reg, alpha = _als.check_hyper(reg, alpha)
         solver, cg_steps = _als.check_solver(solver, cg_steps)
-        self._refuse_unbuilt_als_forms(f'fold_in_{name}', solver)
+        self._check_als_kernel(f'fold_in_{name}', solver)   # a fold-in has no forms: ROUTES['als'] is about fit_als alone
         if self._item_sharded():
             raise NotImplementedError(f'item-row-sharded fit: this rank holds only its item rows; fold_in_{name} needs the whole table')
         table = getattr(self, ('item_embedding', 'user_embedding')[side], None)
@@ -383,15 +382,14 @@ class MatrixFactorization:
         loss = _engine.loss_name(self.loss_graph)
         if loss in _engine.PAIR_LOSSES and self.random_ind is None:
             raise SampleTableMissing(f'{type(self.loss_graph).__name__} needs generate_sample=True (random_ind is None)')
-        if getattr(self, 'batch_users', 0):
-            if getattr(self, 'shard_items', 0) or self.data_parallel:
-                raise ValueError('batch_users cannot be combined with shard_items / data_parallel')
+        form = self._engine_form()
+        if form == 'batch_users':
             from .. import _minibatch
             _minibatch.fit_minibatch(self, epochs, n_users, n_items, interactions, lr, U0, V0, self.batch_users)
             return True
-        if getattr(self, 'shard_items', 0) or self._data_parallel_active():
+        if form != 'full':
             from .. import dist as tdist
-            if getattr(self, 'shard_items', 0):
+            if form == 'shard_items':
                 tdist.fit_item_sharded(self, epochs, n_users, n_items, interactions, lr, U0, V0, windows_per_rank=int(self.shard_items))
             else:
                 tdist.fit_data_parallel(self, epochs, n_users, n_items, interactions, lr, U0, V0)
@@ -431,11 +429,7 @@ class MatrixFactorization:
             return None, 0.0
         wplan, c = None, 0.0
         if wmrb:
-            R = torch.as_tensor(self.random_ind).to(device=dev, dtype=torch.int32).contiguous()
-            if R.dim() != 2 or R.shape[0] != n_users:
-                raise ValueError(f'random_ind has shape {tuple(R.shape)}, expected [{n_users}, n_samples]')
-            if R.numel() and (int(R.min()) < 0 or int(R.max()) >= n_items):
-                raise IndexError('random_ind holds item ids outside [0, n_items)')
+            R = _engine.checked_negatives(self.random_ind, n_users, n_items, dev)
             if loss == 'wmrb':
                 c = self.n_items / self.n_samples  # constructor ints, true division (:167)
             wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype, force_sliced=loss != 'wmrb')

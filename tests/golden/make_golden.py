@@ -15,6 +15,7 @@ reproduced) and are stored in the fixtures.
 """
 import hashlib
 import os
+import string
 import sys
 
 import numpy as np
@@ -192,7 +193,119 @@ def plugins():
         save(name, **plugin_case(name))
 
 
+# ------------------------------------------------------------------------------------------------------------------------
+# fit_routes.json: which trainer MatrixFactorization.fit / fit_als calls, or what it refuses with, over a grid of models
+# ------------------------------------------------------------------------------------------------------------------------
+ROUTE_LOSSES = ('MSELoss', 'WMRBLoss', 'KLDivergenceLoss', 'LogisticLoss', 'BPRLoss', 'WARPLoss', 'subclass of MSELoss')
+ROUTE_SIDES = ('Linear/eye', 'Biased/eye', 'ReLU/eye', 'Linear/SparseFeatures', 'ReLU/SparseFeatures', 'Linear/dense',
+               'subclass of Linear/eye')
+ROUTE_SETTINGS = (('batch_users', 8), ('shard_items', 2), ('data_parallel', True), ('data_parallel', 'force'),
+                  ('factor_dtype', 'bfloat16'), ('optimizer', 'adam'), ('relu_engine', True), ('user_alpha', 0.1),
+                  ('resample_every', 3))
+ROUTE_ALS_SETTINGS = ROUTE_SETTINGS + (('item_alpha', 0.1),)
+
+
+def route_setting_combos():
+    """No setting, every single one, every unordered pair of two different attributes: 1 + 9 + 35."""
+    single = [(s,) for s in ROUTE_SETTINGS]
+    pairs = [(a, b) for i, a in enumerate(ROUTE_SETTINGS) for b in ROUTE_SETTINGS[i + 1:] if a[0] != b[0]]
+    return [()] + single + pairs
+
+
+def fit_route_outcomes():
+    """What the imported teamoflow_amd does, as {'fit': {'<loss> gpu=<bool>': [outcome per (user side, item side, combo)]},
+    'als': {'gpu=<bool>': [outcome per (user side, item side, setting)]}} - an outcome is 'engine' / 'generic' (fit), 'als' (fit_als) or
+    'ExceptionType: message'.  The trainers are patched to record their call; no GPU and no libtmf.so is needed."""
+    import torch
+    from teamoflow_amd import _als
+    from teamoflow_amd.mf import embedding_graphs as E, loss_graphs as L
+    from teamoflow_amd.mf.initializer_graphs import Initializer
+    from teamoflow_amd.mf.matrix_factorization import MatrixFactorization
+    from teamoflow_amd.mf.sparse import SparseFeatures, SparseInteractions, eye
+
+    class MyMSE(L.MSELoss):
+        pass
+
+    class MyLinear(E.LinearEmbedding):
+        pass
+
+    class CpuZeros(Initializer):   # the built-in initialisers ask for the current device
+        def initialize_weights(self, n_features, n_components):
+            return torch.zeros(n_features, n_components)
+
+    m, n, r = 6, 7, 2
+    losses = dict(zip(ROUTE_LOSSES, (L.MSELoss, L.WMRBLoss, L.KLDivergenceLoss, L.LogisticLoss, L.BPRLoss, L.WARPLoss, MyMSE)))
+
+    def features(kind, rows):   # built on the CPU, before torch.cuda.is_available is patched
+        if kind == 'SparseFeatures':
+            own = torch.arange(rows)
+            return SparseFeatures(torch.stack([own, (own + 1) % 4], 1), torch.ones(rows), (rows, 4), device='cpu')
+        return torch.eye(rows) + 0.5 if kind == 'dense' else eye(rows)
+    graphs = {'Linear': E.LinearEmbedding, 'Biased': E.BiasedLinearEmbedding, 'ReLU': E.ReLUEmbedding, 'subclass of Linear': MyLinear}
+    sides = [(graphs[s.split('/')[0]], features(s.split('/')[1], m), features(s.split('/')[1], n)) for s in ROUTE_SIDES]
+    interactions = SparseInteractions(torch.tensor([[0, 1], [2, 3], [5, 6]]), torch.tensor([1.0, -1.0, 2.0]), (m, n), device='cpu')
+
+    def model(loss, user, item, settings):
+        mf = MatrixFactorization(r, user(), item(), loss(), CpuZeros(), CpuZeros(), n_users=m, n_items=n, n_samples=3)
+        mf.random_ind, mf.verbose = torch.zeros(m, 3, dtype=torch.int64), False
+        for name, value in settings:
+            setattr(mf, name, torch.bfloat16 if value == 'bfloat16' else value)
+        return mf
+
+    calls = []
+
+    def outcome(call):
+        del calls[:]
+        try:
+            call()
+        except Exception as e:   # noqa: BLE001 - the refusal is the record
+            return f'{type(e).__name__}: {e}'
+        return calls[-1]
+
+    kept = MatrixFactorization._fit_sparse, MatrixFactorization._fit_generic, _als.fit, torch.cuda.is_available
+    MatrixFactorization._fit_sparse = lambda self, *a, **k: calls.append('engine') or True
+    MatrixFactorization._fit_generic = lambda self, *a, **k: calls.append('generic')
+    _als.fit = lambda model, epochs, n_users, n_items, inter, U0, V0, *a: calls.append('als') or (U0, V0)
+    out = {'fit': {}, 'als': {}}
+    try:
+        for gpu in (False, True):
+            torch.cuda.is_available = lambda gpu=gpu: gpu
+            for name, loss in losses.items():
+                out['fit'][f'{name} gpu={gpu}'] = [
+                    outcome(lambda: model(loss, ug, ig, combo).fit(1, uf, itf, interactions))
+                    for ug, uf, _ in sides for ig, _, itf in sides for combo in route_setting_combos()]
+            out['als'][f'gpu={gpu}'] = [
+                outcome(lambda: model(L.MSELoss, ug, ig, combo).fit_als(1, uf, itf, interactions))
+                for ug, uf, _ in sides for ig, _, itf in sides for combo in [()] + [(s,) for s in ROUTE_ALS_SETTINGS]]
+    finally:
+        MatrixFactorization._fit_sparse, MatrixFactorization._fit_generic, _als.fit, torch.cuda.is_available = kept
+    return out
+
+
+def fit_routes():
+    """Writes fit_routes.json, the record of what the PARENT of the commit that introduced the route table did.  It must be run in
+    a worktree of that parent, with this file copied into it (``python tests/golden/make_golden.py fit_routes``), and is never
+    regenerated from a later tree: tests/test_fit_routes_cpu.py replays it against the code under test.  Every distinct outcome
+    text is stored once; a row is one character: string.ascii_letters[index of its outcome]."""
+    import json
+    got = fit_route_outcomes()
+    texts = sorted({o for part in got.values() for rows in part.values() for o in rows}, key=lambda o: (':' in o, o))
+    letter = dict(zip(texts, string.ascii_letters[:len(texts)], strict=True))
+    doc = dict(losses=ROUTE_LOSSES, sides=ROUTE_SIDES, settings=[list(s) for s in ROUTE_SETTINGS],
+               als_settings=[list(s) for s in ROUTE_ALS_SETTINGS], outcomes=texts,
+               **{kind: {key: ''.join(letter[o] for o in rows) for key, rows in part.items()} for kind, part in got.items()})
+    path = os.path.join(HERE, 'fit_routes.json')
+    with open(path, 'w') as f:
+        json.dump(doc, f, indent=1)
+        f.write('\n')
+    rows = [o for part in got.values() for r in part.values() for o in r]
+    print(f'fit_routes: {len(rows)} rows, {len(texts)} outcomes, {os.path.getsize(path) / 1024:.1f} KiB; '
+          + ', '.join(f'{rows.count(o)} {o[:40]}' for o in texts[:3]))
+
+
 if __name__ == '__main__':
+    if sys.argv[1:] == ['fit_routes']:
+        sys.exit(fit_routes())
     plugins()
     gather_known_answer()
     c1_mse()

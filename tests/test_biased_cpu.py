@@ -203,18 +203,18 @@ def test_dispatch_without_a_gpu_stays_generic(monkeypatch):
             setattr(mf, k, v)
         return mf
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
-    assert not model()._on_fast_path(eye(6), eye(7))
-    assert not model(i=LinearEmbedding)._on_fast_path(eye(6), eye(7)) and not model(u=LinearEmbedding)._on_fast_path(eye(6), eye(7))
-    assert model(LinearEmbedding, LinearEmbedding)._on_fast_path(eye(6), eye(7))
+    assert model()._route(eye(6), eye(7)) == 'generic'
+    assert model(i=LinearEmbedding)._route(eye(6), eye(7)) == 'generic' and model(u=LinearEmbedding)._route(eye(6), eye(7)) == 'generic'
+    assert model(LinearEmbedding, LinearEmbedding)._route(eye(6), eye(7)) == 'engine'
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: True)
     for loss in (None, WMRBLoss(), KLDivergenceLoss()):
-        assert model(loss=loss)._on_fast_path(eye(6), eye(7))
-        assert model(i=LinearEmbedding, loss=loss)._on_fast_path(eye(6), eye(7))
-        assert model(u=LinearEmbedding, loss=loss)._on_fast_path(eye(6), eye(7))
+        assert model(loss=loss)._route(eye(6), eye(7)) == 'engine'
+        assert model(i=LinearEmbedding, loss=loss)._route(eye(6), eye(7)) == 'engine'
+        assert model(u=LinearEmbedding, loss=loss)._route(eye(6), eye(7)) == 'engine'
     dense = lambda k: torch.eye(k) + 0.05   # noqa: E731  (a dense identity matrix would count as an indicator)
-    assert not model()._on_fast_path(dense(6), eye(7)) and not model()._on_fast_path(eye(6), dense(7))
-    assert not model(u=Mine)._on_fast_path(eye(6), eye(7)) and not model(i=ReLUEmbedding)._on_fast_path(eye(6), eye(7))
+    assert model()._route(dense(6), eye(7)) == 'generic' and model()._route(eye(6), dense(7)) == 'generic'
+    assert model(u=Mine)._route(eye(6), eye(7)) == 'generic' and model(i=ReLUEmbedding)._route(eye(6), eye(7)) == 'generic'
     for name, value in (('batch_users', 8), ('shard_items', 2), ('data_parallel', 'force'), ('factor_dtype', torch.bfloat16),
                         ('optimizer', 'adam')):
-        assert not model(**{name: value})._on_fast_path(eye(6), eye(7)), name
-        assert model(LinearEmbedding, LinearEmbedding, **{name: value})._on_fast_path(eye(6), eye(7)), name
+        assert model(**{name: value})._route(eye(6), eye(7)) == 'generic', name
+        assert model(LinearEmbedding, LinearEmbedding, **{name: value})._route(eye(6), eye(7)) == 'engine', name

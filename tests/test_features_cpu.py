@@ -233,26 +233,27 @@ def test_dispatch_predicate(monkeypatch):
             setattr(mf, k, v)
         return mf
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
-    assert not model()._on_fast_path(F6, eye(7)) and not model()._on_fast_path(eye(6), F7) and not model()._on_fast_path(F6, F7)
-    assert model()._on_fast_path(eye(6), eye(7))
+    assert model()._route(F6, eye(7)) == 'generic' and model()._route(eye(6), F7) == 'generic' and model()._route(F6, F7) == 'generic'
+    assert model()._route(eye(6), eye(7)) == 'engine'
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: True)
     for loss in (None, WMRBLoss(), KLDivergenceLoss()):
-        assert model(loss=loss)._on_fast_path(F6, eye(7)) and model(loss=loss)._on_fast_path(eye(6), F7)
-        assert model(loss=loss)._on_fast_path(F6, F7)
-        assert model(u=BiasedLinearEmbedding, loss=loss)._on_fast_path(eye(6), F7)      # a biased indicator side beside a featured one
-    assert not model(loss=MyLoss())._on_fast_path(F6, F7)
+        assert model(loss=loss)._route(F6, eye(7)) == 'engine' and model(loss=loss)._route(eye(6), F7) == 'engine'
+        assert model(loss=loss)._route(F6, F7) == 'engine'
+        assert model(u=BiasedLinearEmbedding, loss=loss)._route(eye(6), F7) == 'engine'      # a biased indicator side beside a featured one
+    assert model(loss=MyLoss())._route(F6, F7) == 'generic'
     for kind in (BiasedLinearEmbedding, ReLUEmbedding, Mine):
-        assert not model(u=kind)._on_fast_path(F6, eye(7)) and not model(i=kind)._on_fast_path(eye(6), F7), kind
-    assert not model()._on_fast_path(none, eye(7))                                      # nothing to multiply: the generic zeros
+        assert model(u=kind)._route(F6, eye(7)) == 'generic' and model(i=kind)._route(eye(6), F7) == 'generic', kind
+    assert model()._route(none, eye(7)) == 'generic'                                      # nothing to multiply: the generic zeros
     for name, value in (('batch_users', 8), ('shard_items', 2), ('data_parallel', 'force'), ('factor_dtype', torch.bfloat16),
                         ('optimizer', 'adam')):
-        assert not model(**{name: value})._on_fast_path(F6, eye(7)), name
-        assert not model(**{name: value})._on_fast_path(eye(6), F7), name
-        assert model(**{name: value})._on_fast_path(eye(6), eye(7)), name
-        assert model(**{name: value})._biased_engine_allowed() == model(**{name: value})._sided_engine_allowed() is False
+        assert model(**{name: value})._route(F6, eye(7)) == 'generic', name
+        assert model(**{name: value})._route(eye(6), F7) == 'generic', name
+        assert model(**{name: value})._route(eye(6), eye(7)) == 'engine', name
+        assert (model(u=BiasedLinearEmbedding, **{name: value})._route(eye(6), eye(7))
+                == model(**{name: value})._route(F6, eye(7)) == 'generic'), name   # one row of ROUTES for both
     # dense and torch-sparse inputs keep the generic path, as before
     dense = torch.eye(6)[:, :3].contiguous()
-    assert not model()._on_fast_path(dense, eye(7)) and not model()._on_fast_path(dense.to_sparse(), eye(7))
+    assert model()._route(dense, eye(7)) == 'generic' and model()._route(dense.to_sparse(), eye(7)) == 'generic'
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -54,7 +54,7 @@ def test_dense_features_match_the_dense_oracle(ns, loss):
     if loss == 'wmrb':
         model.random_ind = torch.as_tensor(R)
     model.fit(8, torch.tensor(Fu), torch.tensor(Fv), ns.Sparse(idx, val, (m, n)), lr=0.05)
-    assert model.user_embedding.is_cuda and not model._on_fast_path(torch.tensor(Fu), torch.tensor(Fv))
+    assert model.user_embedding.is_cuda and model._route(torch.tensor(Fu), torch.tensor(Fv)) == 'generic'
     ref = D.fit_dense(U0, V0, idx, val, loss, 8, 0.05, random_ind=R, n_items=n, n_samples=R.shape[1], user_features=Fu,
                       item_features=Fv)
     assert rel_err(model.loss_history_[:3], ref['loss'][:3]) < 1e-5 and rel_err(model.loss_history_, ref['loss']) < 1e-3

@@ -127,12 +127,11 @@ def test_dispatch_without_a_gpu_stays_generic(monkeypatch):
     from teamoflow_amd.mf.matrix_factorization import MatrixFactorization
     from teamoflow_amd.mf.sparse import eye
     model = MatrixFactorization(4, loss_graph=KLDivergenceLoss())
-    assert model._on_fast_path(eye(6), eye(7))
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
-    assert not model._kl_engine_allowed()
+    assert model._route(eye(6), eye(7)) == 'generic'
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: True)
-    assert model._kl_engine_allowed()
+    assert model._route(eye(6), eye(7)) == 'engine'
     for name, value in (('batch_users', 8), ('shard_items', 2), ('data_parallel', 'force')):
         other = MatrixFactorization(4, loss_graph=KLDivergenceLoss())
         setattr(other, name, value)
-        assert not other._kl_engine_allowed(), name
+        assert other._route(eye(6), eye(7)) == 'generic', name

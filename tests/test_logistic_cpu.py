@@ -201,22 +201,17 @@ def test_dispatch(monkeypatch):
     inter = SparseInteractions(p['idx'], p['val'], (12, 9), device='cpu')
     forms = (('batch_users', 8), ('shard_items', 2), ('data_parallel', 'force'), ('factor_dtype', torch.bfloat16), ('optimizer', 'adam'))
 
-    def engine(model, uf=None, vf=None):   # fit()'s own condition
-        kl = type(model.loss_graph).__name__ == 'KLDivergenceLoss'
-        return (model._on_fast_path(eye(12) if uf is None else uf, eye(9) if vf is None else vf)
-                and (not kl or model._kl_engine_allowed()) and model._logistic_engine_allowed())
-
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: True)
     for loss in (LogisticLoss(), LogisticLoss(weighted=True)):
-        assert engine(_model(p, loss=loss))
+        assert _model(p, loss=loss)._route(eye(12), eye(9)) == 'engine'
         for name, value in forms:
-            assert engine(_model(p, loss=loss, **{name: value})), name
-    assert not engine(_model(p, loss=MyLogistic()))
-    assert not engine(_model(p), uf=torch.eye(12)[:, :5].contiguous())                       # dense features
-    assert not engine(_model(p, user_repr_graph=ReLUEmbedding()))
+            assert _model(p, loss=loss, **{name: value})._route(eye(12), eye(9)) == 'engine', name
+    assert _model(p, loss=MyLogistic())._route(eye(12), eye(9)) == 'generic'
+    assert _model(p)._route(torch.eye(12)[:, :5].contiguous(), eye(9)) == 'generic'          # dense features
+    assert _model(p, user_repr_graph=ReLUEmbedding())._route(eye(12), eye(9)) == 'generic'
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
     for loss in (LogisticLoss(), LogisticLoss(weighted=True), MyLogistic()):
-        assert not engine(_model(p, loss=loss))
+        assert _model(p, loss=loss)._route(eye(12), eye(9)) == 'generic'
     # and fit() itself, where it can run here: without a GPU everything goes to _fit_generic
     calls = []
     monkeypatch.setattr(MatrixFactorization, '_fit_sparse', lambda self, *a, **k: calls.append('engine') or True)

@@ -129,31 +129,31 @@ def test_dispatch_predicate(monkeypatch):
     feats = ((eye(6), eye(7)), (F6, eye(7)), (F6, F7))
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: True)
     for uf, vf in feats:
-        assert not model()._on_fast_path(uf, vf)                                        # the default: generic, as before
-        assert not model(relu_engine=False)._on_fast_path(uf, vf)
+        assert model()._route(uf, vf) == 'generic'                                        # the default: generic, as before
+        assert model(relu_engine=False)._route(uf, vf) == 'generic'
     for loss in (None, WMRBLoss(), KLDivergenceLoss(), LogisticLoss()):
         for uf, vf in feats:
-            assert model(loss=loss, relu_engine=True)._on_fast_path(uf, vf)
-            assert model(u=LinearEmbedding, i=ReLUEmbedding, loss=loss, relu_engine=True)._on_fast_path(uf, vf)
-            assert model(i=ReLUEmbedding, loss=loss, relu_engine=True)._on_fast_path(uf, vf)
-        assert model(i=BiasedLinearEmbedding, loss=loss, relu_engine=True)._on_fast_path(F6, eye(7))   # beside a biased side
-    assert not model(u=Mine, relu_engine=True)._on_fast_path(eye(6), eye(7))            # exactly ReLUEmbedding
-    assert not model(u=LinearEmbedding, i=Mine, relu_engine=True)._on_fast_path(eye(6), eye(7))
-    assert not model(loss=MyLoss(), relu_engine=True)._on_fast_path(eye(6), eye(7))     # one of the four built-in losses
-    assert not model(relu_engine=True)._on_fast_path(none, eye(7))                      # SparseFeatures with entries
+            assert model(loss=loss, relu_engine=True)._route(uf, vf) == 'engine'
+            assert model(u=LinearEmbedding, i=ReLUEmbedding, loss=loss, relu_engine=True)._route(uf, vf) == 'engine'
+            assert model(i=ReLUEmbedding, loss=loss, relu_engine=True)._route(uf, vf) == 'engine'
+        assert model(i=BiasedLinearEmbedding, loss=loss, relu_engine=True)._route(F6, eye(7)) == 'engine'   # beside a biased side
+    assert model(u=Mine, relu_engine=True)._route(eye(6), eye(7)) == 'generic'            # exactly ReLUEmbedding
+    assert model(u=LinearEmbedding, i=Mine, relu_engine=True)._route(eye(6), eye(7)) == 'generic'
+    assert model(loss=MyLoss(), relu_engine=True)._route(eye(6), eye(7)) == 'generic'     # one of the four built-in losses
+    assert model(relu_engine=True)._route(none, eye(7)) == 'generic'                      # SparseFeatures with entries
     dense = torch.eye(6)[:, :3].contiguous()
-    assert not model(relu_engine=True)._on_fast_path(dense, eye(7)) and not model(relu_engine=True)._on_fast_path(dense.to_sparse(), eye(7))
-    assert model(r=204, relu_engine=True)._on_fast_path(eye(6), eye(7))                 # 5 r <= 1024
-    assert not model(r=205, relu_engine=True)._on_fast_path(eye(6), eye(7))
-    assert model(u=LinearEmbedding, r=205, relu_engine=True)._on_fast_path(eye(6), eye(7))
+    assert model(relu_engine=True)._route(dense, eye(7)) == 'generic' and model(relu_engine=True)._route(dense.to_sparse(), eye(7)) == 'generic'
+    assert model(r=204, relu_engine=True)._route(eye(6), eye(7)) == 'engine'                 # 5 r <= 1024
+    assert model(r=205, relu_engine=True)._route(eye(6), eye(7)) == 'generic'
+    assert model(u=LinearEmbedding, r=205, relu_engine=True)._route(eye(6), eye(7)) == 'engine'
     for name, value in (('batch_users', 8), ('shard_items', 2), ('data_parallel', 'force'), ('factor_dtype', torch.bfloat16),
-                        ('optimizer', 'adam')):                                         # _sided_engine_allowed
+                        ('optimizer', 'adam')):                                         # the 'side' row of ROUTES
         for uf, vf in feats:
-            assert not model(relu_engine=True, **{name: value})._on_fast_path(uf, vf), name
-        assert model(u=LinearEmbedding, relu_engine=True, **{name: value})._on_fast_path(eye(6), eye(7)), name
+            assert model(relu_engine=True, **{name: value})._route(uf, vf) == 'generic', name
+        assert model(u=LinearEmbedding, relu_engine=True, **{name: value})._route(eye(6), eye(7)) == 'engine', name
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
     for uf, vf in feats:
-        assert not model(relu_engine=True)._on_fast_path(uf, vf)
+        assert model(relu_engine=True)._route(uf, vf) == 'generic'
 
 
 @pytest.mark.parametrize('relu_engine', [False, True])

@@ -547,14 +547,12 @@ def test_loss_name_and_dispatch(monkeypatch):
     with pytest.raises(TypeError, match='WARPLoss'):
         _engine.loss_name(MyWARP())
     p = warp_problem(16, 12, 9, 4, 4)
-
-    def engine(model):   # fit()'s own condition
-        return model._on_fast_path(eye(12), eye(9)) and model._logistic_engine_allowed() and model._bpr_engine_allowed()
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: True)
-    assert engine(_model(p)) and engine(_model(p, factor_dtype=torch.bfloat16)) and engine(_model(p, optimizer='adam'))
-    assert not engine(_model(p, loss=MyWARP()))
+    for settings in ({}, dict(factor_dtype=torch.bfloat16), dict(optimizer='adam')):
+        assert _model(p, **settings)._route(eye(12), eye(9)) == 'engine', settings
+    assert _model(p, loss=MyWARP())._route(eye(12), eye(9)) == 'generic'
     monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
-    assert not engine(_model(p))
+    assert _model(p)._route(eye(12), eye(9)) == 'generic'
 
 
 def test_a_warp_epoch_needs_a_sliced_plan():

@@ -168,7 +168,7 @@ def child_ml1m(args):
                                     user_weight_graph=FixedInitializer(U0), item_weight_graph=FixedInitializer(V0))
         model.verbose, model.random_ind = False, R
         if name == 'generic':
-            model._biased_engine_allowed = lambda: False
+            model._route = lambda user_features, item_features: 'generic'
         model.fit(epochs, eye(m), eye(n), SparseInteractions(idx, val, (m, n)), lr=0.1)
         torch.cuda.synchronize()
         res[name + '_ms_per_epoch'] = 1e3 * model.fit_seconds_ / epochs

@@ -121,7 +121,7 @@ def child_c2(args):
         model = MatrixFactorization(r, user_weight_graph=FixedInitializer(U0), item_weight_graph=FixedInitializer(V0))
         model.verbose = False
         if name == 'generic':
-            model._sided_engine_allowed = lambda: False
+            model._route = lambda user_features, item_features: 'generic'
         model.fit(epochs, Fu, Fv, SparseInteractions(idx, val, (m, n)), lr=0.01)
         torch.cuda.synchronize()
         assert hasattr(model, '_state') == (name == 'engine')
