@@ -374,6 +374,19 @@ int tmf_warp_pairs(const int64_t* rowptr, const float* val, const float* p, cons
 int tmf_warp_pairs_ranked(const int64_t* rowptr, const float* val, const float* p, const float* sp, const uint16_t* rank,
                           int32_t n_users, int32_t n_samples, int32_t n_items, float* delta, float* D, float* loss_part,
                           const int32_t* user_order, void* stream);
+/* SampledSoftmaxLoss (an extension) in the same place, the arguments of tmf_wmrb_hinge2_ordered in their layout: for the stored
+ * values > 0 of user u, with M = max_s sp[u, s], e_s = exp(sp[u, s] - M), Z = sum_s e_s, m = max(p[k], M), t = exp(M - m),
+ * b = c Z t and den = exp(p[k] - m) + b:  loss_k = log(den) + (m - p[k]) = -log(exp(p[k]) / (exp(p[k]) + c sum_s exp(sp[u, s]))),
+ * delta[k] = -b / den (0 for a stored value <= 0),  D[u, s] = e_s sum_k c t / den,  loss_part[u] = sum_k loss_k; the epoch's loss
+ * is the sum of loss_part over the number of positives.  c = 1, or n_items / n_samples for the uniform-sampling estimate of the
+ * full-catalog partition.  sp and D may keep a user's samples in any order: the loss does not depend on it.  Every element of
+ * delta [nnz], D [n_users, n_samples] and loss_part [n_users] is overwritten, whatever the buffers held; a user without a value
+ * > 0 gets zeros.  Reads no table; one exponential per (user, sample) and two per positive, rows of any length >= 1 (the first 1024
+ * samples of a row stay in registers between the read and the write).  n_users = 0 is legal, and so are NULL val / p / delta for a
+ * table without interactions.  No atomics; the outputs are bit-identical from run to run and do not depend on user_order (speed
+ * only: heavy users first).  Finite for every finite score; a NaN or an infinity stays inside its user. */
+int tmf_softmax_pairs(const int64_t* rowptr, const float* val, const float* p, const float* sp, int32_t n_users, int32_t n_samples,
+                      float c, float* delta, float* D, float* loss_part, const int32_t* user_order, void* stream);
 int tmf_wmrb_gradu3_f32(const tmf_slice_lists* lists, const float* D, const float* delta, const void* V, float* part,
                         int per_slice_launches, int n_components, void* stream);
 int tmf_wmrb_gradu3_bf16(const tmf_slice_lists* lists, const float* D, const float* delta, const void* V, float* part,

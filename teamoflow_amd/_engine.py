@@ -9,6 +9,7 @@ What replaces what (reference paths under /root/reference/src/teamoflow/mf/):
   epoch_logistic: LogisticLoss (mf/loss_graphs.py; an extension - the reference has no such loss)
   epoch_wmrb(pairs='bpr'): BPRLoss (mf/loss_graphs.py; an extension): the WMRB epoch with tmf_bpr_pairs in the hinge kernel's place
   epoch_wmrb(pairs='warp'): WARPLoss (mf/loss_graphs.py; an extension): the same epoch with tmf_warp_pairs there
+  epoch_wmrb(pairs='softmax'): SampledSoftmaxLoss (mf/loss_graphs.py; an extension): the same epoch with tmf_softmax_pairs there
   epoch_sides <- the same loop with plug-in sides: any loss above, then the step of every side that is an object (TrainState.sides:
                  PlainL2Side, BiasSide, FeatureSide, ReLUSide <- embedding_graphs.py:30-87)
 """
@@ -1352,21 +1353,23 @@ def _timed(prof, name, call):
 LOGISTIC_LOSSES = ('logistic', 'logistic_w')   # LogisticLoss(weighted=False) / LogisticLoss(weighted=True)
 
 
-PAIR_LOSSES = ('wmrb', 'bpr', 'warp')   # the losses over the static negative table: WmrbPlan, sp / p / delta / D, denominator n_pos
+SLICED_ONLY = ('bpr', 'warp', 'softmax')   # pair steps of the sliced user pass alone: the one-kernel pass has the hinge built in
+PAIR_LOSSES = ('wmrb', 'bpr', 'warp', 'softmax')   # the losses over the static negative table: WmrbPlan, sp / p / delta / D, denominator n_pos
 
 
 def loss_name(loss_graph):
-    """The name run_epoch knows the loss of a fit by: 'mse', 'wmrb', 'kl', 'bpr', 'warp', 'logistic' or 'logistic_w' for exactly the
-    six built-in loss classes (not their subclasses: what a subclass computes is its own business, and the generic path's).  Anything
+    """The name run_epoch knows the loss of a fit by: 'mse', 'wmrb', 'kl', 'bpr', 'warp', 'softmax', 'logistic' or 'logistic_w' for exactly
+    the seven built-in loss classes (not their subclasses: what a subclass computes is its own business, and the generic path's).  Anything
     else raises - no loss trains as another one because a chain of isinstance tests fell through."""
     from .mf import loss_graphs as L
     kind = type(loss_graph)
     if kind is L.LogisticLoss:
         return 'logistic_w' if loss_graph.weighted else 'logistic'
-    names = {L.MSELoss: 'mse', L.WMRBLoss: 'wmrb', L.KLDivergenceLoss: 'kl', L.BPRLoss: 'bpr', L.WARPLoss: 'warp'}
+    names = {L.MSELoss: 'mse', L.WMRBLoss: 'wmrb', L.KLDivergenceLoss: 'kl', L.BPRLoss: 'bpr', L.WARPLoss: 'warp',
+             L.SampledSoftmaxLoss: 'softmax'}
     if kind not in names:
         raise TypeError(f'{kind.__name__} is not a loss the HIP engine trains (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, '
-                        f'BPRLoss, WARPLoss)')
+                        f'BPRLoss, WARPLoss, SampledSoftmaxLoss)')
     return names[kind]
 
 
@@ -1397,14 +1400,15 @@ def checked_negatives(random_ind, n_rows, n_items, device, rows=None):
 
 def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM,
               user_out=None):
-    """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'bpr', 'warp', 'kl', 'logistic', 'logistic_w' or 'mse' - on the
-    state's tables: the ONE place that maps a loss to its epoch.  The other arguments as in epoch_mse.
-    'bpr' and 'warp' are epochs only of a state whose WmrbPlan is sliced (wmrb_plan_for(force_sliced=True)): the one-kernel user pass has the
-    hinge built in.  On any other state it is refused like a name nobody knows - never run as WMRB."""
+    """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'bpr', 'warp', 'softmax' (c = 1 or n_items / n_samples), 'kl',
+    'logistic', 'logistic_w' or 'mse' - on the state's tables: the ONE place that maps a loss to its epoch.  The other arguments as
+    in epoch_mse.  'bpr', 'warp' and 'softmax' are epochs only of a state whose WmrbPlan is sliced (wmrb_plan_for(force_sliced=True)):
+    the one-kernel user pass has the hinge built in.  On any other state they are refused like a name nobody knows - never run as
+    WMRB."""
     if loss == 'wmrb':
         epoch_wmrb(st, adam, c, loss_out, item_epi, item_out, prof, user_epi, user_out)
-    elif loss in ('bpr', 'warp') and getattr(getattr(st, 'wplan', None), 'sliced', False):
-        epoch_wmrb(st, adam, 0.0, loss_out, item_epi, item_out, prof, user_epi, user_out, pairs=loss)
+    elif loss in SLICED_ONLY and getattr(getattr(st, 'wplan', None), 'sliced', False):
+        epoch_wmrb(st, adam, c if loss == 'softmax' else 0.0, loss_out, item_epi, item_out, prof, user_epi, user_out, pairs=loss)
     elif loss == 'kl':
         epoch_kl(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
     elif loss in LOGISTIC_LOSSES:
@@ -1412,7 +1416,7 @@ def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=
     elif loss == 'mse':
         epoch_mse(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
     else:
-        raise ValueError(f'run_epoch: unknown loss {loss!r}' + (' on a state without a sliced WmrbPlan' if loss in ('bpr', 'warp') else ''))
+        raise ValueError(f'run_epoch: unknown loss {loss!r}' + (' on a state without a sliced WmrbPlan' if loss in SLICED_ONLY else ''))
 
 
 def _row_pass_finish(lib, seg, slab, X_old, X_out, r, epi, adam, stream, sfx='_f32'):
@@ -1475,7 +1479,9 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
     pairs='bpr': tmf_bpr_pairs (csrc/tmf_bpr.hip) in the hinge kernel's place - same arguments but c, same layout of delta and D.
     pairs='warp': tmf_warp_pairs_ranked (csrc/tmf_warp.hip) there - those arguments, the plan's n_items (the weight's rank
     estimate) and WmrbPlan.sample_rank(): the one loss here that depends on the order of a user's samples tries them in the model's
-    table order, whatever order the plan keeps them in."""
+    table order, whatever order the plan keeps them in.
+    pairs='softmax': tmf_softmax_pairs (csrc/tmf_softmax.hip) there - the hinge kernel's arguments, c = 1 or n_items / n_samples; the
+    loss does not depend on the order of a user's samples, so it takes sp and D as the plan keeps them."""
     p, w, r = st.plan, st.wplan, st.r
     i32 = ctypes.c_int32
     m, S, ns = p.n_users, w.S, w.n_slices
@@ -1512,6 +1518,10 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
                                                                      _lib.ptr(st.sp), _lib.ptr(rank), i32(m), i32(S), i32(p.n_items),
                                                                      _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part),
                                                                      _lib.ptr(w.hinge_order), s))
+    elif pairs == 'softmax':
+        _timed(prof, 'softmax_pairs', lambda: lib.tmf_softmax_pairs(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk), _lib.ptr(st.sp),
+                                                                    i32(m), i32(S), c, _lib.ptr(w.delta), _lib.ptr(w.D),
+                                                                    _lib.ptr(st.loss_part), _lib.ptr(w.hinge_order), s))
     else:
         _timed(prof, 'wmrb_hinge', lambda: lib.tmf_wmrb_hinge2_ordered(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk), _lib.ptr(st.sp),
                                                                 i32(m), i32(S), c, _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part),
@@ -1536,9 +1546,11 @@ def epoch_wmrb(st, adam, c, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, pro
     pairs='bpr': one BPRLoss epoch - the same scores, gathers and item pass around tmf_bpr_pairs (c is unused); loss_out receives
     sum over positives of mean_s softplus(sp[u, s] - p_k).  Only on a sliced plan.
     pairs='warp': one WARPLoss epoch in the same way around tmf_warp_pairs; loss_out receives sum over positives of
-    w_k (1 - p_k + sp[u, s*_k]).  Only on a sliced plan."""
-    if pairs not in ('hinge', 'bpr', 'warp'):
-        raise ValueError(f'epoch_wmrb: pairs={pairs!r} (hinge, bpr or warp)')
+    w_k (1 - p_k + sp[u, s*_k]).  Only on a sliced plan.
+    pairs='softmax': one SampledSoftmaxLoss epoch in the same way around tmf_softmax_pairs (c = 1, or n_items / n_samples); loss_out
+    receives sum over positives of -log(exp(p_k) / (exp(p_k) + c sum_s exp(sp[u, s]))).  Only on a sliced plan."""
+    if pairs not in ('hinge',) + SLICED_ONLY:
+        raise ValueError(f'epoch_wmrb: pairs={pairs!r} (hinge, bpr, warp or softmax)')
     if pairs != 'hinge' and not st.wplan.sliced:
         raise ValueError(f'epoch_wmrb: pairs={pairs} needs the sliced user pass (wmrb_plan_for(force_sliced=True))')
     lib, p, w, r = _lib.get(), st.plan, st.wplan, st.r

@@ -110,6 +110,7 @@ _BASE_SIGNATURES = {
     'tmf_bpr_pairs': (_I, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
     'tmf_warp_pairs': (_I, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     'tmf_warp_pairs_ranked': (_I, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    'tmf_softmax_pairs': (_I, [_P, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P, _P]),
     'tmf_wmrb_gradu3_f32': (_I, [_SL, _P, _P, _P, _P, _I, _I, _P]),
     'tmf_wmrb_gradu4_supported': (_I, [_I, _I]),
     'tmf_wmrb_gradu4_workspace_bytes': (_SZ, [_I32, _I32, _I32]),

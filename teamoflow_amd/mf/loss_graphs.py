@@ -1,12 +1,13 @@
 """Loss graphs (plug-in interface of /root/reference/src/teamoflow/mf/loss_graphs.py).
 
-``MSELoss``, ``WMRBLoss``, ``KLDivergenceLoss``, ``LogisticLoss``, ``BPRLoss`` and ``WARPLoss`` (extensions: the reference has no
-logistic loss, pointwise or pairwise, and no first-violator ranking loss) with ``LinearEmbedding`` over indicator features are recognised by
+``MSELoss``, ``WMRBLoss``, ``KLDivergenceLoss``, ``LogisticLoss``, ``BPRLoss``, ``WARPLoss`` and ``SampledSoftmaxLoss`` (extensions: the
+reference has no logistic loss, pointwise or pairwise, no first-violator ranking loss and no softmax) with ``LinearEmbedding`` over indicator features are recognised by
 ``MatrixFactorization.fit`` (same isinstance dispatch as matrix_factorization.py:152-162) and run as
 fused HIP kernels; ``get_loss`` below is the generic differentiable definition used when the model is
 built from other plug-ins (dense features, custom embeddings), always called by keyword like
 matrix_factorization.py:165-167 does.
 """
+import math
 from abc import ABC, abstractmethod
 
 import torch
@@ -130,3 +131,27 @@ class WARPLoss(LossGraph):
             w = torch.where(found, torch.log(rank.to(pos.dtype)), torch.zeros_like(pos))
         margin = 1.0 - pos + sp.gather(1, first[:, None])[:, 0]
         return torch.where(w > 0.0, w * margin, torch.zeros_like(pos))
+
+
+class SampledSoftmaxLoss(LossGraph):
+    """Extension (the sampled softmax of retrieval models; not in the reference): the softmax of a positive against the user's row of
+    the static negative table WMRBLoss samples from.  For every stored interaction k of user u with a value > 0 and score p_k, against
+    the user's row sp[u, :] of sampled scores:
+
+        loss_k = -log( exp(p_k) / (exp(p_k) + c sum_s exp(sp[u, s])) )        c = 1, or n_items / n_samples with ``catalog_scale``
+
+    With ``catalog_scale`` c is the constant WMRBLoss uses: the uniform-sampling correction that makes the sum an estimate of the
+    full-catalog partition.  d loss_k / d p_k = -(1 - q_k) and d loss_k / d sp[u, s] = c exp(sp[u, s]) / (exp(p_k) + c sum_s' exp(sp[u, s']))
+    with q_k the probability inside the logarithm: every sample pulls, the higher it scores the harder.  Stored values <= 0 take
+    no part and a negative that coincides with one of the user's positives is not filtered (both as in WMRBLoss)."""
+
+    def __init__(self, catalog_scale=False):
+        self.catalog_scale = bool(catalog_scale)
+
+    def get_loss(self, tf_interactions, tf_sample_predictions, tf_prediction_serial, n_items, n_samples, predictions=None):
+        mask = tf_interactions.values > 0.0
+        users = tf_interactions.indices[:, 0][mask]
+        pos = tf_prediction_serial[mask]
+        log_c = math.log(n_items / n_samples) if self.catalog_scale else 0.0
+        partition = torch.logsumexp(tf_sample_predictions, dim=1)[users] + log_c     # log(c sum_s exp(sp[u, s])), per positive
+        return torch.logaddexp(pos, partition) - pos

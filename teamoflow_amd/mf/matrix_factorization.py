@@ -3,7 +3,7 @@
 
 Dispatch (``MatrixFactorization._route``; same isinstance test the reference uses at :115,:136-162): a model made of
 (``LinearEmbedding`` | ``BiasedLinearEmbedding``) x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss`` |
-``LogisticLoss`` | ``BPRLoss`` | ``WARPLoss``) - or ``LinearEmbedding`` over ``SparseFeatures`` on either side, or with ``relu_engine = True``
+``LogisticLoss`` | ``BPRLoss`` | ``WARPLoss`` | ``SampledSoftmaxLoss``) - or ``LinearEmbedding`` over ``SparseFeatures`` on either side, or with ``relu_engine = True``
 (off by default) a ``ReLUEmbedding`` side over either - trains on the HIP engine (``_engine.py`` -> libtmf.so); for unbiased MSE / WMRB it
 needs a GPU - there is no CPU fallback for them.  Any other combination of plug-ins (dense features, ReLU embeddings, user subclasses)
 trains through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins' own ``get_repr`` /
@@ -25,7 +25,7 @@ import torch
 from .. import _als, _engine, _lib, _ops
 from .embedding_graphs import BiasedLinearEmbedding, Embeddings, LinearEmbedding, ReLUEmbedding
 from .initializer_graphs import NormalInitializer
-from .loss_graphs import BPRLoss, KLDivergenceLoss, LogisticLoss, LossGraph, MSELoss, WARPLoss, WMRBLoss
+from .loss_graphs import BPRLoss, KLDivergenceLoss, LogisticLoss, LossGraph, MSELoss, SampledSoftmaxLoss, WARPLoss, WMRBLoss
 from .sparse import IndicatorFeatures, SparseFeatures, SparseInteractions, default_device, is_indicator
 from .utils import gather_matrix_indices, random_sampler, random_sampler_device
 
@@ -37,7 +37,9 @@ GRAPH_MAX_WORK = 20_000_000    # interactions + sampled scores per epoch below w
 # What trains where (DESIGN.md prints this table; MatrixFactorization._route reads it).  A row is a feature of a fit, a column a
 # setting that leaves the single-GPU full-batch fp32 fresh-Adam fit: 'ok' = the engine has that form, 'generic' = fit() trains
 # through _fit_generic, 'refuse' = NotImplementedError before any weight is drawn or plan built.
-ENGINE_LOSSES = (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, BPRLoss, WARPLoss)   # exactly these types, no subclass
+ENGINE_LOSSES = (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, BPRLoss, WARPLoss, SampledSoftmaxLoss)   # exactly these types, no subclass
+TABLE_LOSSES = (WMRBLoss, BPRLoss, WARPLoss, SampledSoftmaxLoss)   # these and their subclasses read the static negative table
+PAIR_STEP_LOSSES = (BPRLoss, WARPLoss, SampledSoftmaxLoss)          # the route feature 'pair': a pair step of the sliced user pass
 _SETTINGS = {   # column -> (the attribute a refusal names, has the model left its default?), in the order refusals are met
     'relu_engine': ('relu_engine', lambda m: getattr(m, 'relu_engine', 0)     # counts beside a ReLUEmbedding side only
                     and ReLUEmbedding in (type(m.user_repr_graph), type(m.item_repr_graph))),
@@ -52,7 +54,7 @@ _SETTINGS = {   # column -> (the attribute a refusal names, has the model left i
 ROUTES = {feature: dict(zip(_SETTINGS, row.split(), strict=True)) for feature, row in {
     # feature     relu_engine  batch_users  shard_items  dp set   dp active  bf16     adam     no GPU
     'kl':        'ok           generic      generic      ok       generic    ok       ok       generic',   # KLDivergenceLoss
-    'pair':      'ok           refuse       refuse       refuse   refuse     ok       ok       generic',   # BPRLoss, WARPLoss
+    'pair':      'ok           refuse       refuse       refuse   refuse     ok       ok       generic',   # PAIR_STEP_LOSSES
     'logistic':  'ok           ok           ok           ok       ok         ok       ok       generic',   # LogisticLoss
     'side':      'ok           generic      generic      ok       generic    generic  generic  generic',   # biased, SparseFeatures, ReLU
     'l2':        'refuse       refuse       refuse       refuse   refuse     ok       ok       ok',        # user_alpha / item_alpha > 0
@@ -66,7 +68,7 @@ _BUILT = {'pair': 'only the single-GPU full-batch fit is built for this loss',
 
 
 class SampleTableMissing(AttributeError):
-    """WMRB, BPR and WARP need the static negative table: build the model with generate_sample=True
+    """WMRB, BPR, WARP and the sampled softmax need the static negative table: build the model with generate_sample=True
     (the reference fails with AttributeError inside gather_matrix_indices, matrix_factorization.py:153)."""
 
 
@@ -147,7 +149,7 @@ class MatrixFactorization:
         # interactions per row
         self.user_alpha = 0.0
         self.item_alpha = 0.0
-        # extension, OFF by default (the reference trains on ONE negative table): k > 0 = a fit of WMRBLoss, BPRLoss or WARPLoss trains
+        # extension, OFF by default (the reference trains on ONE negative table): k > 0 = a fit of one of the TABLE_LOSSES trains
         # epoch e on the table of round j = e // k - round 0 on random_ind as it stands, round j >= 1 on
         # _ops.sample_negatives(n_items, n_users, n_samples of random_ind, seed=sample_seed + j) (LightFM and implicit draw fresh
         # negatives every step).  random_ind itself is never changed, so every fit starts again from round 0.  Losses that read no
@@ -187,7 +189,7 @@ class MatrixFactorization:
         every setting is a form of theirs, and without a GPU they fail in _fit_sparse - there is no CPU fallback."""
         loss, kinds = type(self.loss_graph), (type(self.user_repr_graph), type(self.item_repr_graph))
         # the refusals, in the order a model that meets several has always met them
-        answers = [self._answer('pair', loss.__name__)] if loss in (BPRLoss, WARPLoss) else []
+        answers = [self._answer('pair', loss.__name__)] if loss in PAIR_STEP_LOSSES else []
         if any(self._alphas()):
             self._answer('l2', 'user_alpha / item_alpha > 0')
         every = self._resample_setting()[0]
@@ -238,7 +240,7 @@ class MatrixFactorization:
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or (name == 'resample_every' and v < 0):
                 raise ValueError(f'{name}={v!r}: an integer' + (' >= 0 (0 = never resample)' if name == 'resample_every' else ''))
             out.append(int(v))
-        if not isinstance(self.loss_graph, (WMRBLoss, BPRLoss, WARPLoss)):
+        if not isinstance(self.loss_graph, TABLE_LOSSES):
             return 0, out[1]
         return tuple(out)
 
@@ -419,9 +421,9 @@ class MatrixFactorization:
         return True
 
     def _sparse_state(self, loss, n_users, n_items, interactions, U0, V0, dev, user_feat=None, item_feat=None):
-        """(TrainState, c) of a single-GPU full-batch fit: the interaction plan, for WMRB, BPR and WARP the checked negative table and its
-        plan (BPR, WARP: always the sliced user pass), for WMRB c = n_items / n_samples, and the starting bias of a BiasedLinearEmbedding
-        side.  (None, 0.0) for KL with an empty class."""
+        """(TrainState, c) of a single-GPU full-batch fit: the interaction plan, for the table losses the checked negative table and its
+        plan (BPR, WARP, softmax: always the sliced user pass), for WMRB c = n_items / n_samples (for the softmax that or 1), and the
+        starting bias of a BiasedLinearEmbedding side.  (None, 0.0) for KL with an empty class."""
         wmrb, kl = loss in _engine.PAIR_LOSSES, loss == 'kl'
         plan = _engine.InteractionPlan(interactions.indices, interactions.values, n_users, n_items,
                                        user_chunks=1 if wmrb else _engine.mse_user_chunks(), csc=not wmrb)
@@ -430,8 +432,10 @@ class MatrixFactorization:
         wplan, c = None, 0.0
         if wmrb:
             R = _engine.checked_negatives(self.random_ind, n_users, n_items, dev)
-            if loss == 'wmrb':
+            if loss == 'wmrb' or (loss == 'softmax' and self.loss_graph.catalog_scale):
                 c = self.n_items / self.n_samples  # constructor ints, true division (:167)
+            elif loss == 'softmax':
+                c = 1.0
             wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype, force_sliced=loss != 'wmrb')
             if loss == 'warp':
                 wplan.sample_rank()   # WARP tries the samples in the table's order: built here, before any epoch is captured
@@ -576,7 +580,7 @@ class MatrixFactorization:
         random_ind = None if self.random_ind is None else torch.as_tensor(self.random_ind).to(dev)
         user_alpha, item_alpha = self._alphas()
         every = self._resample_setting()[0]
-        self.resample_rounds_ = int(isinstance(self.loss_graph, (WMRBLoss, BPRLoss, WARPLoss)) and random_ind is not None)
+        self.resample_rounds_ = int(isinstance(self.loss_graph, TABLE_LOSSES) and random_ind is not None)
         for epoch in range(epochs):
             start = timeit.default_timer()
             if every and epoch and epoch % every == 0 and random_ind is not None:   # round epoch // every: its own table, random_ind stays
@@ -594,7 +598,7 @@ class MatrixFactorization:
             self._keep_aux_variables()
             predictions = user_embedding @ item_embedding.T
             tf_sample_predictions = tf_prediction_serial = None
-            if isinstance(self.loss_graph, (WMRBLoss, BPRLoss, WARPLoss)):
+            if isinstance(self.loss_graph, TABLE_LOSSES):
                 if random_ind is None:
                     raise SampleTableMissing(f'{type(self.loss_graph).__name__} needs generate_sample=True (random_ind is None)')
                 tf_sample_predictions = torch.gather(predictions, 1, random_ind.to(torch.int64))
