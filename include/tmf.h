@@ -332,8 +332,22 @@ int tmf_wmrb_scores6_bf16(const int32_t* ids, const int32_t* outs, const int64_t
  *                   at most tmf_wmrb_scores7_slots() slots; the buffer is then stored slot i -> place[sub_place[sub] + i]
  *   chunk_sub [n_slices * n_groups + 1]   first sub-chunk of chunk slice * n_groups + group
  * Every (user, item) pair of the epoch is in exactly one non-pad slot.  fp32 rows of 65..128 components, n_items < 2^24, V below
- * 4 GB (tmf_wmrb_scores7_supported; 0 for everything else, bf16 included). */
+ * 4 GB (tmf_wmrb_scores7_supported; 0 for everything else, bf16 included).
+ * tmf_wmrb_scores7_f32 deals the steps of a sub-chunk round-robin to its lane groups and computes all 4 slots of every step, pads
+ * included (their scores land behind the buffer); it is correct for the steps of a sub-chunk in ANY order.
+ * tmf_wmrb_scores7_fill_f32 wants the steps of every sub-chunk by descending FILL (= slots that are no pads; a step's entries come
+ * first, its pads behind them) and two tables that say so:
+ *   sub_fill [n_sub, 4]    the sub-chunk's steps of fill 4, 3, 2, 1 (they sum to its steps)
+ *   sub_wave [n_sub, tmf_wmrb_scores7_waves() + 1]   first step, counted from the sub-chunk's first, of every wave's contiguous range:
+ *                   starts at 0, ends at the sub-chunk's steps, never descends; an empty range leaves the wave idle
+ * A wave cuts its range at the class borders and runs each part with a loop that computes slots k < fill only: a pad slot costs
+ * nothing.  The same scores, bit for bit: a score does not depend on the step, lane group or loop it is computed in. */
 int tmf_wmrb_scores7_users_per_group(void);
+int tmf_wmrb_scores7_waves(void);
+int tmf_wmrb_scores7_fill_f32(const void* steps, const int32_t* place, const int64_t* sub_step, const int64_t* sub_place,
+                              const int32_t* chunk_sub, const int32_t* sub_wave, const int32_t* sub_fill, int64_t n_groups,
+                              int32_t n_slices, int64_t n_users, int64_t n_items, const void* U, const void* V, float* sp, float* p,
+                              int n_components, void* stream);
 int tmf_wmrb_scores7_slots(void);
 int tmf_wmrb_scores7_supported(int n_components, int bf16, int64_t n_items);
 int tmf_wmrb_scores7_f32(const void* steps, const int32_t* place, const int64_t* sub_step, const int64_t* sub_place,

@@ -679,6 +679,12 @@ class Scores6Plan(_ScoreStreams):
 
 SCORES7_SLICE_BYTES = 4 << 20   # slices of the item-run scores kernel (TMF_S7_SLICE_BYTES)
 SCORES7_MIN_SHARE = 1.5         # expected entries per distinct row of a group from which sharing the row load pays (C4: 2.9; config-5 shard: 0.29)
+# Scores7Plan.order_by_fill: a step costs STEP + SLOT * fill when a wave's range of a sub-chunk is cut (one row load and the record
+# per step; four LDS reads, the products and the reduction per slot).  The unrolled loops of fill 4 / 3 / 2 / 1 issue 110 / 85 / 62 /
+# 38 VALU and 16 / 12 / 8 / 4 LDS reads per wave-round of 8 steps against 64 CU clocks of row bytes: 3 + 2 fill = 11 / 9 / 7 / 5 sits
+# between the VALU ratio and the flat row cost.  C4 figures: profiles/scores7_fill_c4.json
+SCORES7_COST_STEP, SCORES7_COST_SLOT = 3, 2
+SCORES7_FILL = True             # the default of TMF_S7_FILL
 
 
 def scores7_wanted(plan, wplan, n_components, dtype=torch.float32):
@@ -704,6 +710,12 @@ def scores7_wanted(plan, wplan, n_components, dtype=torch.float32):
         return False
     UG = int(lib.tmf_wmrb_scores7_users_per_group())
     return UG * (S + plan.nnz / max(m, 1)) / plan.n_items >= SCORES7_MIN_SHARE
+
+
+def scores7_fill_wanted():
+    """Whether a TrainState that adopts a Scores7Plan puts its steps into fill order (Scores7Plan.order_by_fill) and runs
+    tmf_wmrb_scores7_fill_f32.  TMF_S7_FILL = 0 | 1 forces the choice; 0 leaves the plan in item order for tmf_wmrb_scores7_f32."""
+    return os.environ.get('TMF_S7_FILL', '1' if SCORES7_FILL else '0') != '0'
 
 
 class Scores7Plan:
@@ -800,6 +812,58 @@ class Scores7Plan:
         steps[:n_steps, 3] = (slot4[:, 2] | (slot4[:, 3] << 16)).to(i32)
         self.steps = steps
         self.n_entries = E
+
+    sub_wave = sub_fill = None   # the tables of tmf_wmrb_scores7_fill_f32: order_by_fill() builds them
+
+    def order_by_fill(self):
+        """The second step of the plan, for tmf_wmrb_scores7_fill_f32 (include/tmf.h): the step records of every sub-chunk, stably, into
+        descending FILL (= slots that are no pads), so the kernel runs each class with a loop that computes its slots only and a pad
+        slot costs nothing.  A sub-chunk keeps its steps, its slots and its places: place / sub_place / sub_step / chunk_sub do not
+        change, and inside a class the steps still ascend by (item, local user).
+          sub_fill [n_sub, 4] int32          steps of fill 4, 3, 2, 1
+          sub_wave [n_sub, waves + 1] int32  first step (counted from the sub-chunk's first) of every wave's contiguous range, cut for
+                                             equal cost SCORES7_COST_STEP + SCORES7_COST_SLOT * fill per step, at multiples of 8 steps
+                                             (a wave-round reads 8 records = 128 contiguous bytes)
+        A second call changes nothing.  -> self"""
+        if self.sub_wave is not None:
+            return self
+        W = int(_lib.load_library().tmf_wmrb_scores7_waves())
+        K, cap, n_steps, n_sub = self.K, self.pad_slot, self.n_steps, self.n_sub
+        dev, i32, i64 = self.steps.device, torch.int32, torch.int64
+        rec = self.steps[:n_steps]
+        fill = torch.zeros(n_steps, dtype=i64, device=dev)
+        for word in (rec[:, 2], rec[:, 3]):
+            fill += ((word & 0xffff) != cap).to(i64) + (((word >> 16) & 0xffff) != cap).to(i64)
+        # the sub-chunk of every step (no sub-chunk is empty): a mark at every first step but the very first, summed up - with the
+        # sorts, gathers and sums the constructor runs at this size (4.4e8 steps at C4), nothing else
+        sub_of = torch.zeros(n_steps, dtype=i64, device=dev)
+        if n_sub > 1:
+            sub_of.scatter_add_(0, self.sub_step[1:n_sub], torch.ones(n_sub - 1, dtype=i64, device=dev))
+        sub_of = torch.cumsum(sub_of, 0)
+        key = sub_of * K + (K - fill)
+        del fill, sub_of
+        order = torch.sort(key, stable=True)[1]
+        cnt = torch.bincount(key, minlength=K * n_sub).view(n_sub, K)      # steps of fill 4, 3, 2, 1
+        del key
+        steps = torch.zeros_like(self.steps)                               # with the record behind the last
+        old64, new64 = self.steps.view(i64), steps.view(i64)               # a record = two 64-bit words, gathered one after the other
+        for half in range(2):
+            new64[:n_steps, half] = old64[:n_steps, half][order]
+        del order, rec, old64, new64
+        self.steps = steps
+        self.sub_fill = cnt.to(i32).contiguous()
+        # wave w of W takes the steps between the points where the running cost passes w / W of the sub-chunk's; the running cost is
+        # piecewise linear in the step (one slope per class), so the points come from the class counts alone - in integers
+        zero = torch.zeros(n_sub, 1, dtype=i64, device=dev)
+        slope = torch.tensor([SCORES7_COST_STEP + SCORES7_COST_SLOT * f for f in range(K, 0, -1)], dtype=i64, device=dev)
+        step_edge = torch.cat([zero, torch.cumsum(cnt, 1)], 1)             # [n_sub, K + 1] first step of every class
+        cost_edge = torch.cat([zero, torch.cumsum(cnt * slope, 1)], 1) * W
+        target = cost_edge[:, K:] // W * torch.arange(1, W, device=dev, dtype=i64)       # [n_sub, W - 1], in units of 1 / W
+        cls = (target[:, :, None] >= cost_edge[:, None, 1:K]).sum(2)                     # the class the point falls in
+        cut = torch.gather(step_edge, 1, cls) + (target - torch.gather(cost_edge, 1, cls)) // (W * slope[cls])
+        cut = torch.minimum((cut + 4) // 8 * 8, step_edge[:, K:])
+        self.sub_wave = torch.cat([zero, cut, step_edge[:, K:]], 1).to(i32).contiguous()
+        return self
 
 
 def scores5_wanted(plan, wplan, n_components, dtype=torch.float32):
@@ -956,14 +1020,16 @@ class TrainState:
                 self.part_layers, self.gradu_launches = 1, 1           # a launch per slice
             need.update(sp=m * S, pk=max(plan.nnz, 1), part=self.part_layers * max(m, 1) * self.ld)
             if scores7_wanted(plan, wplan, self.r, dtype):
-                if wplan.s7 is None or wplan.s7.key != (self.r, dtype):
-                    if os.environ.get('TMF_SCORES7') == '1':
+                try:
+                    if wplan.s7 is None or wplan.s7.key != (self.r, dtype):
                         wplan.s7 = Scores7Plan(plan, wplan, self.r, dtype)
-                    else:   # the default: streams of ~10 bytes per entry that do not fit leave the pass with scores3 / scores6
-                        try:
-                            wplan.s7 = Scores7Plan(plan, wplan, self.r, dtype)
-                        except torch.OutOfMemoryError:
-                            wplan.s7 = None
+                    if scores7_fill_wanted():
+                        wplan.s7.order_by_fill()   # a plan that has its tables stays as it is
+                except torch.OutOfMemoryError:
+                    # the default: streams of ~10 bytes per entry that do not fit leave the pass with scores3 / scores6
+                    if os.environ.get('TMF_SCORES7') == '1':
+                        raise
+                    wplan.s7 = None
             else:
                 wplan.s7 = None
             if wplan.s7 is None and scores6_wanted(plan, wplan, self.r, dtype):
@@ -1488,7 +1554,13 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
     s = _lib.stream_ptr()
     lists = w.lists(p)
     s5, s6, s7 = w.s5, w.s6, w.s7
-    if s7 is not None:
+    if s7 is not None and s7.sub_wave is not None:
+        # item runs, the steps of a sub-chunk classed by fill: a pad slot costs no work (Scores7Plan.order_by_fill)
+        _timed(prof, 'wmrb_scores', lambda: lib.tmf_wmrb_scores7_fill_f32(
+            _lib.ptr(s7.steps), _lib.ptr(s7.place), _lib.ptr(s7.sub_step), _lib.ptr(s7.sub_place), _lib.ptr(s7.chunk_sub),
+            _lib.ptr(s7.sub_wave), _lib.ptr(s7.sub_fill), s7.n_groups, i32(s7.n_slices), m, p.n_items, _lib.ptr(st.U), _lib.ptr(st.V),
+            _lib.ptr(st.sp), _lib.ptr(st.pk), r, s))
+    elif s7 is not None:
         # item runs: one workgroup per (slice, group of 256 users) chunk, the group's rows in LDS, one load of a V row per run
         _timed(prof, 'wmrb_scores', lambda: lib.tmf_wmrb_scores7_f32(
             _lib.ptr(s7.steps), _lib.ptr(s7.place), _lib.ptr(s7.sub_step), _lib.ptr(s7.sub_place), _lib.ptr(s7.chunk_sub), s7.n_groups,

@@ -99,6 +99,8 @@ _BASE_SIGNATURES = {
     'tmf_wmrb_scores6_f32': (_I, [_P, _P, _P, _L, _I32, _L, _L, _P, _P, _P, _P, _I, _P]),
     'tmf_wmrb_scores7_users_per_group': (_I, []),
     'tmf_wmrb_scores7_slots': (_I, []),
+    'tmf_wmrb_scores7_waves': (_I, []),
+    'tmf_wmrb_scores7_fill_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I32, _L, _L, _P, _P, _P, _P, _I, _P]),
     'tmf_wmrb_scores7_supported': (_I, [_I, _I, _L]),
     'tmf_wmrb_scores7_f32': (_I, [_P, _P, _P, _P, _P, _L, _I32, _L, _L, _P, _P, _P, _P, _I, _P]),
     'tmf_wmrb_scores5_users_per_workgroup': (_I, []),

@@ -1504,6 +1504,14 @@ static int wmrb_scores6_impl(const int32_t* ids, const int32_t* outs, const int6
 // VALU wave-instructions per round of one wave (8 steps = 32 entry slots), counted in the gfx950 disassembly of the unrolled loop:
 // 110 = 16 v_pk_mul + 16 v_pk_fma + 38 v_add_f32 (12 of them DPP) + 8 v_cndmask + 32 address / select / bookkeeping: 3.4 per
 // entry slot (the lean scores3 walk: 7.7 per row).
+// Steps classed by fill (tmf_wmrb_scores7_fill_f32; _engine.Scores7Plan.order_by_fill): at C4 35.5 % of the slots are pads, and a pad
+// costs what an entry costs.  The plan puts the steps of a sub-chunk into descending fill (slots that are no pads) and says where
+// the classes end (sub_fill) and which contiguous range of them each wave takes (sub_wave: equal cost, not equal steps); a wave runs
+// each class's part of its range with the instance of the loop that computes slots k < FILL only - chosen by scalar branches OUTSIDE
+// the loop (a branch or a bound inside it is if-converted or costs the wait counts).  VALU / LDS reads per round of 8 steps:
+// 110 / 16, 85 / 12, 62 / 8, 38 / 4 for FILL 4, 3, 2, 1.  Without the tables: round-robin, every step as FILL 4 - the kernel as it was.
+// gfx950: 102 VGPRs, no scratch, no spills.  C4, same box, 5 alternating rounds: scores 19.73 -> 17.64 ms, epoch 79.72 -> 77.37
+// (profiles/scores7_fill_c4.json).
 // ---------------------------------------------------------------------------------------------
 namespace tmf {
 // C4 scores ms, same box, scores3 26.8 (profiles/scores7_c4.json): 256 users / 16 waves / 6144 slots / 2 rows in flight 19.1 - 20.2
@@ -1524,6 +1532,8 @@ struct S7Streams {
     const int64_t* sub_step;    // [n_sub + 1] first step of every sub-chunk
     const int64_t* sub_place;   // [n_sub + 1] first place of every sub-chunk
     const int32_t* chunk_sub;   // [n_chunks + 1] first sub-chunk of every chunk
+    const int32_t* sub_wave;    // [n_sub, kS7Waves + 1] first step (in its sub-chunk) of every wave's range, or null: round-robin
+    const int32_t* sub_fill;    // [n_sub, kS7K] steps of fill 4, 3, 2, 1 of every sub-chunk (its steps come in that order), or null
 };
 
 __global__ __launch_bounds__(64 * kS7Waves) void k_wmrb_scores7(S7Streams a, int64_t chunk0, int64_t n_groups, int64_t n_users,
@@ -1546,6 +1556,8 @@ __global__ __launch_bounds__(64 * kS7Waves) void k_wmrb_scores7(S7Streams a, int
     __syncthreads();
     const uint32_t par = (lane >> 4) & 1;
     const uint32_t offA = 16u * g + 128u * par, offB = 16u * g + 128u * (par ^ 1u);   // pieces (0, 1) or (1, 0) of a 256-byte half
+    // v_perm_b32 selector of this lane's slot in a record: bytes 2 k, 2 k + 1 of {z, w} (k = g & 3) under two zero bytes
+    const uint32_t slot_sel = 0x0c0c0000u | ((2u * (g & 3) + 1u) << 8) | (2u * (g & 3));
     struct Row {
         float4 v[4];
     };
@@ -1562,94 +1574,124 @@ __global__ __launch_bounds__(64 * kS7Waves) void k_wmrb_scores7(S7Streams a, int
         }
         return (q[0] + q[2]) + (q[1] + q[3]);
     };
+    // One class of steps: the pipelined loop over the steps first, first + stride, ... < end of this lane group (`rounds` of them for
+    // the wave's first group: the wave runs as many; beyond its last step a group repeats step end - 1 into the pad slot, so every
+    // load below is unconditional).  FILL = the slots of a step that are computed and stored; it is a template argument because the
+    // loop body has to stay branch-free: the class is chosen by scalar branches OUTSIDE the loop.
+    auto run = [&](auto fill_tag, const int4* rec0, int first, int stride, int end, int rounds) {
+        constexpr int FILL = decltype(fill_tag)::value;
+        auto fetch = [&](int i) {   // the record as loaded: whether round i is past the group's last step is decided where it is used
+            const int st = first + stride * i;
+            return rec0[st < end ? st : end - 1];
+        };
+        auto gather = [&](Row& y, const int4& r) {
+            const char* base = reinterpret_cast<const char*>(V);
+            const uint32_t oa = row_byte_off<kS7RowBytes>((uint32_t)r.x, offA), ob = row_byte_off<kS7RowBytes>((uint32_t)r.x, offB);
+            y.v[0] = *reinterpret_cast<const float4*>(base + oa);
+            y.v[1] = *reinterpret_cast<const float4*>(base + ob);
+            y.v[2] = *reinterpret_cast<const float4*>(base + oa + 256);
+            y.v[3] = *reinterpret_cast<const float4*>(base + ob + 256);
+        };
+        auto finish = [&](const Row& y, const int4& r, int i) {
+            float s[FILL];
+#pragma unroll
+            for (int k = 0; k < FILL; ++k) {
+                const uint32_t lu = ((uint32_t)r.y >> (8 * k)) & 0xffu;
+                const char* xa = smem_raw + (lu * kS7RowBytes + offA);
+                const char* xb = smem_raw + (lu * kS7RowBytes + offB);
+                Row x;
+                x.v[0] = *reinterpret_cast<const float4*>(xa);
+                x.v[1] = *reinterpret_cast<const float4*>(xb);
+                x.v[2] = *reinterpret_cast<const float4*>(xa + 256);
+                x.v[3] = *reinterpret_cast<const float4*>(xb + 256);
+                float t = dot(x, y);
+                t += TMF_DPP_MOV(t, 0xB1);    // quad_perm [1,0,3,2]
+                t += TMF_DPP_MOV(t, 0x4E);    // quad_perm [2,3,0,1]
+                t += TMF_DPP_MOV(t, 0x141);   // row_half_mirror (quads are uniform by now): all 8 lanes hold the score
+                s[k] = t;
+            }
+            // lane k < FILL of the group stores score k at its slot (a pad's slot is the one behind the buffer: never flushed)
+            // (its 16 bits of z, w by one byte permute: selects between the words of a record make the compiler keep the ring of
+            // records in scratch memory and index it per lane)
+            float mine_s = s[0];
+            if constexpr (FILL == 2) mine_s = (g & 1) ? s[1] : s[0];
+            if constexpr (FILL == 3) mine_s = (g & 2) ? s[2] : ((g & 1) ? s[1] : s[0]);
+            if constexpr (FILL == 4) mine_s = (g & 2) ? ((g & 1) ? s[3] : s[2]) : ((g & 1) ? s[1] : s[0]);
+            uint32_t slot = __builtin_amdgcn_perm((uint32_t)r.w, (uint32_t)r.z, slot_sel);
+            slot = (slot < (uint32_t)kS7Slots && first + stride * i < end) ? slot : (uint32_t)kS7Slots;
+            if (g < FILL) sbuf[slot] = mine_s;
+        };
+        // Loads return in order (vmcnt): the record of round i + 2 FL is asked for BEHIND the rows of round i + FL, so waiting for
+        // the rows of a round never waits for anything issued after them
+        // (a ring of 2 FL records, the loop unrolled as far: a record is never copied, which would wait for its load).
+        Row y[FL];
+        int4 rec[2 * FL];
+        // The body is branch-free - with a branch per round the compiler's wait counts fall back to vmcnt(0) - and the last
+        // rounds (fewer than 2 FL) run in a tail of their own.
+#pragma unroll
+        for (int j = 0; j < FL; ++j) rec[j] = fetch(j);
+#pragma unroll
+        for (int j = 0; j < FL; ++j) {
+            gather(y[j], rec[j]);
+            rec[FL + j] = fetch(FL + j);
+        }
+        int i = 0;
+        for (; i + 2 * FL <= rounds; i += 2 * FL) {
+#pragma unroll
+            for (int j = 0; j < 2 * FL; ++j) {
+                __builtin_amdgcn_sched_barrier(0);
+                finish(y[j % FL], rec[j], i + j);
+                __builtin_amdgcn_sched_barrier(0);
+                gather(y[j % FL], rec[(j + FL) % (2 * FL)]);   // round i + j + FL (past the end: the last step again, never used)
+                rec[j] = fetch(i + j + 2 * FL);
+            }
+        }
+        const int rem = rounds - i;
+#pragma unroll
+        for (int j = 0; j < 2 * FL - 1; ++j) {
+            if (j < rem) {
+                __builtin_amdgcn_sched_barrier(0);
+                finish(y[j % FL], rec[j], i + j);
+                __builtin_amdgcn_sched_barrier(0);
+                if (j + FL < rem) gather(y[j % FL], rec[j + FL]);
+            }
+        }
+    };
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool by_fill = a.sub_wave != nullptr;   // the steps of a sub-chunk come by descending fill, cut into one range per wave
     for (int sub = sub_b; sub < sub_e; ++sub) {
         const int64_t st0 = a.sub_step[sub];
         const int nsteps = (int)(a.sub_step[sub + 1] - st0);
         const int64_t pl0 = a.sub_place[sub];
         const int nslots = (int)(a.sub_place[sub + 1] - pl0);   // <= kS7Slots
         const int4* rec0 = a.steps + st0;
-        // step i of this lane group is gid + NG i; the wave runs as many rounds as its first group has steps; beyond its last step
-        // a group repeats the sub-chunk's last step into the pad slot, so every load below is unconditional
-        const int mine = nsteps > gid ? (nsteps - gid + NG - 1) / NG : 0;
-        const int rounds = __builtin_amdgcn_readfirstlane(mine);
         // the places of the flush, asked for before the steps: they are the oldest loads in flight and cost the flush no round trip
         const int32_t* pl = a.place + pl0;
         int32_t where[kS7Slots / NT];
 #pragma unroll
         for (int q = 0; q < kS7Slots / NT; ++q) where[q] = (tid + NT * q < nslots) ? __builtin_nontemporal_load(pl + tid + NT * q) : 0;
-        if (rounds > 0) {
-            auto fetch = [&](int i) {   // the record as loaded: whether round i is past the group's last step is decided where it is used
-                const int st = gid + NG * i;
-                return rec0[st < nsteps ? st : nsteps - 1];
-            };
-            auto gather = [&](Row& y, const int4& r) {
-                const char* base = reinterpret_cast<const char*>(V);
-                const uint32_t oa = row_byte_off<kS7RowBytes>((uint32_t)r.x, offA), ob = row_byte_off<kS7RowBytes>((uint32_t)r.x, offB);
-                y.v[0] = *reinterpret_cast<const float4*>(base + oa);
-                y.v[1] = *reinterpret_cast<const float4*>(base + ob);
-                y.v[2] = *reinterpret_cast<const float4*>(base + oa + 256);
-                y.v[3] = *reinterpret_cast<const float4*>(base + ob + 256);
-            };
-            auto finish = [&](const Row& y, const int4& r, int i) {
-                float s[kS7K];
-#pragma unroll
-                for (int k = 0; k < kS7K; ++k) {
-                    const uint32_t lu = ((uint32_t)r.y >> (8 * k)) & 0xffu;
-                    const char* xa = smem_raw + (lu * kS7RowBytes + offA);
-                    const char* xb = smem_raw + (lu * kS7RowBytes + offB);
-                    Row x;
-                    x.v[0] = *reinterpret_cast<const float4*>(xa);
-                    x.v[1] = *reinterpret_cast<const float4*>(xb);
-                    x.v[2] = *reinterpret_cast<const float4*>(xa + 256);
-                    x.v[3] = *reinterpret_cast<const float4*>(xb + 256);
-                    float t = dot(x, y);
-                    t += TMF_DPP_MOV(t, 0xB1);    // quad_perm [1,0,3,2]
-                    t += TMF_DPP_MOV(t, 0x4E);    // quad_perm [2,3,0,1]
-                    t += TMF_DPP_MOV(t, 0x141);   // row_half_mirror (quads are uniform by now): all 8 lanes hold the score
-                    s[k] = t;
-                }
-                // lane k < kS7K of the group stores score k at its slot (a pad's slot is the one behind the buffer: never flushed)
-                const float mine_s = (g & 2) ? ((g & 1) ? s[3] : s[2]) : ((g & 1) ? s[1] : s[0]);
-                const uint32_t w = (g & 2) ? (uint32_t)r.w : (uint32_t)r.z;
-                uint32_t slot = (g & 1) ? (w >> 16) : (w & 0xffffu);
-                slot = (slot < (uint32_t)kS7Slots && gid + NG * i < nsteps) ? slot : (uint32_t)kS7Slots;
-                if (g < kS7K) sbuf[slot] = mine_s;
-            };
-            // Loads return in order (vmcnt): the record of round i + 2 FL is asked for BEHIND the rows of round i + FL, so waiting for
-            // the rows of a round never waits for anything issued after them
-            // (a ring of 2 FL records, the loop unrolled as far: a record is never copied, which would wait for its load).
-            Row y[FL];
-            int4 rec[2 * FL];
-            // The body is branch-free - with a branch per round the compiler's wait counts fall back to vmcnt(0) - and the last
-            // rounds (fewer than 2 FL) run in a tail of their own.
-#pragma unroll
-            for (int j = 0; j < FL; ++j) rec[j] = fetch(j);
-#pragma unroll
-            for (int j = 0; j < FL; ++j) {
-                gather(y[j], rec[j]);
-                rec[FL + j] = fetch(FL + j);
-            }
-            int i = 0;
-            for (; i + 2 * FL <= rounds; i += 2 * FL) {
-#pragma unroll
-                for (int j = 0; j < 2 * FL; ++j) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    finish(y[j % FL], rec[j], i + j);
-                    __builtin_amdgcn_sched_barrier(0);
-                    gather(y[j % FL], rec[(j + FL) % (2 * FL)]);   // round i + j + FL (past the end: the last step again, never used)
-                    rec[j] = fetch(i + j + 2 * FL);
-                }
-            }
-            const int rem = rounds - i;
-#pragma unroll
-            for (int j = 0; j < 2 * FL - 1; ++j) {
-                if (j < rem) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    finish(y[j % FL], rec[j], i + j);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (j + FL < rem) gather(y[j % FL], rec[j + FL]);
-                }
-            }
+        // Without the tables step i of a lane group is gid + NG i (round-robin over the workgroup) and every step runs as fill 4: a pad
+        // slot is computed and lands behind the buffer.  With them this wave owns steps [wb, we) of the sub-chunk, a lane group takes
+        // every eighth of a class's part of that range, and a class runs the loop that computes its slots only.
+        int lo = 8 * wave, hi = nsteps, stride = NG, wb = 0, we = 0, cls = 0;
+        if (by_fill) {
+            const int32_t* sw = a.sub_wave + (int64_t)sub * (kS7Waves + 1) + wave;
+            wb = __builtin_amdgcn_readfirstlane(sw[0]);
+            we = __builtin_amdgcn_readfirstlane(sw[1]);
+            cls = __builtin_amdgcn_readfirstlane(a.sub_fill[(int64_t)sub * kS7K]);
+            lo = wb, hi = we < cls ? we : cls, stride = 8;
+        }
+        if (lo < hi) run(std::integral_constant<int, 4>{}, rec0, lo + (by_fill ? (gid & 7) : gid - 8 * wave), stride, hi, (hi - lo + stride - 1) / stride);
+        if (by_fill) {
+            const int32_t* sf = a.sub_fill + (int64_t)sub * kS7K;
+            int end = cls + __builtin_amdgcn_readfirstlane(sf[1]);
+            lo = wb > cls ? wb : cls, hi = we < end ? we : end, cls = end;
+            if (lo < hi) run(std::integral_constant<int, 3>{}, rec0, lo + (gid & 7), 8, hi, (hi - lo + 7) / 8);
+            end = cls + __builtin_amdgcn_readfirstlane(sf[2]);
+            lo = wb > cls ? wb : cls, hi = we < end ? we : end, cls = end;
+            if (lo < hi) run(std::integral_constant<int, 2>{}, rec0, lo + (gid & 7), 8, hi, (hi - lo + 7) / 8);
+            lo = wb > cls ? wb : cls, hi = we;   // the rest of the range is fill 1
+            if (lo < hi) run(std::integral_constant<int, 1>{}, rec0, lo + (gid & 7), 8, hi, (hi - lo + 7) / 8);
         }
         __syncthreads();
         // flush: thread i stores slot i where place[] says; consecutive slots of a user are consecutive addresses
@@ -1668,10 +1710,11 @@ static bool s7_supported(int n_components, int bf16, int64_t n_items) {
 }
 
 static int wmrb_scores7_impl(const void* steps, const int32_t* place, const int64_t* sub_step, const int64_t* sub_place,
-                             const int32_t* chunk_sub, int64_t n_groups, int32_t n_slices, int64_t n_users, int64_t n_items,
+                             const int32_t* chunk_sub, const int32_t* sub_wave, const int32_t* sub_fill, int64_t n_groups, int32_t n_slices, int64_t n_users, int64_t n_items,
                              const void* U, const void* V, float* sp, float* p, int n_components, void* stream) {
     if (n_users == 0 || n_slices == 0) return TMF_OK;
     TMF_REQUIRE(steps && place && sub_step && sub_place && chunk_sub && U && V && sp && p, "wmrb_scores7: null pointer");
+    TMF_REQUIRE(!sub_wave == !sub_fill, "wmrb_scores7: sub_wave and sub_fill come together");
     TMF_REQUIRE(n_groups == (n_users + kS7Users - 1) / kS7Users && n_slices > 0, "wmrb_scores7: %lld groups for %lld users (%d per group), %d slices",
                 (long long)n_groups, (long long)n_users, kS7Users, n_slices);
     if (!s7_supported(n_components, 0, n_items)) {
@@ -1681,7 +1724,7 @@ static int wmrb_scores7_impl(const void* steps, const int32_t* place, const int6
     }
     static LdsGrant grant;
     if (int rc = grant_dynamic_lds(reinterpret_cast<const void*>(&k_wmrb_scores7), kS7Lds, grant)) return rc;
-    const S7Streams a{static_cast<const int4*>(steps), place, sub_step, sub_place, chunk_sub};
+    const S7Streams a{static_cast<const int4*>(steps), place, sub_step, sub_place, chunk_sub, sub_wave, sub_fill};
     // whole slices per launch, fewer than 2^32 work-items each
     const int64_t per_slice = n_groups * 64 * kS7Waves;
     const int max_slices = (int)((((int64_t)1 << 32) - 1) / per_slice);
@@ -1814,9 +1857,18 @@ extern "C" int tmf_wmrb_scores6_supported(int n_components, int bf16, int64_t n_
 extern "C" int tmf_wmrb_scores7_f32(const void* steps, const int32_t* place, const int64_t* sub_step, const int64_t* sub_place,
                                     const int32_t* chunk_sub, int64_t n_groups, int32_t n_slices, int64_t n_users, int64_t n_items,
                                     const void* U, const void* V, float* sp, float* p, int n_components, void* stream) {
-    return wmrb_scores7_impl(steps, place, sub_step, sub_place, chunk_sub, n_groups, n_slices, n_users, n_items, U, V, sp, p,
+    return wmrb_scores7_impl(steps, place, sub_step, sub_place, chunk_sub, nullptr, nullptr, n_groups, n_slices, n_users, n_items, U, V, sp, p,
                              n_components, stream);
 }
+extern "C" int tmf_wmrb_scores7_fill_f32(const void* steps, const int32_t* place, const int64_t* sub_step, const int64_t* sub_place,
+                                         const int32_t* chunk_sub, const int32_t* sub_wave, const int32_t* sub_fill, int64_t n_groups,
+                                         int32_t n_slices, int64_t n_users, int64_t n_items, const void* U, const void* V, float* sp,
+                                         float* p, int n_components, void* stream) {
+    TMF_REQUIRE(sub_wave && sub_fill, "wmrb_scores7_fill: null pointer");
+    return wmrb_scores7_impl(steps, place, sub_step, sub_place, chunk_sub, sub_wave, sub_fill, n_groups, n_slices, n_users, n_items, U, V,
+                             sp, p, n_components, stream);
+}
+extern "C" int tmf_wmrb_scores7_waves(void) { return tmf::kS7Waves; }
 extern "C" int tmf_wmrb_scores7_users_per_group(void) { return tmf::kS7Users; }
 extern "C" int tmf_wmrb_scores7_slots(void) { return tmf::kS7Slots; }
 extern "C" int tmf_wmrb_scores7_supported(int n_components, int bf16, int64_t n_items) { return s7_supported(n_components, bf16, n_items); }

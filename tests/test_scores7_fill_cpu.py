@@ -1,0 +1,128 @@
+"""_engine.Scores7Plan.order_by_fill (the second step of the plan, for tmf_wmrb_scores7_fill_f32: include/tmf.h), on CPU tensors,
+against NumPy: the step records of every sub-chunk come by descending fill and keep their item order inside a class; nothing else of
+the plan moves; sub_fill counts the classes and sub_wave cuts every sub-chunk into one contiguous range per wave; and a walk exactly
+as the kernel does it - wave range -> class segments -> slots k < FILL of each step - writes every slot of every sub-chunk exactly
+once and never a pad."""
+import numpy as np
+import pytest
+import torch
+
+from test_scores7_cpu import _lib_and_engine, _problem
+
+K = 4
+
+
+def _fields(steps):
+    """steps [n, 4] uint32 -> item [n], users [n, K], slots [n, K]"""
+    users = np.stack([(steps[:, 1] >> (8 * k)) & 0xff for k in range(K)], 1)
+    slots = np.stack([(steps[:, 2 + k // 2] >> (16 * (k % 2))) & 0xffff for k in range(K)], 1)
+    return steps[:, 0].astype(np.int64), users.astype(np.int64), slots.astype(np.int64)
+
+
+def _walk(s7, W):
+    """The kernel's walk in NumPy.  -> (slots processed, rounds included: a lane group past its last step of a class still runs the
+    round, into the pad slot; entries written)"""
+    cap = s7.pad_slot
+    steps = s7.steps.numpy().view(np.uint32)
+    sub_step, sub_place = s7.sub_step.numpy(), s7.sub_place.numpy()
+    sub_wave, sub_fill = s7.sub_wave.numpy().astype(np.int64), s7.sub_fill.numpy().astype(np.int64)
+    processed = written = 0
+    for sub in range(s7.n_sub):
+        _, _, slots = _fields(steps[sub_step[sub]:sub_step[sub + 1]])
+        filled = np.zeros(sub_place[sub + 1] - sub_place[sub], dtype=np.int64)
+        edge = np.concatenate([[0], np.cumsum(sub_fill[sub])])
+        for w in range(W):
+            wb, we = sub_wave[sub, w], sub_wave[sub, w + 1]
+            for c, FILL in enumerate((4, 3, 2, 1)):
+                lo, hi = max(wb, edge[c]), min(we, edge[c + 1])
+                if lo >= hi:
+                    continue
+                rounds = (hi - lo + 7) // 8                      # lane group j of the wave takes lo + j, lo + j + 8, ...
+                processed += rounds * 8 * FILL
+                mine = slots[lo:hi, :FILL].reshape(-1)
+                assert (mine != cap).all()                       # never a pad
+                np.add.at(filled, mine, 1)
+                written += mine.size
+        assert (filled == 1).all(), sub                          # every slot of the sub-chunk exactly once
+    return processed, written
+
+
+def _check_fill(E, lib, m, n, S, nnz, seed, slice_rows=None, slots=None, empty_user=None, problem=None):
+    r = 128
+    W, cap = lib.tmf_wmrb_scores7_waves(), lib.tmf_wmrb_scores7_slots()
+    idx, val, R = problem or _problem(m, n, S, nnz, seed, empty_user)
+    plan = E.InteractionPlan(idx, val, m, n)
+    wplan = E.WmrbPlan(plan, R, item_slices=2, n_components=r, sliced=True)
+    kw = dict(slice_bytes=slice_rows * 512 if slice_rows else None, slots=slots)
+    a = E.Scores7Plan(plan, wplan, r, torch.float32, **kw)       # stays in item order
+    b = E.Scores7Plan(plan, wplan, r, torch.float32, **kw)
+    assert a.sub_wave is None and a.sub_fill is None
+    assert b.order_by_fill() is b
+    for name in ('place', 'sub_place', 'sub_step', 'chunk_sub'):  # bit-equal to before
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
+    assert (b.n_steps, b.n_sub, b.n_entries, b.slots, b.pad_slot) == (a.n_steps, a.n_sub, a.n_entries, a.slots, a.pad_slot)
+    c = E.Scores7Plan(plan, wplan, r, torch.float32, **kw)       # the untouched plan still equals a fresh construction
+    assert torch.equal(a.steps, c.steps) and torch.equal(a.place, c.place) and c.sub_wave is None
+    before = [t.clone() for t in (b.steps, b.sub_wave, b.sub_fill)]
+    assert b.order_by_fill() is b                                # a second call changes nothing
+    assert all(torch.equal(x, y) for x, y in zip(before, (b.steps, b.sub_wave, b.sub_fill)))
+
+    n_sub, sub_step = b.n_sub, b.sub_step.numpy()
+    assert b.steps.shape == a.steps.shape and b.steps.dtype == torch.int32 and bool((b.steps[b.n_steps:] == 0).all())
+    assert b.sub_fill.shape == (n_sub, K) and b.sub_fill.dtype == torch.int32
+    assert b.sub_wave.shape == (n_sub, W + 1) and b.sub_wave.dtype == torch.int32
+    old, new = a.steps.numpy().view(np.uint32), b.steps.numpy().view(np.uint32)
+    sub_fill, sub_wave = b.sub_fill.numpy(), b.sub_wave.numpy()
+    nst = np.diff(sub_step)
+    assert (sub_fill >= 0).all() and (sub_fill.sum(1) == nst).all()                 # sub_fill sums to the sub-chunk's steps
+    assert (sub_wave[:, 0] == 0).all() and (sub_wave[:, W] == nst).all() and (np.diff(sub_wave, axis=1) >= 0).all()
+    for sub in range(n_sub):
+        o, s = old[sub_step[sub]:sub_step[sub + 1]], new[sub_step[sub]:sub_step[sub + 1]]
+        assert np.array_equal(o[np.lexsort(o.T[::-1])], s[np.lexsort(s.T[::-1])])   # the multiset of records is kept
+        item, users, slots = _fields(s)
+        fill = (slots != cap).sum(1)
+        assert (np.diff(fill) <= 0).all() and fill.min() >= 1                       # fills descend
+        assert np.array_equal(np.bincount(K - fill, minlength=K), sub_fill[sub])
+        key = item * 256 + users[:, 0]
+        same = np.diff(fill) == 0
+        assert (np.diff(key)[same] > 0).all()                                       # (item, user) ascends inside a class
+    processed, written = _walk(b, W)
+    assert written == b.n_entries
+    return b, processed
+
+
+@pytest.mark.parametrize('which', ['one', 'ug-1', 'ug+1', '3ug+7'])
+def test_fill_order_on_the_shapes_of_the_streams_test(which):
+    lib, E = _lib_and_engine()
+    UG = lib.tmf_wmrb_scores7_users_per_group()
+    m = {'one': 1, 'ug-1': UG - 1, 'ug+1': UG + 1, '3ug+7': 3 * UG + 7}[which]
+    _check_fill(E, lib, m, 300, 20, 6 * m, seed=m, slice_rows=100, empty_user=min(3, m - 1))
+
+
+def test_fill_order_of_a_tiny_catalog_with_small_sub_chunks():
+    """40 items, S = 30, 64 slots: sub-chunks with fewer steps than a wave has lane groups, waves with empty ranges, classes missing."""
+    lib, E = _lib_and_engine()
+    b, _ = _check_fill(E, lib, 70, 40, 30, 400, seed=9, slice_rows=13, slots=64)
+    W = lib.tmf_wmrb_scores7_waves()
+    assert bool((b.sub_wave[:, 1:] == b.sub_wave[:, :W]).any())                     # empty ranges exist ...
+    assert bool((b.sub_fill == 0).any())                                            # ... and so do missing classes
+
+
+def test_fill_order_at_the_density_of_the_benchmark():
+    """One group of 256 users at n = 100000, S = 1024 with ~100 interactions per user (uniform negatives, zipf-like positives): 36 % of
+    the slots of the item-ordered steps are pads.  The walk over the fill-ordered plan may process at most 1.10 x the entries - the
+    slack is for the rounds at the borders of a class and of a wave's range, where lane groups past the last step run into the pad
+    slot.  A plan that stopped sorting processes ~1.55 x."""
+    lib, E = _lib_and_engine()
+    m, n, S = lib.tmf_wmrb_scores7_users_per_group(), 100_000, 1024
+    g = torch.Generator().manual_seed(5)
+    R = torch.stack([torch.randperm(n, generator=g)[:S] for _ in range(m)]).to(torch.int32)
+    u = torch.arange(m).repeat_interleave(100)
+    j = (n * torch.rand(u.numel(), generator=g, dtype=torch.float64) ** 3).long().clamp_(max=n - 1)   # popular items first
+    key = torch.unique(u * n + j)
+    idx, val = torch.stack([key // n, key % n], 1), torch.ones(key.numel())
+    b, processed = _check_fill(E, lib, m, n, S, None, None, problem=(idx, val, R))
+    ratio, unsorted = processed / b.n_entries, K * b.n_steps / b.n_entries
+    print(f'slots processed / entries: {ratio:.4f} in fill order, {unsorted:.4f} with every step as fill 4')
+    assert unsorted > 1.4                                                           # the shape has the pads the issue is about
+    assert ratio <= 1.10
