@@ -808,6 +808,35 @@ int tmf_sample_rows_supported(int32_t n_items, int32_t n_samples);
 int tmf_sample_rows(int32_t n_items, int64_t n_users, int32_t n_samples, int64_t seed, int64_t user_offset, int32_t* R,
                     int32_t* failed, void* stream);
 
+/* EXTENSION (the reference has no softmax): the softmax of a positive against the WHOLE catalog - FullSoftmaxLoss - without the
+ * [m, n] score matrix (csrc/tmf_fullsoftmax.hip).  TMF_VERSION stays 203: nothing that existed changes.
+ * All three take fp32 tables of 1 <= n_components <= tmf_fsm_max_components (128) - any value, not only multiples of 4 - on
+ * v_mfma_f32_32x32x2_f32; beyond it they return TMF_E_UNSUPPORTED before any launch.  A, B: [rows, ld] row-major, 16-byte aligned,
+ * ld % 4 == 0, ld >= n_components; columns >= n_components are never used, whatever they hold.  No atomics: every output is
+ * bit-identical from run to run.
+ *
+ *   tmf_fsm_lse_f32   lse[u] = log sum_{i < n} exp(A[u] . B[i]) for u < m, by a running maximum: finite for every finite score.
+ *                     A row of A that holds a NaN (or whose scores reach +inf) gets a non-finite lse; no other row reads it.
+ *                     lse: [m] fp32; nothing beyond lse[m - 1] is written.  m == 0: TMF_OK, no launch.
+ *   tmf_fsm_wsum_f32  G[a, c] += sum_{b < nb} w_u exp(A[a] . B[b] - lse_u) B[b, c]   for a < ma, c < n_components,
+ *                     where u, the row lse and w are indexed by, is a when user_is_a == 1 (lse, w: [ma]) and b when user_is_a == 0
+ *                     (lse, w: [nb]).  `+=`: the sums are added onto what G [ma, ldg] holds, one read and one write per element;
+ *                     columns >= n_components of G are not touched.  user_is_a == 1: a row with w[a] == 0 is not written at all.
+ *                     user_is_a == 0: a swept row with w[b] == 0 contributes nothing, whatever lse[b] is.  ma == 0 or nb == 0:
+ *                     TMF_OK, no launch.
+ *   tmf_fsm_pos_pass_f32  the arguments of tmf_mse_pass_f32 up to the slab, always under TMF_EPI_GRAD: G_out[row] = - sum of
+ *                     Y_old[other[k]] over the entries k of the row with val[k] > 0 (zeros for a row without one; a NaN value is not
+ *                     > 0); rows cut into several segments leave their parts in the slab for tmf_combine_rows_f32, as there.
+ *                     loss_part != NULL (then lse != NULL, [table rows]): loss_part[seg] = sum over those entries of
+ *                     (lse[row] - X_old[row] . Y_old[other[k]]), for tmf_sum_f32. */
+int tmf_fsm_max_components(void);
+int tmf_fsm_lse_f32(const float* A, const float* B, int64_t m, int64_t n, int n_components, int64_t lda, int64_t ldb, float* lse,
+                    void* stream);
+int tmf_fsm_wsum_f32(const float* A, const float* B, int64_t ma, int64_t nb, int n_components, int64_t lda, int64_t ldb,
+                     const float* lse, const float* w, int user_is_a, float* G, int64_t ldg, void* stream);
+int tmf_fsm_pos_pass_f32(const tmf_segments* seg, const int32_t* other, const float* val, const float* X_old, const float* Y_old,
+                         float* G_out, float* slab, const float* lse, float* loss_part, int n_components, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

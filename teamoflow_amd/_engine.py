@@ -927,8 +927,14 @@ class TrainState:
     (``share_scratch``) instead of once per state."""
 
     def __init__(self, U0, V0, plan, n_components, wplan=None, dtype=torch.float32, V_tables=None, scratch=None, kl=False,
-                 user_bias=None, item_bias=None, user_feat=None, item_feat=None, user_relu=None, item_relu=None):
+                 user_bias=None, item_bias=None, user_feat=None, item_feat=None, user_relu=None, item_relu=None, full_softmax=False):
         dev = plan.col_u.device
+        if full_softmax:   # epoch_full_softmax: every user's log-partition (rewritten each epoch) and its number of positives, as fp32
+            if dtype is not torch.float32 or int(n_components) > FULL_SOFTMAX_MAX_COMPONENTS or plan.seg_i is None or V_tables is not None:
+                raise ValueError(f'the full softmax needs float32 tables of its own with n_components <= {FULL_SOFTMAX_MAX_COMPONENTS} '
+                                 f'and a plan with csc=True')
+            self.fsm_lse = torch.zeros(max(plan.n_users, 1), dtype=torch.float32, device=dev)
+            self.fsm_w = torch.bincount(plan.user_of[plan.val_u > 0].to(torch.int64), minlength=max(plan.n_users, 1)).to(torch.float32)
         if kl:   # epoch_kl: the per-segment fp64 moments of the user side and the six coefficients tmf_kl_coeffs derives from them
             self.kl_part = torch.zeros(max(plan.seg_u.nseg, 1), 6, dtype=torch.float64, device=dev)
             self.kl_coef = torch.zeros(6, dtype=torch.float64, device=dev)
@@ -1417,6 +1423,7 @@ def _timed(prof, name, call):
 
 
 LOGISTIC_LOSSES = ('logistic', 'logistic_w')   # LogisticLoss(weighted=False) / LogisticLoss(weighted=True)
+FULL_SOFTMAX_MAX_COMPONENTS = 128   # tmf_fsm_max_components: the widest table csrc/tmf_fullsoftmax.hip sweeps (fp32 only)
 
 
 SLICED_ONLY = ('bpr', 'warp', 'softmax')   # pair steps of the sliced user pass alone: the one-kernel pass has the hinge built in
@@ -1424,18 +1431,19 @@ PAIR_LOSSES = ('wmrb', 'bpr', 'warp', 'softmax')   # the losses over the static 
 
 
 def loss_name(loss_graph):
-    """The name run_epoch knows the loss of a fit by: 'mse', 'wmrb', 'kl', 'bpr', 'warp', 'softmax', 'logistic' or 'logistic_w' for exactly
-    the seven built-in loss classes (not their subclasses: what a subclass computes is its own business, and the generic path's).  Anything
+    """The name run_epoch knows the loss of a fit by: 'mse', 'wmrb', 'kl', 'bpr', 'warp', 'softmax', 'full_softmax', 'logistic' or
+    'logistic_w' for exactly the eight built-in loss classes (not their subclasses: what a subclass computes is its own business, and
+    the generic path's).  Anything
     else raises - no loss trains as another one because a chain of isinstance tests fell through."""
     from .mf import loss_graphs as L
     kind = type(loss_graph)
     if kind is L.LogisticLoss:
         return 'logistic_w' if loss_graph.weighted else 'logistic'
     names = {L.MSELoss: 'mse', L.WMRBLoss: 'wmrb', L.KLDivergenceLoss: 'kl', L.BPRLoss: 'bpr', L.WARPLoss: 'warp',
-             L.SampledSoftmaxLoss: 'softmax'}
+             L.SampledSoftmaxLoss: 'softmax', L.FullSoftmaxLoss: 'full_softmax'}
     if kind not in names:
         raise TypeError(f'{kind.__name__} is not a loss the HIP engine trains (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, '
-                        f'BPRLoss, WARPLoss, SampledSoftmaxLoss)')
+                        f'BPRLoss, WARPLoss, SampledSoftmaxLoss, FullSoftmaxLoss)')
     return names[kind]
 
 
@@ -1467,7 +1475,8 @@ def checked_negatives(random_ind, n_rows, n_items, device, rows=None):
 def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM,
               user_out=None):
     """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'bpr', 'warp', 'softmax' (c = 1 or n_items / n_samples), 'kl',
-    'logistic', 'logistic_w' or 'mse' - on the state's tables: the ONE place that maps a loss to its epoch.  The other arguments as
+    'logistic', 'logistic_w', 'mse' or 'full_softmax' (only on a state built with full_softmax=True) - on the state's tables: the ONE
+    place that maps a loss to its epoch.  The other arguments as
     in epoch_mse.  'bpr', 'warp' and 'softmax' are epochs only of a state whose WmrbPlan is sliced (wmrb_plan_for(force_sliced=True)):
     the one-kernel user pass has the hinge built in.  On any other state they are refused like a name nobody knows - never run as
     WMRB."""
@@ -1481,8 +1490,11 @@ def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=
         epoch_logistic(st, adam, loss_out, loss == 'logistic_w', item_epi, item_out, prof, user_epi, user_out)
     elif loss == 'mse':
         epoch_mse(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
+    elif loss == 'full_softmax' and getattr(st, 'fsm_lse', None) is not None:
+        epoch_full_softmax(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
     else:
-        raise ValueError(f'run_epoch: unknown loss {loss!r}' + (' on a state without a sliced WmrbPlan' if loss in SLICED_ONLY else ''))
+        raise ValueError(f'run_epoch: unknown loss {loss!r}' + (' on a state without a sliced WmrbPlan' if loss in SLICED_ONLY else '')
+                         + (' on a state built without full_softmax=True' if loss == 'full_softmax' else ''))
 
 
 def _row_pass_finish(lib, seg, slab, X_old, X_out, r, epi, adam, stream, sfx='_f32'):
@@ -1538,6 +1550,44 @@ def epoch_kl(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=Non
         p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(st.kl_part), r, s))
     _timed(prof, 'kl_coeffs', lambda: lib.tmf_kl_coeffs(_lib.ptr(st.kl_part), p.seg_u.nseg, _lib.ptr(loss_out), _lib.ptr(st.kl_coef), s))
     _list_passes(st, adam, 'tmf_kl_pass', 'kl', st.kl_coef, st.kl_coef, (), None, item_epi, item_out, prof, user_epi, user_out)
+
+
+def epoch_full_softmax(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM, user_out=None):
+    """One FullSoftmaxLoss epoch (st built with full_softmax=True; csrc/tmf_fullsoftmax.hip): lse of every user over the whole catalog
+    -> the positives' term of both gradients over the interaction lists (the user pass also sums lse_u - p_k: the loss) -> the two
+    sweeps that add n_u pi_ui V[i] to G_U and n_u pi_ui U[u] to G_V -> the steps.  Everything reads the pre-update tables.
+    loss_out: 1-element fp64 device tensor receiving sum over positives of (lse_u - p_k).
+    Both sides always form their raw gradient table.  item_epi / user_epi = EPI_GRAD: that table is item_out / user_out and nothing is
+    stepped here (the sides, L2, persistent Adam).  EPI_ADAM: the gradient takes the second buffer's place, the table steps in place from
+    it (tmf_adam_fresh_rows_f32) and the two names change hands, so that the caller's swap() leaves the stepped table in U / V as after
+    any other epoch - the same two buffers every epoch, whatever the number of epochs captured.
+    Stream-ordered, nothing allocated, no host reads, no atomics: graph-capturable and bit-reproducible."""
+    lib, p, r, s, P = _lib.get(), st.plan, st.r, _lib.stream_ptr(), _lib.ptr
+    m, n, ld = p.n_users, p.n_items, st.ld
+    for epi, out, nxt in ((user_epi, user_out, st.U_nxt), (item_epi, item_out, st.V_nxt)):
+        if epi not in (_lib.EPI_ADAM, _lib.EPI_GRAD) or (epi == _lib.EPI_ADAM) != (out is None) or (out is None and nxt is None):
+            raise ValueError('epoch_full_softmax: EPI_GRAD with the gradient table to fill, or EPI_ADAM without one on a side that has '
+                             'its second buffer')
+    G_U = st.U_nxt if user_out is None else user_out
+    G_V = st.V_nxt if item_out is None else item_out
+    _timed(prof, 'fsm_lse', lambda: lib.tmf_fsm_lse_f32(P(st.U), P(st.V), m, n, r, ld, ld, P(st.fsm_lse), s))
+    _timed(prof, 'fsm_user_pass', lambda: lib.tmf_fsm_pos_pass_f32(p.seg_u.cstruct(), P(p.col_u), P(p.val_u), P(st.U), P(st.V), P(G_U),
+                                                                   P(st.slab), P(st.fsm_lse), P(st.loss_part), r, s))
+    _row_pass_finish(lib, p.seg_u, st.slab, st.U, G_U, r, _lib.EPI_GRAD, adam, s)
+    _lib.check(lib.tmf_sum_f32(P(st.loss_part), p.seg_u.nseg, P(loss_out), s), lib)
+    _timed(prof, 'fsm_item_pass', lambda: lib.tmf_fsm_pos_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(st.V), P(st.U), P(G_V),
+                                                                   P(st.slab), None, None, r, s))
+    _row_pass_finish(lib, p.seg_i, st.slab, st.V, G_V, r, _lib.EPI_GRAD, adam, s)
+    _timed(prof, 'fsm_wsum_user', lambda: lib.tmf_fsm_wsum_f32(P(st.U), P(st.V), m, n, r, ld, ld, P(st.fsm_lse), P(st.fsm_w), 1, P(G_U),
+                                                               G_U.shape[1], s))
+    _timed(prof, 'fsm_wsum_item', lambda: lib.tmf_fsm_wsum_f32(P(st.V), P(st.U), n, m, r, ld, ld, P(st.fsm_lse), P(st.fsm_w), 0, P(G_V),
+                                                               G_V.shape[1], s))
+    if user_epi == _lib.EPI_ADAM:
+        _timed(prof, 'fsm_user_step', lambda: lib.tmf_adam_fresh_rows_f32(P(st.U), P(G_U), m, r, adam, s))
+        st.U, st.U_nxt = st.U_nxt, st.U
+    if item_epi == _lib.EPI_ADAM:
+        _timed(prof, 'fsm_item_step', lambda: lib.tmf_adam_fresh_rows_f32(P(st.V), P(G_V), n, r, adam, s))
+        st.V, st.V_nxt = st.V_nxt, st.V
 
 
 def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, U_out=None, pairs='hinge'):

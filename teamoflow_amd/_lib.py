@@ -179,6 +179,10 @@ _BASE_SIGNATURES = {
     'tmf_als_cg_rows_f32': (_I, [_P, _L, _I, _L, _P, _L, _P, _P, _P, _P, _F, _P, _L, _P, _L, _P, _L, _I, _P, _P]),
     'tmf_sample_rows_supported': (_I, [_I32, _I32]),
     'tmf_sample_rows': (_I, [_I32, _L, _I32, _L, _L, _P, _P, _P]),
+    'tmf_fsm_max_components': (_I, []),
+    'tmf_fsm_lse_f32': (_I, [_P, _P, _L, _L, _I, _L, _L, _P, _P]),
+    'tmf_fsm_wsum_f32': (_I, [_P, _P, _L, _L, _I, _L, _L, _P, _P, _I, _P, _L, _P]),
+    'tmf_fsm_pos_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
 }
 
 SIGNATURES.update(_BASE_SIGNATURES)

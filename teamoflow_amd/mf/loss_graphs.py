@@ -1,7 +1,9 @@
 """Loss graphs (plug-in interface of /root/reference/src/teamoflow/mf/loss_graphs.py).
 
-``MSELoss``, ``WMRBLoss``, ``KLDivergenceLoss``, ``LogisticLoss``, ``BPRLoss``, ``WARPLoss`` and ``SampledSoftmaxLoss`` (extensions: the
-reference has no logistic loss, pointwise or pairwise, no first-violator ranking loss and no softmax) with ``LinearEmbedding`` over indicator features are recognised by
+``MSELoss``, ``WMRBLoss``, ``KLDivergenceLoss``, ``LogisticLoss``, ``BPRLoss``, ``WARPLoss``, ``SampledSoftmaxLoss`` and
+``FullSoftmaxLoss`` (extensions: the reference has no logistic loss, pointwise or pairwise, no first-violator ranking loss and no
+softmax, sampled or over the whole catalog - the last one reads no negative table: its partition is swept through the matrix cores,
+csrc/tmf_fullsoftmax.hip) with ``LinearEmbedding`` over indicator features are recognised by
 ``MatrixFactorization.fit`` (same isinstance dispatch as matrix_factorization.py:152-162) and run as
 fused HIP kernels; ``get_loss`` below is the generic differentiable definition used when the model is
 built from other plug-ins (dense features, custom embeddings), always called by keyword like
@@ -155,3 +157,23 @@ class SampledSoftmaxLoss(LossGraph):
         log_c = math.log(n_items / n_samples) if self.catalog_scale else 0.0
         partition = torch.logsumexp(tf_sample_predictions, dim=1)[users] + log_c     # log(c sum_s exp(sp[u, s])), per positive
         return torch.logaddexp(pos, partition) - pos
+
+
+class FullSoftmaxLoss(LossGraph):
+    """Extension (the softmax the sampled losses approximate; not in the reference): the softmax of a positive against EVERY item of
+    the catalog.  For every stored interaction k of user u with a value > 0 and score p_k:
+
+        loss_k = logsumexp_i(predictions[u, :]) - p_k
+
+    The positive itself is part of the partition, and so is every other positive of the user.  Stored values <= 0 take no part (as
+    in WMRBLoss); a duplicate counts as often as it is stored.  With pi_ui = exp(s_ui - lse_u) and n_u the number of stored entries
+    of u with a value > 0, the gradient of the sum over positives is  n_u pi_ui - [number of positives of u at i]  per score: dense
+    on the item side (every item row moves when any user has a positive), zero for a user without positives.  No negative table, no
+    n_samples, no resampling: the engine sweeps U V^T through the matrix cores without materialising it; this is the definition."""
+
+    def get_loss(self, tf_interactions, predictions, tf_sample_predictions=None, tf_prediction_serial=None, n_items=None,
+                 n_samples=None):
+        mask = tf_interactions.values > 0.0
+        users = tf_interactions.indices[:, 0][mask]
+        items = tf_interactions.indices[:, 1][mask]
+        return torch.logsumexp(predictions, dim=1)[users] - predictions[users, items]

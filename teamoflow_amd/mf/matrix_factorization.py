@@ -3,7 +3,7 @@
 
 Dispatch (``MatrixFactorization._route``; same isinstance test the reference uses at :115,:136-162): a model made of
 (``LinearEmbedding`` | ``BiasedLinearEmbedding``) x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss`` |
-``LogisticLoss`` | ``BPRLoss`` | ``WARPLoss`` | ``SampledSoftmaxLoss``) - or ``LinearEmbedding`` over ``SparseFeatures`` on either side, or with ``relu_engine = True``
+``LogisticLoss`` | ``BPRLoss`` | ``WARPLoss`` | ``SampledSoftmaxLoss`` | ``FullSoftmaxLoss``) - or ``LinearEmbedding`` over ``SparseFeatures`` on either side, or with ``relu_engine = True``
 (off by default) a ``ReLUEmbedding`` side over either - trains on the HIP engine (``_engine.py`` -> libtmf.so); for unbiased MSE / WMRB it
 needs a GPU - there is no CPU fallback for them.  Any other combination of plug-ins (dense features, ReLU embeddings, user subclasses)
 trains through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins' own ``get_repr`` /
@@ -25,7 +25,8 @@ import torch
 from .. import _als, _engine, _lib, _ops
 from .embedding_graphs import BiasedLinearEmbedding, Embeddings, LinearEmbedding, ReLUEmbedding
 from .initializer_graphs import NormalInitializer
-from .loss_graphs import BPRLoss, KLDivergenceLoss, LogisticLoss, LossGraph, MSELoss, SampledSoftmaxLoss, WARPLoss, WMRBLoss
+from .loss_graphs import (BPRLoss, FullSoftmaxLoss, KLDivergenceLoss, LogisticLoss, LossGraph, MSELoss, SampledSoftmaxLoss, WARPLoss,
+                          WMRBLoss)
 from .sparse import IndicatorFeatures, SparseFeatures, SparseInteractions, default_device, is_indicator
 from .utils import gather_matrix_indices, random_sampler, random_sampler_device
 
@@ -37,9 +38,11 @@ GRAPH_MAX_WORK = 20_000_000    # interactions + sampled scores per epoch below w
 # What trains where (DESIGN.md prints this table; MatrixFactorization._route reads it).  A row is a feature of a fit, a column a
 # setting that leaves the single-GPU full-batch fp32 fresh-Adam fit: 'ok' = the engine has that form, 'generic' = fit() trains
 # through _fit_generic, 'refuse' = NotImplementedError before any weight is drawn or plan built.
-ENGINE_LOSSES = (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, BPRLoss, WARPLoss, SampledSoftmaxLoss)   # exactly these types, no subclass
+ENGINE_LOSSES = (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, BPRLoss, WARPLoss, SampledSoftmaxLoss,
+                 FullSoftmaxLoss)   # exactly these types, no subclass
 TABLE_LOSSES = (WMRBLoss, BPRLoss, WARPLoss, SampledSoftmaxLoss)   # these and their subclasses read the static negative table
 PAIR_STEP_LOSSES = (BPRLoss, WARPLoss, SampledSoftmaxLoss)          # the route feature 'pair': a pair step of the sliced user pass
+PAIR_ROW_LOSSES = PAIR_STEP_LOSSES + (FullSoftmaxLoss,)             # the losses that answer by the row 'pair': single GPU, full batch
 _SETTINGS = {   # column -> (the attribute a refusal names, has the model left its default?), in the order refusals are met
     'relu_engine': ('relu_engine', lambda m: getattr(m, 'relu_engine', 0)     # counts beside a ReLUEmbedding side only
                     and ReLUEmbedding in (type(m.user_repr_graph), type(m.item_repr_graph))),
@@ -189,7 +192,7 @@ class MatrixFactorization:
         every setting is a form of theirs, and without a GPU they fail in _fit_sparse - there is no CPU fallback."""
         loss, kinds = type(self.loss_graph), (type(self.user_repr_graph), type(self.item_repr_graph))
         # the refusals, in the order a model that meets several has always met them
-        answers = [self._answer('pair', loss.__name__)] if loss in PAIR_STEP_LOSSES else []
+        answers = [self._answer('pair', loss.__name__)] if loss in PAIR_ROW_LOSSES else []
         if any(self._alphas()):
             self._answer('l2', 'user_alpha / item_alpha > 0')
         every = self._resample_setting()[0]
@@ -205,7 +208,18 @@ class MatrixFactorization:
         structured = any(featured) or BiasedLinearEmbedding in kinds or ReLUEmbedding in kinds
         answers += [self._answer(feature) for feature, there in (('kl', loss is KLDivergenceLoss), ('logistic', loss is LogisticLoss),
                                                                  ('side', structured)) if there]
-        return 'generic' if 'generic' in answers else 'engine'
+        if 'generic' in answers:
+            return 'generic'
+        if loss is FullSoftmaxLoss:
+            # the sweep kernels' own limits.  Refused, not handed to the generic loop: its [m, n] matrix is what this loss avoids
+            if self.factor_dtype is not torch.float32:
+                raise NotImplementedError(f'FullSoftmaxLoss with factor_dtype={self.factor_dtype}: its kernels sweep float32 tables '
+                                          f'only (set factor_dtype back to torch.float32)')
+            if self.n_components > _engine.FULL_SOFTMAX_MAX_COMPONENTS:
+                raise NotImplementedError(f'FullSoftmaxLoss with n_components={self.n_components} > {_engine.FULL_SOFTMAX_MAX_COMPONENTS}: '
+                                          f'the sweep kernel holds a 128-row tile of the swept table in LDS beside its output '
+                                          f'accumulators; wider models are not built')
+        return 'engine'
 
     def _engine_form(self):
         """Which fit _fit_sparse runs: 'batch_users' | 'shard_items' | 'data_parallel' | 'full'.  The forms exclude each other:
@@ -399,12 +413,14 @@ class MatrixFactorization:
         st, c = self._sparse_state(loss, n_users, n_items, interactions, U0, V0, dev, user_feat, item_feat)
         if st is None:
             return False   # an empty class: no moments to take (the reference's arithmetic gives NaN; the generic path keeps that)
-        denom = st.plan.n_pos if loss in _engine.PAIR_LOSSES else 1 if loss == 'kl' else st.plan.nnz   # KL: the loss is one scalar, its mean is itself
+        # KL: the loss is one scalar, its mean is itself; the losses over positives: their number
+        denom = st.plan.n_pos if loss in _engine.PAIR_LOSSES + ('full_softmax',) else 1 if loss == 'kl' else st.plan.nnz
         self.loss_history_ = []
         step = self._sparse_step(st, loss, c, lr)
         # Launch-bound problems (a few hundred microseconds of kernels per epoch): capture an even number of
         # epochs into one hipGraph and replay it - the per-launch host cost disappears from the loop.
-        work = st.plan.nnz + (st.plan.n_users * st.wplan.S if loss in _engine.PAIR_LOSSES else 0)
+        work = st.plan.nnz + (st.plan.n_users * st.wplan.S if loss in _engine.PAIR_LOSSES else 0) \
+            + (st.plan.n_users * st.plan.n_items if loss == 'full_softmax' else 0)   # every score of the catalog, five times an epoch
         G = min(epochs - epochs % 2, GRAPH_EPOCHS)
         use_graph = G >= 4 and work <= GRAPH_MAX_WORK and os.environ.get('TMF_NO_GRAPH') is None and self.optimizer != 'adam'
         every = self._resample_setting()[0]   # 0 for a loss that reads no table
@@ -456,7 +472,8 @@ class MatrixFactorization:
                                    b0=torch.zeros(aux, device=dev) if kept_b is None else kept_b)
                 feat[side] = None
         st = _engine.TrainState(U0, V0, plan, r, wplan, dtype=self.factor_dtype, kl=kl, user_bias=bias0[0], item_bias=bias0[1],
-                                user_feat=feat[0], item_feat=feat[1], user_relu=relu0[0], item_relu=relu0[1])
+                                user_feat=feat[0], item_feat=feat[1], user_relu=relu0[0], item_relu=relu0[1],
+                                full_softmax=loss == 'full_softmax')
         alphas = self._alphas()
         if any(alphas):   # never called with zeros: an unpenalised fit is today's state, launch for launch
             st.set_l2(*alphas)
