@@ -57,7 +57,7 @@ def stable_order(keys, n_rows):
         perm = torch.empty(n, dtype=torch.int64, device=keys.device)
         rowptr = torch.empty(n_rows + 1, dtype=torch.int64, device=keys.device)
         ws = torch.empty(lib.tmf_stable_order_workspace_bytes(n), dtype=torch.uint8, device=keys.device)
-        _lib.check(lib.tmf_stable_order_i32(_lib.ptr(k32), n, n_rows, _lib.ptr(perm), None, _lib.ptr(rowptr), _lib.ptr(ws),
+        _lib.check(lib.tmf_stable_order_i32(k32, n, n_rows, perm, None, rowptr, ws,
                                             ws.numel(), _lib.stream_ptr()), lib)
         return perm, rowptr
     perm = torch.sort(keys, stable=True)[1]
@@ -158,8 +158,8 @@ class InteractionPlan:
             self.val_u = torch.empty(nnz, dtype=torch.float32, device=dev)
             self.user_of = torch.empty(nnz, dtype=torch.int32, device=dev)
             ws = torch.empty(lib.tmf_csr_build_workspace_bytes(nnz), dtype=torch.uint8, device=dev)
-            _lib.check(lib.tmf_csr_build(_lib.ptr(idx64), _lib.ptr(values), nnz, n_users, n_items, _lib.ptr(self.rowptr_u),
-                                         _lib.ptr(self.col_u), _lib.ptr(self.val_u), _lib.ptr(self.user_of), _lib.ptr(ws),
+            _lib.check(lib.tmf_csr_build(idx64, values, nnz, n_users, n_items, self.rowptr_u,
+                                         self.col_u, self.val_u, self.user_of, ws,
                                          ws.numel(), _lib.stream_ptr()), lib)
             del ws, idx64
         else:
@@ -409,7 +409,6 @@ class WmrbPlan:
         self.R_model = R  # the caller's table (model order): only D_in_model_order() reads it
         native = R.is_cuda
         lib = _lib.get() if native else None
-        i32 = ctypes.c_int32
         self.slice_off = self.pos_off = None
         if self.sliced:
             # every user's negatives in ascending item order (the order of s is immaterial to the loss); D is
@@ -418,15 +417,15 @@ class WmrbPlan:
             if native:
                 Rs = torch.empty_like(R)
                 ws = torch.empty(lib.tmf_sort_samples_workspace_bytes(m, S), dtype=torch.uint8, device=dev)
-                _lib.check(lib.tmf_sort_samples(_lib.ptr(R), i32(m), i32(S), i32(n), _lib.ptr(Rs), _lib.ptr(ws), ws.numel(),
+                _lib.check(lib.tmf_sort_samples(R, m, S, n, Rs, ws, ws.numel(),
                                                 _lib.stream_ptr()), lib)
                 del ws
                 self.slice_off = torch.empty(m, ns + 1, dtype=torch.int32, device=dev)
                 self.pos_off = torch.empty(m, ns + 1, dtype=torch.int32, device=dev)
-                _lib.check(lib.tmf_slice_offsets(_lib.ptr(Rs), None, S, i32(m), i32(n), i32(ns), _lib.ptr(self.slice_off),
+                _lib.check(lib.tmf_slice_offsets(Rs, None, S, m, n, ns, self.slice_off,
                                                  _lib.stream_ptr()), lib)
-                _lib.check(lib.tmf_slice_offsets(_lib.ptr(plan.col_u), _lib.ptr(plan.rowptr_u), 0, i32(m), i32(n), i32(ns),
-                                                 _lib.ptr(self.pos_off), _lib.stream_ptr()), lib)
+                _lib.check(lib.tmf_slice_offsets(plan.col_u, plan.rowptr_u, 0, m, n, ns,
+                                                 self.pos_off, _lib.stream_ptr()), lib)
             else:
                 Rs = torch.sort(R.to(torch.int64), dim=1, stable=True)[0].to(torch.int32).contiguous()
                 width = -(-n // ns)
@@ -445,9 +444,9 @@ class WmrbPlan:
         if native:
             ent_id = torch.empty(E, dtype=torch.int32, device=dev)
             ws = torch.empty(lib.tmf_wmrb_entry_lists_workspace_bytes(nnz, m, S), dtype=torch.uint8, device=dev)
-            _lib.check(lib.tmf_wmrb_entry_lists(_lib.ptr(plan.user_of), _lib.ptr(plan.col_u), _lib.ptr(plan.val_u), nnz,
-                                                _lib.ptr(self.R), i32(m), i32(S), i32(n), i32(C), _lib.ptr(self.ent_row),
-                                                _lib.ptr(ent_id), _lib.ptr(rowptr), _lib.ptr(ws), ws.numel(),
+            _lib.check(lib.tmf_wmrb_entry_lists(plan.user_of, plan.col_u, plan.val_u, nnz,
+                                                self.R, m, S, n, C, self.ent_row,
+                                                ent_id, rowptr, ws, ws.numel(),
                                                 _lib.stream_ptr()), lib)
             del ws
         else:
@@ -1172,15 +1171,15 @@ class BiasSide:
     def step(self, E, slab, adam, prof=None, tag=''):
         """From the gradient table G (filled by this epoch's pass): column sums -> bias step -> row update, which also rebuilds
         E = W + b in place.  Stream-ordered, nothing allocated, no host scalars: graph-capturable."""
-        lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
+        lib, s = _lib.get(), _lib.stream_ptr()
         rows = E.shape[0]
-        _timed(prof, tag + 'bias_colsum', lambda: lib.tmf_bias_colsum_f32(P(self.G), rows, self.r, P(self.part), self.part_rows, None, s))
-        _timed(prof, tag + 'bias_adam', lambda: lib.tmf_bias_adam_f32(P(self.part), self.part_rows, P(self.b), P(self.g_b), self.r, adam, s))
+        _timed(prof, tag + 'bias_colsum', lambda: lib.tmf_bias_colsum_f32(self.G, rows, self.r, self.part, self.part_rows, None, s))
+        _timed(prof, tag + 'bias_adam', lambda: lib.tmf_bias_adam_f32(self.part, self.part_rows, self.b, self.g_b, self.r, adam, s))
         if self.l2:   # the weights are penalised, the bias never: its step above saw the raw gradient
-            _timed(prof, tag + 'adam_bias_rows_l2', lambda: lib.tmf_adam_bias_rows_l2_f32(P(self.W), P(self.G), P(self.b), P(E), rows,
+            _timed(prof, tag + 'adam_bias_rows_l2', lambda: lib.tmf_adam_bias_rows_l2_f32(self.W, self.G, self.b, E, rows,
                                                                                           self.r, adam, self.l2, s))
             return
-        _timed(prof, tag + 'adam_bias_rows', lambda: lib.tmf_adam_bias_rows_f32(P(self.W), P(self.G), P(self.b), P(E), rows, self.r, adam, s))
+        _timed(prof, tag + 'adam_bias_rows', lambda: lib.tmf_adam_bias_rows_f32(self.W, self.G, self.b, E, rows, self.r, adam, s))
 
 
 class PlainL2Side:
@@ -1196,9 +1195,9 @@ class PlainL2Side:
 
     def step(self, E, slab, adam, prof=None, tag=''):
         """E = fresh-Adam(E, G + l2 E) in place.  Stream-ordered, no host scalars: graph-capturable."""
-        lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
+        lib, s = _lib.get(), _lib.stream_ptr()
         step = getattr(lib, 'tmf_adam_fresh_rows_l2' + self.sfx)
-        _timed(prof, tag + 'adam_rows_l2', lambda: step(P(E), P(self.G), E.shape[0], self.r, adam, self.l2, s))
+        _timed(prof, tag + 'adam_rows_l2', lambda: step(E, self.G, E.shape[0], self.r, adam, self.l2, s))
 
 
 class FeatureSide:
@@ -1231,16 +1230,16 @@ class FeatureSide:
     def _backward(self, slab, adam):
         """W_nxt[f] = fresh_adam(W[f], sum_i x_if G[i]) over the CSC lists (a feature no row carries keeps its weights), then the swap.
         With penalised weights (l2 > 0): the sums as a table of their own, then the regularised step in place and no swap."""
-        lib, s, P, p = _lib.get(), _lib.stream_ptr(), _lib.ptr, self.plan
+        lib, s, p = _lib.get(), _lib.stream_ptr(), self.plan
         if self.l2:
             # penalised weights: dW = F^T G into GW (a feature no row carries gets a zero row), then W = fresh-Adam(W, dW + l2 W) in
             # place over EVERY feature - one no row carries decays, its penalty gradient is not zero
-            _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(self.G), None, P(self.GW), P(slab),
+            _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), p.row_i, p.val_i, self.G, None, self.GW, slab,
                                              self.r, _lib.EPI_GRAD, adam, s), lib)
             _row_pass_finish(lib, p.seg_i, slab, None, self.GW, self.r, _lib.EPI_GRAD, adam, s)
-            _lib.check(lib.tmf_adam_fresh_rows_l2_f32(P(self.W), P(self.GW), self.W.shape[0], self.r, adam, self.l2, s), lib)
+            _lib.check(lib.tmf_adam_fresh_rows_l2_f32(self.W, self.GW, self.W.shape[0], self.r, adam, self.l2, s), lib)
             return
-        _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(self.G), P(self.W), P(self.W_nxt), P(slab),
+        _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), p.row_i, p.val_i, self.G, self.W, self.W_nxt, slab,
                                          self.r, _lib.EPI_ADAM, adam, s), lib)
         _row_pass_finish(lib, p.seg_i, slab, self.W, self.W_nxt, self.r, _lib.EPI_ADAM, adam, s)
         self.W, self.W_nxt = self.W_nxt, self.W
@@ -1248,9 +1247,9 @@ class FeatureSide:
 
 def feature_forward(plan, W, E, slab, r):
     """E = F W over the CSR lists of ``plan`` (every row of E is written; a row without entries becomes zeros)."""
-    lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
+    lib, s = _lib.get(), _lib.stream_ptr()
     adam = lib.tmf_adam_fresh(0.0)   # unused by the GRAD epilogue
-    _lib.check(lib.tmf_feat_pass_f32(plan.seg_u.cstruct(), P(plan.col_u), P(plan.val_u), P(W), None, P(E), P(slab), r,
+    _lib.check(lib.tmf_feat_pass_f32(plan.seg_u.cstruct(), plan.col_u, plan.val_u, W, None, E, slab, r,
                                      _lib.EPI_GRAD, adam, s), lib)
     _row_pass_finish(lib, plan.seg_u, slab, None, E, r, _lib.EPI_GRAD, adam, s)
 
@@ -1319,23 +1318,23 @@ class ReLUSide:
         the partials of dW = H^T G and dZ = (G W^T) . mask first, then W, then b from the column sums of dZ, then Wr from F^T dZ
         over the CSC lists (a feature no row carries keeps its weights); last the rebuilt Z = F Wr and E = relu(Z + b) W.
         Stream-ordered, nothing allocated, no host scalars, no atomics: graph-capturable and bit-reproducible."""
-        lib, s, P, p = _lib.get(), _lib.stream_ptr(), _lib.ptr, self.plan
+        lib, s, p = _lib.get(), _lib.stream_ptr(), self.plan
         rows, aux, r = self.rows, self.aux, self.r
-        _timed(prof, tag + 'relu_dweights', lambda: lib.tmf_relu_dweights_f32(P(self.Z), P(self.b), P(self.G), P(self.part),
+        _timed(prof, tag + 'relu_dweights', lambda: lib.tmf_relu_dweights_f32(self.Z, self.b, self.G, self.part,
                                                                               self.part_rows, rows, aux, r, s))
-        _timed(prof, tag + 'relu_dhidden', lambda: lib.tmf_relu_dhidden_f32(P(self.G), P(self.W), P(self.Z), P(self.b), P(self.dZ),
+        _timed(prof, tag + 'relu_dhidden', lambda: lib.tmf_relu_dhidden_f32(self.G, self.W, self.Z, self.b, self.dZ,
                                                                             rows, aux, r, s))
-        _timed(prof, tag + 'relu_adam_weights', lambda: lib.tmf_relu_adam_weights_f32(P(self.part), self.part_rows, P(self.W),
-                                                                                      P(self.W_nxt), None, aux, r, adam, s))
+        _timed(prof, tag + 'relu_adam_weights', lambda: lib.tmf_relu_adam_weights_f32(self.part, self.part_rows, self.W,
+                                                                                      self.W_nxt, None, aux, r, adam, s))
         self.W, self.W_nxt = self.W_nxt, self.W
-        _timed(prof, tag + 'relu_bias_colsum', lambda: lib.tmf_bias_colsum_f32(P(self.dZ), rows, aux, P(self.bias_part),
+        _timed(prof, tag + 'relu_bias_colsum', lambda: lib.tmf_bias_colsum_f32(self.dZ, rows, aux, self.bias_part,
                                                                                self.bias_part_rows, None, s))
-        _timed(prof, tag + 'relu_bias_adam', lambda: lib.tmf_bias_adam_f32(P(self.bias_part), self.bias_part_rows, P(self.b),
-                                                                           P(self.g_b), aux, adam, s))
+        _timed(prof, tag + 'relu_bias_adam', lambda: lib.tmf_bias_adam_f32(self.bias_part, self.bias_part_rows, self.b,
+                                                                           self.g_b, aux, adam, s))
 
         def hidden_backward():
-            _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(self.dZ), P(self.Wr), P(self.Wr_nxt),
-                                             P(slab), aux, _lib.EPI_ADAM, adam, s), lib)
+            _lib.check(lib.tmf_feat_pass_f32(p.seg_i.cstruct(), p.row_i, p.val_i, self.dZ, self.Wr, self.Wr_nxt,
+                                             slab, aux, _lib.EPI_ADAM, adam, s), lib)
             _row_pass_finish(lib, p.seg_i, slab, self.Wr, self.Wr_nxt, aux, _lib.EPI_ADAM, adam, s)
             self.Wr, self.Wr_nxt = self.Wr_nxt, self.Wr
         _timed(prof, tag + 'relu_feat_backward', hidden_backward)
@@ -1344,20 +1343,20 @@ class ReLUSide:
 
 def relu_forward(side, E, slab, prof=None, tag=''):
     """E = relu(F Wr + b) W from the side's current variables: the pre-activations over the CSR lists, then tmf_relu_embed_f32."""
-    lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
+    lib, s = _lib.get(), _lib.stream_ptr()
     _timed(prof, tag + 'relu_feat_forward', lambda: feature_forward(side.plan, side.Wr, side.Z, slab, side.aux))
-    _timed(prof, tag + 'relu_embed', lambda: lib.tmf_relu_embed_f32(P(side.Z), P(side.b), P(side.W), P(E), side.rows, side.aux,
+    _timed(prof, tag + 'relu_embed', lambda: lib.tmf_relu_embed_f32(side.Z, side.b, side.W, E, side.rows, side.aux,
                                                                     side.r, s))
 
 
 def embed_relu(F, side, chunk=DEFAULT_CHUNK):
     """relu(F Wr + b) W [rows, ld] for the variables of a trained ReLUSide on the GPU: the two forward kernels over a plan built for
     F alone - for the rows the fit saw, bit for bit the table it left."""
-    lib, s, P = _lib.get(), _lib.stream_ptr(), _lib.ptr
+    lib, s = _lib.get(), _lib.stream_ptr()
     rows, dev = int(F.shape[0]), side.W.device
     Z = embed_features(F, side.Wr, side.aux, chunk)
     E = torch.empty(rows, side.W.shape[1], dtype=torch.float32, device=dev)
-    _lib.check(lib.tmf_relu_embed_f32(P(Z), P(side.b), P(side.W), P(E), rows, side.aux, side.r, s), lib)
+    _lib.check(lib.tmf_relu_embed_f32(Z, side.b, side.W, E, rows, side.aux, side.r, s), lib)
     return E
 
 
@@ -1499,8 +1498,8 @@ def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=
 
 def _row_pass_finish(lib, seg, slab, X_old, X_out, r, epi, adam, stream, sfx='_f32'):
     if seg.n_long:
-        _lib.check(getattr(lib, 'tmf_combine_rows' + sfx)(_lib.ptr(seg.long_rows), _lib.ptr(seg.long_slab_beg), seg.n_long,
-                                            _lib.ptr(slab), _lib.ptr(X_old), _lib.ptr(X_out), r, epi, adam, stream), lib)
+        _lib.check(getattr(lib, 'tmf_combine_rows' + sfx)(seg.long_rows, seg.long_slab_beg, seg.n_long,
+                                            slab, X_old, X_out, r, epi, adam, stream), lib)
 
 
 def _list_passes(st, adam, entry, span, user_slot, item_slot, tail, loss_out, item_epi, item_out, prof, user_epi, user_out):
@@ -1509,17 +1508,17 @@ def _list_passes(st, adam, entry, span, user_slot, item_slot, tail, loss_out, it
     state's type suffix); span: prefix of the two span names; user_slot / item_slot: what the pass gets in its loss_part argument
     (None: nothing to write); tail: its arguments behind ``adam``; loss_out: where the user pass's per-segment loss sums (the
     state's loss_part) are added up, None = they are not."""
-    lib, p, r, s, P = _lib.get(), st.plan, st.r, _lib.stream_ptr(), _lib.ptr
+    lib, p, r, s = _lib.get(), st.plan, st.r, _lib.stream_ptr()
     run = getattr(lib, entry + st.sfx)
     U_out = st.U_nxt if user_out is None else user_out
-    _timed(prof, span + '_user_pass', lambda: run(p.seg_u.cstruct(), P(p.col_u), P(p.val_u), P(st.U), P(st.V), P(U_out), P(st.slab),
-                                                  P(user_slot), r, user_epi, adam, *tail, s))
+    _timed(prof, span + '_user_pass', lambda: run(p.seg_u.cstruct(), p.col_u, p.val_u, st.U, st.V, U_out, st.slab,
+                                                  user_slot, r, user_epi, adam, *tail, s))
     _row_pass_finish(lib, p.seg_u, st.slab, st.U, U_out, r, user_epi, adam, s, st.sfx)
     if loss_out is not None:
-        _lib.check(lib.tmf_sum_f32(P(st.loss_part), p.seg_u.nseg, P(loss_out), s), lib)
+        _lib.check(lib.tmf_sum_f32(st.loss_part, p.seg_u.nseg, loss_out, s), lib)
     V_out = st.V_nxt if item_out is None else item_out
-    _timed(prof, span + '_item_pass', lambda: run(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(st.V), P(st.U), P(V_out), P(st.slab),
-                                                  P(item_slot), r, item_epi, adam, *tail, s))
+    _timed(prof, span + '_item_pass', lambda: run(p.seg_i.cstruct(), p.row_i, p.val_i, st.V, st.U, V_out, st.slab,
+                                                  item_slot, r, item_epi, adam, *tail, s))
     _row_pass_finish(lib, p.seg_i, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx)
 
 
@@ -1547,8 +1546,8 @@ def epoch_kl(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=Non
     lib, p, r = _lib.get(), st.plan, st.r
     s = _lib.stream_ptr()
     _timed(prof, 'kl_moments', lambda: getattr(lib, 'tmf_kl_moments' + st.sfx)(
-        p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(st.kl_part), r, s))
-    _timed(prof, 'kl_coeffs', lambda: lib.tmf_kl_coeffs(_lib.ptr(st.kl_part), p.seg_u.nseg, _lib.ptr(loss_out), _lib.ptr(st.kl_coef), s))
+        p.seg_u.cstruct(), p.col_u, p.val_u, st.U, st.V, st.kl_part, r, s))
+    _timed(prof, 'kl_coeffs', lambda: lib.tmf_kl_coeffs(st.kl_part, p.seg_u.nseg, loss_out, st.kl_coef, s))
     _list_passes(st, adam, 'tmf_kl_pass', 'kl', st.kl_coef, st.kl_coef, (), None, item_epi, item_out, prof, user_epi, user_out)
 
 
@@ -1562,7 +1561,7 @@ def epoch_full_softmax(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None
     it (tmf_adam_fresh_rows_f32) and the two names change hands, so that the caller's swap() leaves the stepped table in U / V as after
     any other epoch - the same two buffers every epoch, whatever the number of epochs captured.
     Stream-ordered, nothing allocated, no host reads, no atomics: graph-capturable and bit-reproducible."""
-    lib, p, r, s, P = _lib.get(), st.plan, st.r, _lib.stream_ptr(), _lib.ptr
+    lib, p, r, s = _lib.get(), st.plan, st.r, _lib.stream_ptr()
     m, n, ld = p.n_users, p.n_items, st.ld
     for epi, out, nxt in ((user_epi, user_out, st.U_nxt), (item_epi, item_out, st.V_nxt)):
         if epi not in (_lib.EPI_ADAM, _lib.EPI_GRAD) or (epi == _lib.EPI_ADAM) != (out is None) or (out is None and nxt is None):
@@ -1570,23 +1569,23 @@ def epoch_full_softmax(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None
                              'its second buffer')
     G_U = st.U_nxt if user_out is None else user_out
     G_V = st.V_nxt if item_out is None else item_out
-    _timed(prof, 'fsm_lse', lambda: lib.tmf_fsm_lse_f32(P(st.U), P(st.V), m, n, r, ld, ld, P(st.fsm_lse), s))
-    _timed(prof, 'fsm_user_pass', lambda: lib.tmf_fsm_pos_pass_f32(p.seg_u.cstruct(), P(p.col_u), P(p.val_u), P(st.U), P(st.V), P(G_U),
-                                                                   P(st.slab), P(st.fsm_lse), P(st.loss_part), r, s))
+    _timed(prof, 'fsm_lse', lambda: lib.tmf_fsm_lse_f32(st.U, st.V, m, n, r, ld, ld, st.fsm_lse, s))
+    _timed(prof, 'fsm_user_pass', lambda: lib.tmf_fsm_pos_pass_f32(p.seg_u.cstruct(), p.col_u, p.val_u, st.U, st.V, G_U,
+                                                                   st.slab, st.fsm_lse, st.loss_part, r, s))
     _row_pass_finish(lib, p.seg_u, st.slab, st.U, G_U, r, _lib.EPI_GRAD, adam, s)
-    _lib.check(lib.tmf_sum_f32(P(st.loss_part), p.seg_u.nseg, P(loss_out), s), lib)
-    _timed(prof, 'fsm_item_pass', lambda: lib.tmf_fsm_pos_pass_f32(p.seg_i.cstruct(), P(p.row_i), P(p.val_i), P(st.V), P(st.U), P(G_V),
-                                                                   P(st.slab), None, None, r, s))
+    _lib.check(lib.tmf_sum_f32(st.loss_part, p.seg_u.nseg, loss_out, s), lib)
+    _timed(prof, 'fsm_item_pass', lambda: lib.tmf_fsm_pos_pass_f32(p.seg_i.cstruct(), p.row_i, p.val_i, st.V, st.U, G_V,
+                                                                   st.slab, None, None, r, s))
     _row_pass_finish(lib, p.seg_i, st.slab, st.V, G_V, r, _lib.EPI_GRAD, adam, s)
-    _timed(prof, 'fsm_wsum_user', lambda: lib.tmf_fsm_wsum_f32(P(st.U), P(st.V), m, n, r, ld, ld, P(st.fsm_lse), P(st.fsm_w), 1, P(G_U),
+    _timed(prof, 'fsm_wsum_user', lambda: lib.tmf_fsm_wsum_f32(st.U, st.V, m, n, r, ld, ld, st.fsm_lse, st.fsm_w, 1, G_U,
                                                                G_U.shape[1], s))
-    _timed(prof, 'fsm_wsum_item', lambda: lib.tmf_fsm_wsum_f32(P(st.V), P(st.U), n, m, r, ld, ld, P(st.fsm_lse), P(st.fsm_w), 0, P(G_V),
+    _timed(prof, 'fsm_wsum_item', lambda: lib.tmf_fsm_wsum_f32(st.V, st.U, n, m, r, ld, ld, st.fsm_lse, st.fsm_w, 0, G_V,
                                                                G_V.shape[1], s))
     if user_epi == _lib.EPI_ADAM:
-        _timed(prof, 'fsm_user_step', lambda: lib.tmf_adam_fresh_rows_f32(P(st.U), P(G_U), m, r, adam, s))
+        _timed(prof, 'fsm_user_step', lambda: lib.tmf_adam_fresh_rows_f32(st.U, G_U, m, r, adam, s))
         st.U, st.U_nxt = st.U_nxt, st.U
     if item_epi == _lib.EPI_ADAM:
-        _timed(prof, 'fsm_item_step', lambda: lib.tmf_adam_fresh_rows_f32(P(st.V), P(G_V), n, r, adam, s))
+        _timed(prof, 'fsm_item_step', lambda: lib.tmf_adam_fresh_rows_f32(st.V, G_V, n, r, adam, s))
         st.V, st.V_nxt = st.V_nxt, st.V
 
 
@@ -1599,7 +1598,6 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
     pairs='softmax': tmf_softmax_pairs (csrc/tmf_softmax.hip) there - the hinge kernel's arguments, c = 1 or n_items / n_samples; the
     loss does not depend on the order of a user's samples, so it takes sp and D as the plan keeps them."""
     p, w, r = st.plan, st.wplan, st.r
-    i32 = ctypes.c_int32
     m, S, ns = p.n_users, w.S, w.n_slices
     s = _lib.stream_ptr()
     lists = w.lists(p)
@@ -1607,58 +1605,58 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
     if s7 is not None and s7.sub_wave is not None:
         # item runs, the steps of a sub-chunk classed by fill: a pad slot costs no work (Scores7Plan.order_by_fill)
         _timed(prof, 'wmrb_scores', lambda: lib.tmf_wmrb_scores7_fill_f32(
-            _lib.ptr(s7.steps), _lib.ptr(s7.place), _lib.ptr(s7.sub_step), _lib.ptr(s7.sub_place), _lib.ptr(s7.chunk_sub),
-            _lib.ptr(s7.sub_wave), _lib.ptr(s7.sub_fill), s7.n_groups, i32(s7.n_slices), m, p.n_items, _lib.ptr(st.U), _lib.ptr(st.V),
-            _lib.ptr(st.sp), _lib.ptr(st.pk), r, s))
+            s7.steps, s7.place, s7.sub_step, s7.sub_place, s7.chunk_sub,
+            s7.sub_wave, s7.sub_fill, s7.n_groups, s7.n_slices, m, p.n_items, st.U, st.V,
+            st.sp, st.pk, r, s))
     elif s7 is not None:
         # item runs: one workgroup per (slice, group of 256 users) chunk, the group's rows in LDS, one load of a V row per run
         _timed(prof, 'wmrb_scores', lambda: lib.tmf_wmrb_scores7_f32(
-            _lib.ptr(s7.steps), _lib.ptr(s7.place), _lib.ptr(s7.sub_step), _lib.ptr(s7.sub_place), _lib.ptr(s7.chunk_sub), s7.n_groups,
-            i32(s7.n_slices), m, p.n_items, _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(st.sp), _lib.ptr(st.pk), r, s))
+            s7.steps, s7.place, s7.sub_step, s7.sub_place, s7.chunk_sub, s7.n_groups,
+            s7.n_slices, m, p.n_items, st.U, st.V, st.sp, st.pk, r, s))
     elif s6 is not None:
         # flat streams on the slice-major grid: one workgroup per (slice, group of 32 users) chunk, the group's rows in LDS
         _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores6' + st.sfx)(
-            _lib.ptr(s6.ids), _lib.ptr(s6.outs), _lib.ptr(s6.chunk_ptr), s6.n_groups, i32(s6.n_slices), m, p.n_items, _lib.ptr(st.U),
-            _lib.ptr(st.V), _lib.ptr(st.sp), _lib.ptr(st.pk), r, s))
+            s6.ids, s6.outs, s6.chunk_ptr, s6.n_groups, s6.n_slices, m, p.n_items, st.U,
+            st.V, st.sp, st.pk, r, s))
     elif s5 is not None:
         # row-stationary scores: workgroups own 256 users (rows in LDS) and walk one flat stream of (user, item) pairs
         _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores5' + st.sfx)(
-            _lib.ptr(s5.ids), _lib.ptr(s5.outs), _lib.ptr(s5.wg_ptr), s5.n_wg, m, p.n_items, _lib.ptr(st.U), _lib.ptr(st.V),
-            _lib.ptr(st.sp), _lib.ptr(st.pk), r, s5.wgs_per_launch, _lib.ptr(s5.wstart) if s5.paced else None, i32(s5.n_windows),
-            s5.lag, _lib.ptr(s5.sync) if s5.paced else None, s5.sync.numel() * 4, s))
+            s5.ids, s5.outs, s5.wg_ptr, s5.n_wg, m, p.n_items, st.U, st.V,
+            st.sp, st.pk, r, s5.wgs_per_launch, s5.wstart if s5.paced else None, s5.n_windows,
+            s5.lag, s5.sync if s5.paced else None, s5.sync.numel() * 4, s))
     else:
-        _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores3' + st.sfx)(lists, _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(st.sp),
-                                                                                _lib.ptr(st.pk), r, s))
+        _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores3' + st.sfx)(lists, st.U, st.V, st.sp,
+                                                                                st.pk, r, s))
     if pairs == 'bpr':
-        _timed(prof, 'bpr_pairs', lambda: lib.tmf_bpr_pairs(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk), _lib.ptr(st.sp),
-                                                            i32(m), i32(S), _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part),
-                                                            _lib.ptr(w.hinge_order), s))
+        _timed(prof, 'bpr_pairs', lambda: lib.tmf_bpr_pairs(p.rowptr_u, p.val_u, st.pk, st.sp,
+                                                            m, S, w.delta, w.D, st.loss_part,
+                                                            w.hinge_order, s))
     elif pairs == 'warp':
         # sp and D are in the plan's order (every user's negatives sorted by item); the trials run in the model's table order
         rank = w.sample_rank()
-        _timed(prof, 'warp_pairs', lambda: lib.tmf_warp_pairs_ranked(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk),
-                                                                     _lib.ptr(st.sp), _lib.ptr(rank), i32(m), i32(S), i32(p.n_items),
-                                                                     _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part),
-                                                                     _lib.ptr(w.hinge_order), s))
+        _timed(prof, 'warp_pairs', lambda: lib.tmf_warp_pairs_ranked(p.rowptr_u, p.val_u, st.pk,
+                                                                     st.sp, rank, m, S, p.n_items,
+                                                                     w.delta, w.D, st.loss_part,
+                                                                     w.hinge_order, s))
     elif pairs == 'softmax':
-        _timed(prof, 'softmax_pairs', lambda: lib.tmf_softmax_pairs(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk), _lib.ptr(st.sp),
-                                                                    i32(m), i32(S), c, _lib.ptr(w.delta), _lib.ptr(w.D),
-                                                                    _lib.ptr(st.loss_part), _lib.ptr(w.hinge_order), s))
+        _timed(prof, 'softmax_pairs', lambda: lib.tmf_softmax_pairs(p.rowptr_u, p.val_u, st.pk, st.sp,
+                                                                    m, S, c, w.delta, w.D,
+                                                                    st.loss_part, w.hinge_order, s))
     else:
-        _timed(prof, 'wmrb_hinge', lambda: lib.tmf_wmrb_hinge2_ordered(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(st.pk), _lib.ptr(st.sp),
-                                                                i32(m), i32(S), c, _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part),
-                                                                _lib.ptr(w.hinge_order), s))
+        _timed(prof, 'wmrb_hinge', lambda: lib.tmf_wmrb_hinge2_ordered(p.rowptr_u, p.val_u, st.pk, st.sp,
+                                                                m, S, c, w.delta, w.D, st.loss_part,
+                                                                w.hinge_order, s))
     if st.row_stationary:
         # gradU + finish in one row-stationary kernel (lane groups own users and walk the slices; no partial rows)
         _timed(prof, 'wmrb_gradu', lambda: getattr(lib, 'tmf_wmrb_gradu4' + st.sfx)(
-            lists, _lib.ptr(w.D), _lib.ptr(w.delta), _lib.ptr(st.V), _lib.ptr(st.U), _lib.ptr(st.U_nxt if U_out is None else U_out),
-            r, user_epi, adam, i32(st.users_per_launch), _lib.ptr(st.g4_sync), st.g4_sync.numel() * 4, s))
+            lists, w.D, w.delta, st.V, st.U, st.U_nxt if U_out is None else U_out,
+            r, user_epi, adam, st.users_per_launch, st.g4_sync, st.g4_sync.numel() * 4, s))
         return
     _timed(prof, 'wmrb_gradu', lambda: getattr(lib, 'tmf_wmrb_gradu3' + st.sfx)(
-        lists, _lib.ptr(w.D), _lib.ptr(w.delta), _lib.ptr(st.V), _lib.ptr(st.part),
+        lists, w.D, w.delta, st.V, st.part,
         st.gradu_launches, r, s))
-    _timed(prof, 'wmrb_finish', lambda: getattr(lib, 'tmf_wmrb_finish' + st.sfx)(_lib.ptr(st.part), i32(st.part_layers), i32(m),
-                                                                          _lib.ptr(st.U), _lib.ptr(st.U_nxt if U_out is None else U_out),
+    _timed(prof, 'wmrb_finish', lambda: getattr(lib, 'tmf_wmrb_finish' + st.sfx)(st.part, st.part_layers, m,
+                                                                          st.U, st.U_nxt if U_out is None else U_out,
                                                                           r, user_epi, adam, s))
 
 
@@ -1681,29 +1679,29 @@ def epoch_wmrb(st, adam, c, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, pro
         _timed(prof, 'wmrb_user_pass', lambda: _wmrb_user_pass_sliced(lib, st, adam, c, prof, user_epi, user_out, pairs))
     else:
         _timed(prof, 'wmrb_user_pass', lambda: getattr(lib, 'tmf_wmrb_user_pass' + st.sfx)(
-            _lib.ptr(p.rowptr_u), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(w.R), p.n_users, w.S, c, _lib.ptr(st.U), _lib.ptr(st.V),
-            _lib.ptr(st.U_nxt if user_out is None else user_out), _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(st.loss_part), None,
+            p.rowptr_u, p.col_u, p.val_u, w.R, p.n_users, w.S, c, st.U, st.V,
+            st.U_nxt if user_out is None else user_out, w.delta, w.D, st.loss_part, None,
             r, user_epi, adam, s))
-    _lib.check(lib.tmf_sum_f32(_lib.ptr(st.loss_part), p.n_users, _lib.ptr(loss_out), s), lib)
+    _lib.check(lib.tmf_sum_f32(st.loss_part, p.n_users, loss_out, s), lib)
     V_out = st.V_nxt if item_out is None else item_out
-    i32, v = ctypes.c_int32, w.vrows
+    v = w.vrows
     if not w.rows4:
         _timed(prof, 'wmrb_item_pass', lambda: getattr(lib, 'tmf_wsum_pass' + st.sfx)(
-            w.seg_e.cstruct(), _lib.ptr(w.ent_row), _lib.ptr(w.ent_w), _lib.ptr(w.wbuf), _lib.ptr(st.U), _lib.ptr(st.V), _lib.ptr(V_out),
-            _lib.ptr(st.slab), r, item_epi, adam, s))
+            w.seg_e.cstruct(), w.ent_row, w.ent_w, w.wbuf, st.U, st.V, V_out,
+            st.slab, r, item_epi, adam, s))
         _timed(prof, 'wmrb_combine', lambda: _row_pass_finish(lib, w.seg_e, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx))
     elif v is not None:
         # row-stationary item pass: lane groups own (virtual) rows and walk the user blocks; no slab but for the parts of cut rows
         _timed(prof, 'wmrb_item_pass', lambda: getattr(lib, 'tmf_wsum_rows5' + st.sfx)(
-            _lib.ptr(w.rowptr_e), i32(p.n_items), i32(w.user_chunks), _lib.ptr(w.ent_row), _lib.ptr(w.ent_w), _lib.ptr(w.wbuf), _lib.ptr(st.U),
-            _lib.ptr(st.V), _lib.ptr(V_out), _lib.ptr(st.slab), _lib.ptr(v.item), _lib.ptr(v.part), _lib.ptr(v.nparts), _lib.ptr(v.slot),
-            i32(v.n_vrows), r, item_epi, adam, i32(st.rows4_per_launch), _lib.ptr(st.rows4_sync), st.rows4_sync.numel() * 4, s))
+            w.rowptr_e, p.n_items, w.user_chunks, w.ent_row, w.ent_w, w.wbuf, st.U,
+            st.V, V_out, st.slab, v.item, v.part, v.nparts, v.slot,
+            v.n_vrows, r, item_epi, adam, st.rows4_per_launch, st.rows4_sync, st.rows4_sync.numel() * 4, s))
         if v.n_long:   # the cut rows: their parts' slab slots summed in part order (VirtualRows has a SegmentTable's long-row fields)
             _timed(prof, 'wmrb_combine', lambda: _row_pass_finish(lib, v, st.slab, st.V, V_out, r, item_epi, adam, s, st.sfx))
     else:
         _timed(prof, 'wmrb_item_pass', lambda: getattr(lib, 'tmf_wsum_rows4' + st.sfx)(
-            _lib.ptr(w.rowptr_e), i32(p.n_items), i32(w.user_chunks), _lib.ptr(w.ent_row), _lib.ptr(w.ent_w), _lib.ptr(w.wbuf), _lib.ptr(st.U),
-            _lib.ptr(st.V), _lib.ptr(V_out), r, item_epi, adam, i32(st.rows4_per_launch), _lib.ptr(st.rows4_sync),
+            w.rowptr_e, p.n_items, w.user_chunks, w.ent_row, w.ent_w, w.wbuf, st.U,
+            st.V, V_out, r, item_epi, adam, st.rows4_per_launch, st.rows4_sync,
             st.rows4_sync.numel() * 4, s))
 
 

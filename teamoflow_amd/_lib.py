@@ -2,9 +2,24 @@
 
 The engine has no CPU implementation: every entry point needs the gfx950 code object and a
 visible MI355X.  ``get()`` raises ``EngineUnavailable`` loudly instead of falling back to anything.
+
+include/tmf.h is the only statement of the ABI: ``parse_header`` reads the constants, the structs and
+the prototypes from it, and the ctypes structures and ``SIGNATURES`` are made from what it read.  An
+entry point is added by declaring it in the header.  The grammar ``parse_header`` accepts, and refuses
+to go beyond (``ValueError`` naming the declaration, never a default type):
+  - comments, ``#ifdef __cplusplus .. #endif`` blocks and preprocessor lines other than ``#define`` are dropped;
+  - ``#define TMF_NAME integer`` (the integer may stand in parentheses); a ``#define`` without a value is a guard;
+  - ``typedef struct tag { fields } name;`` with fields ``type a, b;`` or ``const type* a;`` - no arrays,
+    no nested structs;
+  - ``type tmf_name(void);`` and ``type tmf_name(type a, const type* b, ...);`` - every parameter named,
+    one declarator each, no arrays, no function pointers;
+  - type = int, int32_t, int64_t, size_t, float, double or a struct by value; pointers to those, to
+    uint16_t, void, a struct, and ``const char*``.
 """
+import collections
 import ctypes
 import os
+import re
 import subprocess
 
 import torch
@@ -12,8 +27,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TMF_LIB', os.path.join(_HERE, 'libtmf.so'))
 CSRC = os.path.join(_HERE, 'csrc')
-
-EPI_ADAM, EPI_GRAD = 0, 1
+HEADER_PATH = os.path.join(_HERE, os.pardir, 'include', 'tmf.h')
 
 
 class EngineUnavailable(RuntimeError):
@@ -24,174 +38,119 @@ class EngineError(RuntimeError):
     pass
 
 
-class Adam(ctypes.Structure):
-    _fields_ = [('alpha', ctypes.c_float), ('one_minus_b1', ctypes.c_float), ('one_minus_b2', ctypes.c_float),
-                ('eps', ctypes.c_float)]
+# constants: NAME -> int; structs: typedef name -> [(C type, field)]; functions: name -> (C return type, [C parameter types])
+Header = collections.namedtuple('Header', 'constants structs functions')
+_DECLARATOR = re.compile(r'(const\s+)?(\w+)(\s*\*\s*|\s+)(\w+(?:\s*,\s*\w+)*)')
 
 
-class SliceLists(ctypes.Structure):
-    _fields_ = [('R_sorted', ctypes.c_void_p), ('slice_off', ctypes.c_void_p), ('rowptr', ctypes.c_void_p),
-                ('col', ctypes.c_void_p), ('pos_off', ctypes.c_void_p), ('n_users', ctypes.c_int32),
-                ('n_samples', ctypes.c_int32), ('n_slices', ctypes.c_int32), ('slice_begin', ctypes.c_int32),
-                ('slice_count', ctypes.c_int32), ('item_base', ctypes.c_int32), ('flags', ctypes.c_int32),
-                ('n_items', ctypes.c_int32)]
+def _typed_names(decl, where):
+    """'const int32_t* a' -> ('const int32_t*', ['a']); 'float a, b' -> ('float', ['a', 'b'])."""
+    m = _DECLARATOR.fullmatch(decl.strip())
+    if not m:
+        raise ValueError(f'{where}: cannot read the declaration `{" ".join(decl.split())}`')
+    const, base, star, names = m.groups()
+    return ('const ' if const else '') + base + star.strip(), re.split(r'\s*,\s*', names)
 
 
-class Segments(ctypes.Structure):
-    _fields_ = [('rowptr', ctypes.c_void_p), ('seg_row', ctypes.c_void_p), ('seg_chunk', ctypes.c_void_p),
-                ('seg_slab', ctypes.c_void_p), ('nseg', ctypes.c_int64), ('chunk', ctypes.c_int32),
-                ('row_mod', ctypes.c_int32)]
+def parse_header(text):
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    text = re.sub(r'^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif\b', '', text, flags=re.S | re.M)
+    constants, structs, functions = {}, {}, {}
+    for name, value in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(TMF_\w+)[ \t]*(.*)$', text, re.M):
+        value = value.strip()
+        if value.startswith('(') and value.endswith(')'):
+            value = value[1:-1]
+        try:
+            if value:
+                constants[name] = int(value, 0)
+        except ValueError:
+            raise ValueError(f'#define {name}: `{value}` is not an integer') from None
+    text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+
+    def struct(m):
+        tag, body, name = m.groups()
+        if '{' in body:
+            raise ValueError(f'struct {tag}: nested braces')
+        structs[name] = [(ctype, field) for decl in body.split(';') if decl.strip()
+                         for ctype, fields in [_typed_names(decl, 'struct ' + name)] for field in fields]
+        return ''
+    text = re.sub(r'\btypedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;', struct, text, flags=re.S)
+    for decl in filter(str.strip, text.split(';')):
+        m = re.fullmatch(r'([^()]+)\((.*)\)', decl.strip(), re.S)
+        if not m:
+            raise ValueError(f'cannot read the declaration `{" ".join(decl.split())}`')
+        ret, (name,) = _typed_names(m.group(1), 'prototype')
+        params = [] if m.group(2).strip() == 'void' else m.group(2).split(',')
+        functions[name] = (ret, [_typed_names(p, name)[0] for p in params])
+    return Header(constants, structs, functions)
 
 
-class Exclusion(ctypes.Structure):
-    _fields_ = [('rowptr', ctypes.c_void_p), ('cols', ctypes.c_void_p), ('item_base', ctypes.c_int64)]
+_SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t,
+            'float': ctypes.c_float, 'double': ctypes.c_double}
+_POINTEE_BYTES = {'void': 0, 'uint16_t': 2, **{name: ctypes.sizeof(t) for name, t in _SCALARS.items()}}
 
 
-class RankRows(ctypes.Structure):
-    _fields_ = [('user', ctypes.c_void_p), ('begin', ctypes.c_void_p), ('count', ctypes.c_void_p), ('n_rows', ctypes.c_int64)]
+class TensorPointer(ctypes.c_void_p):
+    """The argtype of a data-pointer parameter: takes what c_void_p takes (None, an int, a c_void_p ..) and a torch.Tensor, whose
+    elements must have the size of the header's pointee type (void: any).  Size, not dtype: the engine reinterprets on purpose in
+    places.  No device and no contiguity check: plans are built on CPU tensors too, and views are legal arguments."""
+    pointee, pointee_bytes = 'void', 0
+
+    @classmethod
+    def from_param(cls, obj):
+        if isinstance(obj, torch.Tensor):
+            if cls.pointee_bytes and obj.element_size() != cls.pointee_bytes:
+                raise TypeError(f'a {obj.dtype} tensor ({obj.element_size()}-byte elements) for a `{cls.pointee}*` parameter')
+            return ctypes.c_void_p(obj.data_ptr())
+        return ctypes.c_void_p.from_param(obj)
 
 
-_P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-_EX = ctypes.POINTER(Exclusion)
-_RR = ctypes.POINTER(RankRows)
-_SEG = ctypes.POINTER(Segments)
-_SL = ctypes.POINTER(SliceLists)
-_I32, _SZ = ctypes.c_int32, ctypes.c_size_t
+_pointer_types = {'void': TensorPointer}
 
-# name -> (restype, argtypes); must list every symbol include/tmf.h declares (tests check this)
-SIGNATURES = {}
-_BASE_SIGNATURES = {
-    'tmf_version': (_I, []),
-    'tmf_last_error': (ctypes.c_char_p, []),
-    'tmf_padded_ld': (_I, [_I]),
-    'tmf_padded_ld_bf16': (_I, [_I]),
-    'tmf_adam_fresh': (Adam, [_F]),
-    'tmf_csr_build_workspace_bytes': (_SZ, [_L]),
-    'tmf_csr_build': (_I, [_P, _P, _L, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
-    'tmf_stable_order_workspace_bytes': (_SZ, [_L]),
-    'tmf_csc_perm': (_I, [_P, _L, _I32, _P, _P, _P, _SZ, _P]),
-    'tmf_stable_order_i32': (_I, [_P, _L, _L, _P, _P, _P, _P, _SZ, _P]),
-    'tmf_sort_samples_workspace_bytes': (_SZ, [_I32, _I32]),
-    'tmf_sort_samples': (_I, [_P, _I32, _I32, _I32, _P, _P, _SZ, _P]),
-    'tmf_slice_offsets': (_I, [_P, _P, _L, _I32, _I32, _I32, _P, _P]),
-    'tmf_wmrb_entry_lists_workspace_bytes': (_SZ, [_L, _I32, _I32]),
-    'tmf_wmrb_entry_lists': (_I, [_P, _P, _P, _L, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _SZ, _P]),
-    'tmf_mse_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
-    'tmf_kl_moments_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _I, _P]),
-    'tmf_kl_moments_bf16': (_I, [_SEG, _P, _P, _P, _P, _P, _I, _P]),
-    'tmf_kl_coeffs': (_I, [_P, _L, _P, _P, _P]),
-    'tmf_kl_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
-    'tmf_kl_pass_bf16': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
-    'tmf_logistic_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _I, _P]),
-    'tmf_logistic_pass_bf16': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _I, _P]),
-    'tmf_wsum_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
-    'tmf_wsum_rows4_rows_per_group': (_I, [_I, _I]),
-    'tmf_wsum_rows4_workspace_bytes': (_SZ, [_I32, _I32, _I32]),
-    'tmf_wsum_rows4_f32': (_I, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _I32, _P, _SZ, _P]),
-    'tmf_wsum_rows5_workspace_bytes': (_SZ, [_I32, _I32, _I32]),
-    'tmf_wsum_rows5_f32': (_I, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I, _I, Adam, _I32, _P, _SZ, _P]),
-    'tmf_combine_rows_f32': (_I, [_P, _P, _L, _P, _P, _P, _I, _I, Adam, _P]),
-    'tmf_wmrb_user_pass_f32': (_I, [_P, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
-    'tmf_wmrb_user_pass_fits': (_I, [_I32, _I]),
-    'tmf_wmrb_scores3_f32': (_I, [_SL, _P, _P, _P, _P, _I, _P]),
-    'tmf_wmrb_scores6_users_per_group': (_I, []),
-    'tmf_wmrb_scores6_supported': (_I, [_I, _I, _L]),
-    'tmf_wmrb_scores6_f32': (_I, [_P, _P, _P, _L, _I32, _L, _L, _P, _P, _P, _P, _I, _P]),
-    'tmf_wmrb_scores7_users_per_group': (_I, []),
-    'tmf_wmrb_scores7_slots': (_I, []),
-    'tmf_wmrb_scores7_waves': (_I, []),
-    'tmf_wmrb_scores7_fill_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I32, _L, _L, _P, _P, _P, _P, _I, _P]),
-    'tmf_wmrb_scores7_supported': (_I, [_I, _I, _L]),
-    'tmf_wmrb_scores7_f32': (_I, [_P, _P, _P, _P, _P, _L, _I32, _L, _L, _P, _P, _P, _P, _I, _P]),
-    'tmf_wmrb_scores5_users_per_workgroup': (_I, []),
-    'tmf_wmrb_scores5_supported': (_I, [_I, _I, _L]),
-    'tmf_wmrb_scores5_workspace_bytes': (_SZ, [_L, _I32, _I]),
-    'tmf_wmrb_scores5_f32': (_I, [_P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _I32, _I, _P, _SZ, _P]),
-    'tmf_wmrb_hinge2': (_I, [_P, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P]),
-    'tmf_wmrb_hinge2_ordered': (_I, [_P, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P, _P]),
-    'tmf_bpr_pairs': (_I, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
-    'tmf_warp_pairs': (_I, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
-    'tmf_warp_pairs_ranked': (_I, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
-    'tmf_softmax_pairs': (_I, [_P, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P, _P]),
-    'tmf_wmrb_gradu3_f32': (_I, [_SL, _P, _P, _P, _P, _I, _I, _P]),
-    'tmf_wmrb_gradu4_supported': (_I, [_I, _I]),
-    'tmf_wmrb_gradu4_workspace_bytes': (_SZ, [_I32, _I32, _I32]),
-    'tmf_wmrb_gradu4_f32': (_I, [_SL, _P, _P, _P, _P, _P, _I, _I, Adam, _I32, _P, _SZ, _P]),
-    'tmf_wmrb_finish_f32': (_I, [_P, _I32, _I32, _P, _P, _I, _I, Adam, _P]),
-    'tmf_adam_fresh_rows_f32': (_I, [_P, _P, _L, _I, Adam, _P]),
-    'tmf_bias_colsum_part_rows': (_L, [_L]),
-    'tmf_bias_colsum_f32': (_I, [_P, _L, _I, _P, _L, _P, _P]),
-    'tmf_bias_adam_f32': (_I, [_P, _L, _P, _P, _I, Adam, _P]),
-    'tmf_adam_bias_rows_f32': (_I, [_P, _P, _P, _P, _L, _I, Adam, _P]),
-    'tmf_feat_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
-    'tmf_relu_embed_f32': (_I, [_P, _P, _P, _P, _L, _I, _I, _P]),
-    'tmf_relu_dhidden_f32': (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _P]),
-    'tmf_relu_part_rows': (_L, [_L]),
-    'tmf_relu_dweights_f32': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _P]),
-    'tmf_relu_adam_weights_f32': (_I, [_P, _L, _P, _P, _P, _I, _I, Adam, _P]),
-    'tmf_adam_step': (Adam, [_F, _I]),
-    'tmf_adam_state_rows_f32': (_I, [_P, _P, _P, _P, _L, _I, Adam, _P]),
-    'tmf_adam_fresh_rows_l2_f32': (_I, [_P, _P, _L, _I, Adam, _F, _P]),
-    'tmf_adam_fresh_rows_l2_bf16': (_I, [_P, _P, _L, _I, Adam, _F, _P]),
-    'tmf_adam_state_rows_l2_f32': (_I, [_P, _P, _P, _P, _L, _I, Adam, _F, _P]),
-    'tmf_adam_bias_rows_l2_f32': (_I, [_P, _P, _P, _P, _L, _I, Adam, _F, _P]),
-    'tmf_mse_pass_bf16': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
-    'tmf_wsum_rows4_bf16': (_I, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _I32, _P, _SZ, _P]),
-    'tmf_wsum_rows5_bf16': (_I, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I, _I, Adam, _I32, _P, _SZ, _P]),
-    'tmf_wsum_pass_bf16': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
-    'tmf_combine_rows_bf16': (_I, [_P, _P, _L, _P, _P, _P, _I, _I, Adam, _P]),
-    'tmf_wmrb_user_pass_bf16': (_I, [_P, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, Adam, _P]),
-    'tmf_adam_fresh_rows_bf16': (_I, [_P, _P, _L, _I, Adam, _P]),
-    'tmf_sum_f32': (_I, [_P, _L, _P, _P]),
-    'tmf_gather_rows_cols_f32': (_I, [_P, _P, _P, _L, _L, _L, _P]),
-    'tmf_predict_gemm_f32': (_I, [_P, _P, _P, _L, _L, _I, _L, _L, _L, _P]),
-    'tmf_topk_workspace_bytes': (_SZ, [_L, _L, _I]),
-    'tmf_topk_stable_f32': (_I, [_P, _L, _L, _L, _I, _I, _P, _P, _P, _SZ, _P]),
-    'tmf_predict_topk_f32': (_I, [_P, _P, _L, _L, _I, _L, _L, _I, _I, _P, _P, _P]),
-    'tmf_predict_topk_bf16': (_I, [_P, _P, _L, _L, _I, _L, _L, _I, _I, _P, _P, _P]),
-    'tmf_predict_topk_split_supported': (_I, [_I, _I]),
-    'tmf_predict_topk_split_workspace_bytes': (_SZ, [_L, _I]),
-    'tmf_predict_topk_split_f32': (_I, [_P, _P, _L, _L, _I, _L, _L, _I, _I, _P, _P, _P, _SZ, _P]),
-    'tmf_predict_topk_half2_supported': (_I, [_I, _I]),
-    'tmf_predict_topk_half2_workspace_bytes': (_SZ, [_L, _I]),
-    'tmf_predict_topk_half2_f32': (_I, [_P, _P, _L, _L, _I, _L, _L, _I, _I, _P, _P, _P, _SZ, _P]),
-    'tmf_predict_topk_exclude_f32': (_I, [_P, _P, _L, _L, _I, _L, _L, _I, _I, _EX, _P, _P, _P]),
-    'tmf_predict_topk_exclude_bf16': (_I, [_P, _P, _L, _L, _I, _L, _L, _I, _I, _EX, _P, _P, _P]),
-    'tmf_predict_topk_split_exclude_f32': (_I, [_P, _P, _L, _L, _I, _L, _L, _I, _I, _EX, _P, _P, _P, _SZ, _P]),
-    'tmf_predict_topk_half2_exclude_f32': (_I, [_P, _P, _L, _L, _I, _L, _L, _I, _I, _EX, _P, _P, _P, _SZ, _P]),
-    'tmf_topk_stable_exclude_f32': (_I, [_P, _L, _L, _L, _I, _I, _EX, _P, _P, _P, _SZ, _P]),
-    'tmf_pair_scores_f32': (_I, [_P, _P, _I, _L, _L, _P, _P, _L, _P, _P]),
-    'tmf_pair_scores_split': (_I, [_P, _P, _I, _L, _L, _P, _P, _L, _P, _P]),
-    'tmf_item_ranks_f32_supported': (_I, [_I]),
-    'tmf_item_ranks_split_supported': (_I, [_I]),
-    'tmf_item_ranks_split_workspace_bytes': (_SZ, [_L, _I]),
-    'tmf_item_ranks_f32': (_I, [_P, _P, _L, _I, _L, _L, _RR, _P, _P, _EX, _P, _P]),
-    'tmf_item_ranks_split': (_I, [_P, _P, _L, _I, _L, _L, _RR, _P, _P, _EX, _P, _P, _SZ, _P]),
-    'tmf_rank_count_rows_f32': (_I, [_P, _L, _L, _L, _L, _RR, _P, _EX, _P, _P]),
-    'tmf_dcg_idcg_f32': (_I, [_P, _P, _P, _L, _L, _P, _L, _I, _P, _P, _P, _P, _P]),
-    'tmf_unit_rows_f32': (_I, [_P, _L, _I, _L, _P, _L, _P, _L, _P, _P]),
-    'tmf_unit_rows_bf16': (_I, [_P, _L, _I, _L, _P, _L, _P, _L, _P, _P]),
-    'tmf_gram_workspace_bytes': (_SZ, [_L, _I]),
-    'tmf_gram_f32': (_I, [_P, _L, _I, _L, _P, _L, _P, _SZ, _P]),
-    'tmf_als_solve_rows_f32': (_I, [_P, _L, _I, _L, _P, _L, _P, _P, _P, _P, _F, _P, _L, _P, _L, _P, _P]),
-    'tmf_gram_wide_workspace_bytes': (_SZ, [_L, _I]),
-    'tmf_gram_wide_f32': (_I, [_P, _L, _I, _L, _P, _L, _P, _SZ, _P]),
-    'tmf_als_cg_rows_f32': (_I, [_P, _L, _I, _L, _P, _L, _P, _P, _P, _P, _F, _P, _L, _P, _L, _P, _L, _I, _P, _P]),
-    'tmf_sample_rows_supported': (_I, [_I32, _I32]),
-    'tmf_sample_rows': (_I, [_I32, _L, _I32, _L, _L, _P, _P, _P]),
-    'tmf_fsm_max_components': (_I, []),
-    'tmf_fsm_lse_f32': (_I, [_P, _P, _L, _L, _I, _L, _L, _P, _P]),
-    'tmf_fsm_wsum_f32': (_I, [_P, _P, _L, _L, _I, _L, _L, _P, _P, _I, _P, _L, _P]),
-    'tmf_fsm_pos_pass_f32': (_I, [_SEG, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
-}
 
-SIGNATURES.update(_BASE_SIGNATURES)
-for _name in ('tmf_wmrb_scores3', 'tmf_wmrb_scores5', 'tmf_wmrb_scores6', 'tmf_wmrb_gradu3', 'tmf_wmrb_gradu4', 'tmf_wmrb_finish'):
-    SIGNATURES[_name + '_bf16'] = SIGNATURES[_name + '_f32']
+def tensor_pointer(pointee):
+    """One TensorPointer class per pointee type, so that two prototypes with the same C types have equal argtypes."""
+    if pointee not in _pointer_types:
+        _pointer_types[pointee] = type(pointee + '_p', (TensorPointer,), {'pointee': pointee, 'pointee_bytes': _POINTEE_BYTES[pointee]})
+    return _pointer_types[pointee]
+
+
+def _ctype(ctype, structs, where, field=False):
+    base = ctype.replace('const ', '').rstrip('*')
+    if not ctype.endswith('*'):
+        t = _SCALARS.get(base) or structs.get(base)
+    elif base in structs:
+        t = ctypes.POINTER(structs[base])
+    elif base in _POINTEE_BYTES:           # a struct's pointers stay untyped: they are filled in from data_ptr() sums
+        t = ctypes.c_void_p if field else tensor_pointer(base)
+    else:
+        t = ctypes.c_char_p if ctype == 'const char*' else None
+    if t is None:
+        raise ValueError(f'{where}: unknown type `{ctype}`')
+    return t
+
+
+def bind(header):
+    """The ctypes side of a parsed header: ({typedef name: Structure class}, {name: (restype, argtypes)})."""
+    structs = {}
+    for name, fields in header.structs.items():
+        fields = [(f, _ctype(t, structs, f'struct {name}', field=True)) for t, f in fields]
+        structs[name] = type(name[4:].title().replace('_', ''), (ctypes.Structure,), {'_fields_': fields})   # tmf_slice_lists: SliceLists
+    return structs, {name: (_ctype(ret, structs, name), [_ctype(t, structs, name) for t in args])
+                     for name, (ret, args) in header.functions.items()}
+
+
+with open(HEADER_PATH) as _fh:
+    HEADER = parse_header(_fh.read())
+_STRUCTS, SIGNATURES = bind(HEADER)   # SIGNATURES: name -> (restype, argtypes)
+Adam, Segments, SliceLists, Exclusion, RankRows = (_STRUCTS[_n] for _n in ('tmf_adam', 'tmf_segments', 'tmf_slice_lists',
+                                                                           'tmf_exclusion', 'tmf_rank_rows'))
+_F, _P = ctypes.c_float, tensor_pointer('void')   # `float`, and `void*` (the stream, a workspace)
+MIN_LIB_VERSION = HEADER.constants['TMF_VERSION']
+EPI_ADAM, EPI_GRAD = HEADER.constants['TMF_EPI_ADAM'], HEADER.constants['TMF_EPI_GRAD']
+SLICE_XCD_MAJOR, SLICE_N_ITEMS_STATED = HEADER.constants['TMF_SLICE_XCD_MAJOR'], HEADER.constants['TMF_SLICE_N_ITEMS_STATED']   # tmf_slice_lists.flags
 
 _lib = None
-MIN_LIB_VERSION = 203   # include/tmf.h TMF_VERSION: 203 = tmf_wsum_rows5, tmf_slice_lists.flags (72-byte struct; n_items counts only with SLICE_N_ITEMS_STATED)
-SLICE_XCD_MAJOR, SLICE_N_ITEMS_STATED = 1, 2   # tmf_slice_lists.flags
 
 
 def build(force=False, verbose=False):

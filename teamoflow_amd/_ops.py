@@ -49,7 +49,7 @@ def predict_gemm(user_embedding, item_embedding, out=None):
         raise ValueError(f'out must be a CUDA float32 [{m}, {n}] tensor with unit column stride and a row stride >= {n}, got '
                          + (f'{out.dtype} {tuple(out.shape)} on {out.device}, strides {tuple(out.stride())}' if torch.is_tensor(out)
                             else type(out).__name__))
-    _lib.check(lib.tmf_predict_gemm_f32(_lib.ptr(A), _lib.ptr(B), _lib.ptr(out), m, n, r, lda, ldb, out.stride(0),
+    _lib.check(lib.tmf_predict_gemm_f32(A, B, out, m, n, r, lda, ldb, out.stride(0),
                                         _lib.stream_ptr()), lib)
     return out
 
@@ -288,12 +288,12 @@ def predict_topk(user_embedding, item_embedding, k, clamp_negatives=False, retur
         """tmf_predict_topk_<form>, or its _exclude twin with the exclusion struct; the plane forms take their workspace."""
         name = {'f32': 'tmf_predict_topk_%sf32', 'bf16': 'tmf_predict_topk_%sbf16', 'split': 'tmf_predict_topk_split_%sf32',
                 'half2': 'tmf_predict_topk_half2_%sf32'}[form] % ('' if ex is None else 'exclude_')
-        args = [_lib.ptr(A), _lib.ptr(B), m, n, r, lda, ldb, k, int(bool(clamp_negatives))]
+        args = [A, B, m, n, r, lda, ldb, k, int(bool(clamp_negatives))]
         if ex is not None:
             args.append(ctypes.byref(ex.struct(m)))
-        args += [_lib.ptr(idx), _lib.ptr(vals)]
+        args += [idx, vals]
         if ws is not None:
-            args += [_lib.ptr(ws), ws.numel()]
+            args += [ws, ws.numel()]
         _lib.check(getattr(lib, name)(*args, _lib.stream_ptr()), lib)   # looked up per call: tests wrap the entry points of lib
         return (vals, idx) if return_values else idx
 
@@ -350,10 +350,10 @@ def topk_stable(x, k, clamp_negatives=False, return_values=False, exclude=None, 
         need = lib.tmf_topk_workspace_bytes(e - b, cols, k)
         if need and (ws is None or ws.numel() < need):
             ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        args = [_lib.ptr(x[b:e]), e - b, cols, x.stride(0), k, int(bool(clamp_negatives))]
+        args = [x[b:e], e - b, cols, x.stride(0), k, int(bool(clamp_negatives))]
         if ex is not None:
             args.append(ctypes.byref(ex.shifted(b).struct(e - b)))
-        _lib.check(run(*args, _lib.ptr(idx[b:e]), _lib.ptr(vals[b:e]) if return_values else None, _lib.ptr(ws),
+        _lib.check(run(*args, idx[b:e], vals[b:e] if return_values else None, ws,
                        ws.numel() if ws is not None else 0, _lib.stream_ptr()), lib)
     if squeeze:
         idx = idx[0]
@@ -373,7 +373,7 @@ def gather_rows_cols(x, idx):
     if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= cols):
         raise IndexError('column index out of range')
     out = torch.empty(rows, k, dtype=torch.float32, device=x.device)
-    _lib.check(lib.tmf_gather_rows_cols_f32(_lib.ptr(x), _lib.ptr(idx), _lib.ptr(out), rows, cols, k,
+    _lib.check(lib.tmf_gather_rows_cols_f32(x, idx, out, rows, cols, k,
                                             _lib.stream_ptr()), lib)
     return out
 
@@ -419,7 +419,7 @@ def unit_rows(table, ids=None, return_norms=False):
     out = torch.empty(q, ldo, dtype=torch.float32, device=T.device)
     norms = torch.empty(q, dtype=torch.float32, device=T.device) if return_norms else None
     run = lib.tmf_unit_rows_bf16 if bf16 else lib.tmf_unit_rows_f32
-    _lib.check(run(_lib.ptr(T), n, r, ldt, _lib.ptr(ids), q, _lib.ptr(out), ldo, _lib.ptr(norms), _lib.stream_ptr()), lib)
+    _lib.check(run(T, n, r, ldt, ids, q, out, ldo, norms, _lib.stream_ptr()), lib)
     return (out[:, :r], norms) if return_norms else out[:, :r]
 
 
@@ -617,16 +617,16 @@ def item_ranks(user_embedding, item_embedding, positives, exclude=None, arithmet
     pair_user = _csr_rows(pos.rowptr).to(torch.int32)
     scores = torch.empty(P, dtype=torch.float32, device=dev)
     pair_fn = lib.tmf_pair_scores_f32 if ws is None else lib.tmf_pair_scores_split
-    _lib.check(pair_fn(_lib.ptr(A), _lib.ptr(B), r, lda, ldb, _lib.ptr(pair_user), _lib.ptr(pos.cols), P, _lib.ptr(scores),
+    _lib.check(pair_fn(A, B, r, lda, ldb, pair_user, pos.cols, P, scores,
                        _lib.stream_ptr()), lib)
     rows = _rank_rows(vu, vb, vc)
     exs = None if ex is None else ctypes.byref(ex.struct(m))
     if ws is None:
-        _lib.check(lib.tmf_item_ranks_f32(_lib.ptr(A), _lib.ptr(B), n, r, lda, ldb, ctypes.byref(rows), _lib.ptr(pos.cols),
-                                          _lib.ptr(scores), exs, _lib.ptr(ranks), _lib.stream_ptr()), lib)
+        _lib.check(lib.tmf_item_ranks_f32(A, B, n, r, lda, ldb, ctypes.byref(rows), pos.cols,
+                                          scores, exs, ranks, _lib.stream_ptr()), lib)
     else:
-        _lib.check(lib.tmf_item_ranks_split(_lib.ptr(A), _lib.ptr(B), n, r, lda, ldb, ctypes.byref(rows), _lib.ptr(pos.cols),
-                                            _lib.ptr(scores), exs, _lib.ptr(ranks), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), lib)
+        _lib.check(lib.tmf_item_ranks_split(A, B, n, r, lda, ldb, ctypes.byref(rows), pos.cols,
+                                            scores, exs, ranks, ws, ws.numel(), _lib.stream_ptr()), lib)
     return out
 
 
@@ -646,8 +646,8 @@ def _item_ranks_blocks(lib, U, V, pos, ex, vu, vb, vc, ranks):
             continue
         X = predict_gemm(U[b:e].float(), Vf)
         rows = _rank_rows(vu, vb, vc, lo, hi)
-        _lib.check(lib.tmf_rank_count_rows_f32(_lib.ptr(X), e - b, n, X.stride(0), b, ctypes.byref(rows), _lib.ptr(pos.cols), exs,
-                                               _lib.ptr(ranks), _lib.stream_ptr()), lib)
+        _lib.check(lib.tmf_rank_count_rows_f32(X, e - b, n, X.stride(0), b, ctypes.byref(rows), pos.cols, exs,
+                                               ranks, _lib.stream_ptr()), lib)
 
 
 def auc_from_ranks(rowptr, ranks, n_items, excluded=None):
@@ -705,8 +705,8 @@ def graded_csr(A, n_users, n_items, device=None):
         rows = torch.empty(nnz, dtype=torch.int32, device=dev)
         ws = torch.empty(lib.tmf_csr_build_workspace_bytes(nnz), dtype=torch.uint8, device=dev)
         pairs = torch.stack([u, i], 1)
-        _lib.check(lib.tmf_csr_build(_lib.ptr(pairs), _lib.ptr(val), nnz, n_users, n_items, _lib.ptr(rowptr), _lib.ptr(cols),
-                                     _lib.ptr(vals), _lib.ptr(rows), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), lib)
+        _lib.check(lib.tmf_csr_build(pairs, val, nnz, n_users, n_items, rowptr, cols,
+                                     vals, rows, ws, ws.numel(), _lib.stream_ptr()), lib)
         del ws, pairs
     else:
         key = u * n_items + i
@@ -763,8 +763,8 @@ def dcg_idcg(table, top, k, n_zero=None, want_dcg=True, want_idcg=True):
             raise ValueError(f'top must be [{m}, >= {k}] int32 with unit column stride, got {tuple(top.shape)}')
         ldt = top.stride(0)
     nz = None if n_zero is None else _cuda(n_zero, torch.int64).contiguous()
-    _lib.check(lib.tmf_dcg_idcg_f32(_lib.ptr(rowptr), _lib.ptr(cols), _lib.ptr(gain), m, n, _lib.ptr(top) if want_dcg else None, ldt, k,
-                                    _lib.ptr(den), _lib.ptr(nz), _lib.ptr(dcg), _lib.ptr(idcg), _lib.stream_ptr()), lib)
+    _lib.check(lib.tmf_dcg_idcg_f32(rowptr, cols, gain, m, n, top if want_dcg else None, ldt, k,
+                                    den, nz, dcg, idcg, _lib.stream_ptr()), lib)
     return dcg, idcg
 
 
@@ -803,7 +803,7 @@ def gram(table):
     size, run = ((lib.tmf_gram_workspace_bytes, lib.tmf_gram_f32) if r <= ALS_MAX_COMPONENTS
                  else (lib.tmf_gram_wide_workspace_bytes, lib.tmf_gram_wide_f32))
     ws = torch.empty(size(n, r), dtype=torch.uint8, device=T.device)
-    _lib.check(run(_lib.ptr(T), n, r, ldt, _lib.ptr(G), r, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), lib)
+    _lib.check(run(T, n, r, ldt, G, r, ws, ws.numel(), _lib.stream_ptr()), lib)
     return G
 
 
@@ -864,9 +864,9 @@ def als_solve_rows(Y, rowptr, col, w, t, reg, G0=None, ids=None, out=None, n_fai
     and CSR checks (a caller that has made them once)."""
     o = _als_row_operands('als_solve_rows', ALS_MAX_COMPONENTS, Y, rowptr, col, w, t, reg, G0, ids, out, n_failed, check)
     lib = _lib.get()
-    _lib.check(lib.tmf_als_solve_rows_f32(_lib.ptr(o['Y']), o['n_other'], o['r'], o['ldy'], _lib.ptr(o['g0']), o['ldg'],
-                                          _lib.ptr(o['rowptr']), _lib.ptr(o['col']), _lib.ptr(o['w']), _lib.ptr(o['t']), o['reg'],
-                                          _lib.ptr(o['ids']), o['q'], _lib.ptr(o['out']), o['ldx'], _lib.ptr(o['n_failed']),
+    _lib.check(lib.tmf_als_solve_rows_f32(o['Y'], o['n_other'], o['r'], o['ldy'], o['g0'], o['ldg'],
+                                          o['rowptr'], o['col'], o['w'], o['t'], o['reg'],
+                                          o['ids'], o['q'], o['out'], o['ldx'], o['n_failed'],
                                           _lib.stream_ptr()), lib)
     return o['out'], o['n_failed']
 
@@ -898,9 +898,9 @@ def als_cg_rows(Y, rowptr, col, w, t, reg, G0=None, ids=None, x0=None, out=None,
             x0t, _, _, ldx0 = _operand(_table_2d(x0, 'x0'))
             if n_rows and _overlap(x0t, n_rows, ldx0, X, ldx):
                 raise ValueError('als_cg_rows: x0 and out overlap without being the same view')
-    _lib.check(lib.tmf_als_cg_rows_f32(_lib.ptr(o['Y']), o['n_other'], r, o['ldy'], _lib.ptr(o['g0']), o['ldg'], _lib.ptr(o['rowptr']),
-                                       _lib.ptr(o['col']), _lib.ptr(o['w']), _lib.ptr(o['t']), o['reg'], _lib.ptr(o['ids']), o['q'],
-                                       _lib.ptr(x0t), ldx0, _lib.ptr(X), ldx, cg_steps, _lib.ptr(o['n_failed']), _lib.stream_ptr()), lib)
+    _lib.check(lib.tmf_als_cg_rows_f32(o['Y'], o['n_other'], r, o['ldy'], o['g0'], o['ldg'], o['rowptr'],
+                                       o['col'], o['w'], o['t'], o['reg'], o['ids'], o['q'],
+                                       x0t, ldx0, X, ldx, cg_steps, o['n_failed'], _lib.stream_ptr()), lib)
     return X, o['n_failed']
 
 
@@ -917,8 +917,8 @@ def pair_scores(A, B, pair_a, pair_b):
     Bt, _, _, ldb = _operand(B)
     out = torch.empty(pair_a.numel(), dtype=torch.float32, device=At.device)
     if pair_a.numel():
-        _lib.check(lib.tmf_pair_scores_f32(_lib.ptr(At), _lib.ptr(Bt), r, lda, ldb, _lib.ptr(pair_a), _lib.ptr(pair_b), pair_a.numel(),
-                                           _lib.ptr(out), _lib.stream_ptr()), lib)
+        _lib.check(lib.tmf_pair_scores_f32(At, Bt, r, lda, ldb, pair_a, pair_b, pair_a.numel(),
+                                           out, _lib.stream_ptr()), lib)
     return out
 
 
@@ -952,7 +952,7 @@ def sample_negatives(n_items, n_users, n_samples, seed=0, device=None, user_offs
     with torch.cuda.device(out.device if out is not None else device):
         R = torch.empty(n_users, n_samples, dtype=torch.int32, device=device) if out is None else out
         failed = torch.zeros(1, dtype=torch.int32, device=R.device)
-        _lib.check(lib.tmf_sample_rows(n_items, n_users, n_samples, seed, user_offset, _lib.ptr(R), _lib.ptr(failed), _lib.stream_ptr()),
+        _lib.check(lib.tmf_sample_rows(n_items, n_users, n_samples, seed, user_offset, R, failed, _lib.stream_ptr()),
                    lib)
         if n_users and int(failed):
             raise RuntimeError('could not draw distinct samples')

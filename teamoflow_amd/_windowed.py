@@ -107,30 +107,28 @@ class WindowedHipBackend:
         lib = _lib.get()
         if self.m == 0:
             return
-        _lib.check(getattr(lib, 'tmf_wmrb_scores3' + self.sfx)(ctypes.byref(self.lists[t]), _lib.ptr(self.U), _lib.ptr(Vwin),
-                                                               _lib.ptr(self.sp), _lib.ptr(self.pk), self.r, _lib.stream_ptr()), lib)
+        _lib.check(getattr(lib, 'tmf_wmrb_scores3' + self.sfx)(ctypes.byref(self.lists[t]), self.U, Vwin,
+                                                               self.sp, self.pk, self.r, _lib.stream_ptr()), lib)
 
     def between(self):
         """WMRB: hinge step over the complete scores -> delta, D, per-user loss."""
         lib, p, w = _lib.get(), self.plan, self.wplan
-        i32 = ctypes.c_int32
-        _lib.check(lib.tmf_wmrb_hinge2_ordered(_lib.ptr(p.rowptr_u), _lib.ptr(p.val_u), _lib.ptr(self.pk), _lib.ptr(self.sp), i32(self.m),
-                                               i32(w.S), self.c, _lib.ptr(w.delta), _lib.ptr(w.D), _lib.ptr(self.loss_part),
-                                               _lib.ptr(getattr(w, 'hinge_order', None)), _lib.stream_ptr()), lib)
+        _lib.check(lib.tmf_wmrb_hinge2_ordered(p.rowptr_u, p.val_u, self.pk, self.sp, self.m,
+                                               w.S, self.c, w.delta, w.D, self.loss_part,
+                                               getattr(w, 'hinge_order', None), _lib.stream_ptr()), lib)
 
     def grads_window(self, t, Vwin, out):
         """Adds the window's part of the user gradient to layer 0 of ``part`` and writes the raw item gradient of the
         window's rows (this rank's users only) into ``out`` [rows, ld] fp32."""
         lib, s, r = _lib.get(), _lib.stream_ptr(), self.r
-        i32 = ctypes.c_int32
         if self.loss == 'wmrb':
             w = self.wplan
             if self.m:
-                _lib.check(getattr(lib, 'tmf_wmrb_gradu3' + self.sfx)(ctypes.byref(self.lists[t]), _lib.ptr(w.D), _lib.ptr(w.delta),
-                                                                      _lib.ptr(Vwin), _lib.ptr(self.part), 1 if t == 0 else 2, r, s), lib)
+                _lib.check(getattr(lib, 'tmf_wmrb_gradu3' + self.sfx)(ctypes.byref(self.lists[t]), w.D, w.delta,
+                                                                      Vwin, self.part, 1 if t == 0 else 2, r, s), lib)
             seg = self.seg[t]
-            _lib.check(getattr(lib, 'tmf_wsum_pass' + self.sfx)(seg.cstruct(), _lib.ptr(w.ent_row), _lib.ptr(w.ent_w), _lib.ptr(w.wbuf),
-                                                                _lib.ptr(self.U), None, _lib.ptr(out), _lib.ptr(self.slab), r,
+            _lib.check(getattr(lib, 'tmf_wsum_pass' + self.sfx)(seg.cstruct(), w.ent_row, w.ent_w, w.wbuf,
+                                                                self.U, None, out, self.slab, r,
                                                                 _lib.EPI_GRAD, self.adam, s), lib)
             _engine._row_pass_finish(lib, seg, self.slab, None, out, r, _lib.EPI_GRAD, self.adam, s, self.sfx)
             return
@@ -147,26 +145,25 @@ class WindowedHipBackend:
             raise ValueError(f'WindowedHipBackend: unknown loss {self.loss!r}')
         layer = self.part[:self.m] if t == 0 else self.part[self.m:2 * self.m]
         if self.m:
-            _lib.check(row_pass(p.seg_u.cstruct(), _lib.ptr(p.col_u), _lib.ptr(p.val_u), _lib.ptr(self.U), _lib.ptr(Vwin),
-                                _lib.ptr(layer), _lib.ptr(self.slab), _lib.ptr(self.loss_part), r, _lib.EPI_GRAD, self.adam, s), lib)
+            _lib.check(row_pass(p.seg_u.cstruct(), p.col_u, p.val_u, self.U, Vwin,
+                                layer, self.slab, self.loss_part, r, _lib.EPI_GRAD, self.adam, s), lib)
             _engine._row_pass_finish(lib, p.seg_u, self.slab, self.U, layer, r, _lib.EPI_GRAD, self.adam, s, self.sfx)
             if t:   # layer 0 += layer 1 (the finish kernel sums layers row by row; reading and writing row u in one thread)
-                _lib.check(getattr(lib, 'tmf_wmrb_finish' + self.sfx)(_lib.ptr(self.part), i32(2), i32(self.m), None,
-                                                                      _lib.ptr(self.part), r, _lib.EPI_GRAD, self.adam, s), lib)
-        _lib.check(lib.tmf_sum_f32(_lib.ptr(self.loss_part), p.seg_u.nseg, _lib.ptr(self.loss_w[t:t + 1]), s), lib)
-        _lib.check(row_pass(p.seg_i.cstruct(), _lib.ptr(p.row_i), _lib.ptr(p.val_i), _lib.ptr(Vwin), _lib.ptr(self.U),
-                            _lib.ptr(out), _lib.ptr(self.slab), None, r, _lib.EPI_GRAD, self.adam, s), lib)
+                _lib.check(getattr(lib, 'tmf_wmrb_finish' + self.sfx)(self.part, 2, self.m, None,
+                                                                      self.part, r, _lib.EPI_GRAD, self.adam, s), lib)
+        _lib.check(lib.tmf_sum_f32(self.loss_part, p.seg_u.nseg, self.loss_w[t:t + 1], s), lib)
+        _lib.check(row_pass(p.seg_i.cstruct(), p.row_i, p.val_i, Vwin, self.U,
+                            out, self.slab, None, r, _lib.EPI_GRAD, self.adam, s), lib)
         _engine._row_pass_finish(lib, p.seg_i, self.slab, Vwin, out, r, _lib.EPI_GRAD, self.adam, s, self.sfx)
 
     def finish_users(self):
         """U <- fresh-Adam(U, summed user gradient); returns this rank's loss sum (1-element fp64 device tensor)."""
         lib, s = _lib.get(), _lib.stream_ptr()
-        i32 = ctypes.c_int32
         if self.m:
-            _lib.check(getattr(lib, 'tmf_wmrb_finish' + self.sfx)(_lib.ptr(self.part), i32(1), i32(self.m), _lib.ptr(self.U),
-                                                                  _lib.ptr(self.U_nxt), self.r, _lib.EPI_ADAM, self.adam, s), lib)
+            _lib.check(getattr(lib, 'tmf_wmrb_finish' + self.sfx)(self.part, 1, self.m, self.U,
+                                                                  self.U_nxt, self.r, _lib.EPI_ADAM, self.adam, s), lib)
         if self.loss == 'wmrb':
-            _lib.check(lib.tmf_sum_f32(_lib.ptr(self.loss_part), self.m, _lib.ptr(self.loss_out), s), lib)
+            _lib.check(lib.tmf_sum_f32(self.loss_part, self.m, self.loss_out, s), lib)
         else:
             self.loss_out[0] = self.loss_w.sum()
         self.U, self.U_nxt = self.U_nxt, self.U
@@ -175,5 +172,5 @@ class WindowedHipBackend:
     def adam_rows(self, W_rows, G_rows):
         lib = _lib.get()
         if W_rows.shape[0]:
-            _lib.check(getattr(lib, 'tmf_adam_fresh_rows' + self.sfx)(_lib.ptr(W_rows), _lib.ptr(G_rows), W_rows.shape[0], self.r,
+            _lib.check(getattr(lib, 'tmf_adam_fresh_rows' + self.sfx)(W_rows, G_rows, W_rows.shape[0], self.r,
                                                                       self.adam, _lib.stream_ptr()), lib)

@@ -87,7 +87,7 @@ class HipBackend:
 
     def adam_rows(self, W_rows, G_rows):
         lib = _lib.get()
-        _lib.check(getattr(lib, 'tmf_adam_fresh_rows' + self.st.sfx)(_lib.ptr(W_rows), _lib.ptr(G_rows), W_rows.shape[0], self.st.r,
+        _lib.check(getattr(lib, 'tmf_adam_fresh_rows' + self.st.sfx)(W_rows, G_rows, W_rows.shape[0], self.st.r,
                                                self.adam, _lib.stream_ptr()), lib)
 
     def V(self):

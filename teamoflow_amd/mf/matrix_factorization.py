@@ -499,10 +499,10 @@ class MatrixFactorization:
             _engine.run_epoch(st, a, out, loss, c, _lib.EPI_GRAD, gV, None, _lib.EPI_GRAD, gU)
             for W, G, M, V2, l2 in sides:
                 if l2:   # the moments see g' = g + l2 w
-                    _lib.check(lib.tmf_adam_state_rows_l2_f32(_lib.ptr(W), _lib.ptr(G), _lib.ptr(M), _lib.ptr(V2), W.shape[0],
+                    _lib.check(lib.tmf_adam_state_rows_l2_f32(W, G, M, V2, W.shape[0],
                                                               self.n_components, a, l2, _lib.stream_ptr()), lib)
                     continue
-                _lib.check(lib.tmf_adam_state_rows_f32(_lib.ptr(W), _lib.ptr(G), _lib.ptr(M), _lib.ptr(V2), W.shape[0],
+                _lib.check(lib.tmf_adam_state_rows_f32(W, G, M, V2, W.shape[0],
                                                        self.n_components, a, _lib.stream_ptr()), lib)
         return persistent
 

@@ -2,6 +2,7 @@
 index builders agree with a NumPy restatement, the engine refuses to run without a GPU."""
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -22,6 +23,111 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.tmf_version() == 203 == _lib.MIN_LIB_VERSION
+
+
+HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason='needs hipcc (host compiler only, nothing is run)')
+def test_the_compiler_agrees_with_the_header_parser(tmp_path):
+    """_lib binds what _lib.parse_header reads from include/tmf.h.  One translation unit states every prototype as parsed and the
+    size and field offsets of every generated ctypes structure as static assertions; the host compiler checks them against the
+    header itself (syntax only: no offload, nothing is linked or run)."""
+    import ctypes
+    from teamoflow_amd import _lib
+    h = _lib.HEADER
+    assert len(h.functions) == len(_lib.SIGNATURES) and set(h.structs) == {'tmf_adam', 'tmf_segments', 'tmf_slice_lists',
+                                                                            'tmf_exclusion', 'tmf_rank_rows'}
+    lines = ['#include <cstddef>', '#include <type_traits>', '#include "tmf.h"']
+    for name, (ret, args) in h.functions.items():
+        lines.append(f'static_assert(std::is_same<decltype(&{name}), {ret} (*)({", ".join(args)})>::value, "{name}");')
+        assert len(_lib.SIGNATURES[name][1]) == len(args)
+    for name, cls in zip(h.structs, (_lib.Adam, _lib.Segments, _lib.SliceLists, _lib.Exclusion, _lib.RankRows)):
+        assert [f for _, f in h.structs[name]] == [f for f, _ in cls._fields_]
+        lines.append(f'static_assert(sizeof({name}) == {ctypes.sizeof(cls)}, "sizeof {name}");')
+        for ctype, field in h.structs[name]:
+            lines.append(f'static_assert(offsetof({name}, {field}) == {getattr(cls, field).offset}, "{name}.{field}");')
+            lines.append(f'static_assert(std::is_same<decltype({name}::{field}), {ctype}>::value, "{name}.{field}");')
+            lines.append(f'static_assert(sizeof({ctype}) == {getattr(cls, field).size}, "{name}.{field}");')
+    for name, value in h.constants.items():
+        lines.append(f'static_assert({name} == {value}, "{name}");')
+    src = tmp_path / 'tmf_abi.cpp'
+    src.write_text('\n'.join(lines) + '\n')
+    res = subprocess.run([HIPCC, '-x', 'c++', '-std=c++17', '-fsyntax-only', '-I' + os.path.join(ROOT, 'include'), str(src)],
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert res.returncode == 0, res.stdout
+    # and the ctypes type bound to every parsed C type: the scalar itself, POINTER(struct), or the pointee's tensor-pointer class
+    scalars = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t,
+               'float': ctypes.c_float, 'double': ctypes.c_double, 'tmf_adam': _lib.Adam, 'const char*': ctypes.c_char_p}
+    for name, (ret, args) in h.functions.items():
+        res_t, arg_ts = _lib.SIGNATURES[name]
+        for ctype, t in zip([ret] + args, [res_t] + arg_ts):
+            base = ctype.replace('const ', '').rstrip('*')
+            if ctype in scalars:
+                assert t is scalars[ctype], (name, ctype)
+            elif base in h.structs:
+                assert t is ctypes.POINTER(_lib._STRUCTS[base]), (name, ctype)
+            else:
+                assert ctype.endswith('*') and issubclass(t, ctypes.c_void_p) and t.pointee == base, (name, ctype)
+
+
+@pytest.mark.parametrize('text', [
+    'int tmf_f(int a, uint8_t b);',                         # an unknown type name
+    'typedef struct tmf_s { int a; wchar_t b; } tmf_s;',
+    'int tmf_f(const float x[4], void* stream);',           # an array parameter
+    'typedef struct tmf_s { int a[2]; } tmf_s;',
+    'int tmf_f(int (*callback)(int), void* stream);',       # a function-pointer parameter
+    'int tmf_f(int, float);',                               # unnamed parameters
+    'typedef struct tmf_s { struct { int a; } in; } tmf_s;',
+    '#define TMF_X 1.5\nint tmf_f(void);',                  # a #define TMF_.. that is no integer
+    '#define TMF_X (TMF_Y + 1)\nint tmf_f(void);',
+])
+def test_the_header_parser_refuses_what_it_does_not_understand(text):
+    from teamoflow_amd import _lib
+    with pytest.raises(ValueError):
+        _lib.bind(_lib.parse_header(text))
+
+
+def test_the_header_parser_reads_the_grammar_of_the_header():
+    from teamoflow_amd import _lib
+    good = _lib.parse_header('#ifndef TMF_H\n#define TMF_H\n#define TMF_X (-3) /* c */\ntypedef struct tmf_s { const float* a; int b, c; } tmf_s;\n'
+                             'tmf_s tmf_f(const tmf_s* s, double* x,\n void* stream);\nint tmf_g(void); // d\n#endif')
+    assert good.constants == {'TMF_X': -3} and good.structs == {'tmf_s': [('const float*', 'a'), ('int', 'b'), ('int', 'c')]}
+    assert good.functions == {'tmf_f': ('tmf_s', ['const tmf_s*', 'double*', 'void*']), 'tmf_g': ('int', [])}
+    structs, signatures = _lib.bind(good)
+    assert signatures['tmf_f'][0] is structs['tmf_s'] and [f for f, _ in structs['tmf_s']._fields_] == ['a', 'b', 'c']
+
+
+def test_tensor_pointer_arguments_check_the_element_size():
+    """A pointer parameter takes None, an int, a c_void_p and a tensor whose elements have the size of the header's pointee type
+    (void: any size) - checked on from_param directly, nothing is launched."""
+    import ctypes
+    from teamoflow_amd import _lib
+    x, out, stream = _lib.SIGNATURES['tmf_sum_f32'][1][0], _lib.SIGNATURES['tmf_sum_f32'][1][2], _lib.SIGNATURES['tmf_sum_f32'][1][3]
+    f32 = torch.arange(6, dtype=torch.float32)
+    assert x.from_param(None) is None
+    for arg, address in ((f32, f32.data_ptr()), (f32[2:], f32.data_ptr() + 8), (f32.view(torch.int32), f32.data_ptr()),
+                         (12345 << 20, 12345 << 20), (ctypes.c_void_p(f32.data_ptr()), f32.data_ptr()), (_lib.ptr(f32), f32.data_ptr())):
+        assert ctypes.cast(x.from_param(arg), ctypes.c_void_p).value == address
+    with pytest.raises(TypeError, match=r'float64.*`float\*`'):
+        x.from_param(f32.double())
+    assert ctypes.cast(out.from_param(f32.double()), ctypes.c_void_p).value
+    with pytest.raises(TypeError, match=r'float32.*`double\*`'):
+        out.from_param(f32)
+    assert stream is _lib._P
+    for dtype in (torch.float32, torch.bfloat16, torch.uint8):                          # void*: any element size
+        t = torch.zeros(4, dtype=dtype)
+        assert ctypes.cast(stream.from_param(t), ctypes.c_void_p).value == t.data_ptr()
+    rank = _lib.SIGNATURES['tmf_warp_pairs_ranked'][1][4]                               # const uint16_t* rank
+    i16 = torch.zeros(4, dtype=torch.int16)
+    assert rank.pointee == 'uint16_t' and ctypes.cast(rank.from_param(i16), ctypes.c_void_p).value == i16.data_ptr()
+    with pytest.raises(TypeError):
+        rank.from_param(i16.to(torch.int32))
+    with pytest.raises(TypeError):
+        x.from_param(1.5)
+    # one class per pointee type: prototypes with the same C types compare equal
+    assert _lib.SIGNATURES['tmf_softmax_pairs'] == _lib.SIGNATURES['tmf_wmrb_hinge2_ordered']
+    assert x is _lib.tensor_pointer('float') is not out
 
 
 def test_padded_ld_and_adam_constants_match_host_mirror():
