@@ -741,7 +741,8 @@ class Scores7Plan:
         n, nnz = plan.n_items, plan.nnz
         E = nnz + m * S
         self.n_groups = ng = -(-m // UG)
-        slice_bytes = int(os.environ.get('TMF_S7_SLICE_BYTES', slice_bytes or SCORES7_SLICE_BYTES))
+        # a slice is a range of whole rows: a size below one row (0 and negative values of TMF_S7_SLICE_BYTES included) means one row
+        slice_bytes = max(1, int(os.environ.get('TMF_S7_SLICE_BYTES', slice_bytes or SCORES7_SLICE_BYTES)))
         ns = int(min(max(1, -(-n * row_bytes(n_components, dtype) // slice_bytes)), max(1, (2 ** 31 - 1) // max(ng, 1))))
         self.width = width = -(-n // ns)
         self.n_slices = ns = -(-n // width)

@@ -130,6 +130,7 @@ class MatrixFactorization:
         self.loss_history_ = []   # extension: mean loss of every epoch of the last fit
         self.fit_seconds_ = 0.0   # extension: time spent in the epoch loop of the last fit
         self.plan_seconds_ = 0.0  # extension: time spent building the index structures of the last fit
+        self.graph_epochs_ = 0    # extension: epochs of the last fit that ran as replays of a captured hipGraph (0: every one launched)
         self.verbose = True
         self.factor_dtype = torch.float32  # extension: torch.bfloat16 = bf16 factor storage, fp32 arithmetic
         self.predict_arithmetic = None     # extension: 'auto' (default: 'split' or 'fp32', both on whole fp32 factors) | 'fp32' | 'split' | 'half2' (opt-in, 22 bits) - _ops.predict_topk
@@ -278,7 +279,7 @@ class MatrixFactorization:
         full-batch steps (loss -> gradient of the SUM of the per-interaction losses -> a fresh Adam
         step), then stores user_embedding / item_embedding / *_trainable.  Returns None."""
         route = self._route(user_features, item_features)   # and the refusals: before any weight is drawn or plan built
-        self.resample_rounds_, self.resample_seconds_ = 0, 0.0
+        self.resample_rounds_, self.resample_seconds_, self.graph_epochs_ = 0, 0.0, 0
         n_users, n_user_features = user_features.shape
         n_items, n_item_features = item_features.shape
         if not isinstance(self.user_repr_graph, ReLUEmbedding):
@@ -527,6 +528,7 @@ class MatrixFactorization:
                 graph.replay()
                 loss_sums[done:done + G].copy_(block)
                 done += G
+                self.graph_epochs_ = done
                 if self.verbose and denom:
                     t_now = None
                     for e in range(done - G, done):

@@ -10,11 +10,9 @@ import pytest
 import torch
 
 from conftest import assert_step
+from test_fuzz_draws_cpu import FORM_KEYS   # every variable that chooses a form, TMF_SCORES7 / TMF_S7_* included: cleared before a test sets its own
 
 pytestmark = pytest.mark.gpu
-
-FORM_KEYS = ('TMF_ROWS4', 'TMF_ROWS5', 'TMF_ROWS5_TARGET', 'TMF_SCORES5', 'TMF_SCORES6', 'TMF_S6_SLICE_BYTES', 'TMF_ROW_STATIONARY',
-             'TMF_ITEM_SLICES', 'TMF_USER_CHUNKS', 'TMF_FORCE_SLICED', 'TMF_SLICE_XCD', 'TMF_G4_USERS', 'TMF_ROWS4_PER_LAUNCH')
 
 
 @pytest.fixture(scope='module')
@@ -74,11 +72,9 @@ def self_pair_floor(c, U64, V64):
     return 1e-7 * c * np.abs(V64).max(), 1e-7 * c * np.abs(U64).max()
 
 
-@pytest.mark.parametrize('seed', range(int(os.environ.get('TMF_FUZZ_SEEDS', '24'))))
-def test_random_forms_against_the_closed_form(eng, monkeypatch, seed):
-    from oracle import sparse_ref as SR
-    from teamoflow_amd import _lib
-    m, n, r, S, idx, val, R, U, V, dtype, env = draw(seed)
+def build_state(eng, monkeypatch, m, n, r, S, idx, val, R, U, V, dtype, env):
+    """Clears every form variable, sets the drawn ones and builds the plans and the state the way a fit does.
+    -> (plan, wplan, st, what: the draw and the forms it led to, for the assertion messages)"""
     for k in FORM_KEYS:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
@@ -88,18 +84,33 @@ def test_random_forms_against_the_closed_form(eng, monkeypatch, seed):
     wplan = eng.wmrb_plan_for(plan, torch.tensor(R, device=dev), r, dtype)
     st = eng.TrainState(torch.tensor(U, device=dev), torch.tensor(V, device=dev), plan, r, wplan, dtype=dtype)
     what = dict(env, m=m, n=n, r=r, S=S, nnz=len(val), dtype=str(dtype), rows4=wplan.rows4, vrows=wplan.vrows is not None,
-                s6=wplan.s6 is not None, rs=st.row_stationary, slices=wplan.n_slices)
-    assert wplan.sliced and wplan.s5 is None, what
-    lr, adam = 0.05, eng.adam_constants(0.05)
+                s6=wplan.s6 is not None, s7=wplan.s7 is not None, rs=st.row_stationary, slices=wplan.n_slices)
+    return plan, wplan, st, what
+
+
+def gradient_and_step_epochs(eng, st, m, n, S):
+    """One epoch that writes the raw gradients (into buffers filled with 7.0), then one that steps the tables (into buffers filled
+    with NaN: what the updated tables hold afterwards - pad columns included - is what this epoch wrote).
+    -> (loss of the first, loss of the second, gU, gV)"""
+    from teamoflow_amd import _lib
+    dev, adam = 'cuda', eng.adam_constants(0.05)
     loss = torch.zeros(1, dtype=torch.float64, device=dev)
     gU = torch.full((m, st.ld), 7.0, device=dev)
     gV = torch.full((n, st.ld), 7.0, device=dev)
     eng.epoch_wmrb(st, adam, n / S, loss, item_epi=_lib.EPI_GRAD, item_out=gV, user_epi=_lib.EPI_GRAD, user_out=gU)
     loss2 = torch.zeros(1, dtype=torch.float64, device=dev)
-    st.U_nxt.fill_(float('nan'))   # what the updated tables hold afterwards - pad columns included - is what this epoch wrote
+    st.U_nxt.fill_(float('nan'))
     st.V_nxt.fill_(float('nan'))
     eng.epoch_wmrb(st, adam, n / S, loss2)
     torch.cuda.synchronize()
+    return loss, loss2, gU, gV
+
+
+def assert_epochs_are_the_closed_form(st, loss, loss2, gU, gV, m, n, r, S, idx, val, R, dtype, what):
+    """What every form of the epoch owes the fp64 closed form of the oracle on the tables as stored: the loss, the raw gradients,
+    the fresh-Adam step interval (fp32), zero pad columns of tables and gradients, every row written."""
+    from oracle import sparse_ref as SR
+    lr = 0.05
     # include/tmf.h: the columns [n_components, ld) of a factor table are zero and stay zero - fp32 and bf16 storage, every form
     assert st.ld >= r and st.U_nxt.shape == (m, st.ld) and st.V_nxt.shape == (n, st.ld), what
     assert not bool(st.U_nxt[:, r:].any()) and not bool(st.V_nxt[:, r:].any()), what
@@ -117,8 +128,10 @@ def test_random_forms_against_the_closed_form(eng, monkeypatch, seed):
     assert float(loss) == float(loss2), what                                             # the two epochs read the same tables
     assert abs(float(loss) / n_pos - mean) <= 1e-5 * abs(mean) + 1e-12, (float(loss) / n_pos, mean, what)
     fU, fV = self_pair_floor(n / S, U64, V64)
+    worst = {}
     for name, g, ref, s in (('gU', gU, t['gU'], sl['gU'] + fU), ('gV', gV, t['gV'], sl['gV'] + fV)):
         d = np.abs(g[:, :r].double().cpu().numpy() - ref) - 1.0001 * s
+        worst[name] = max(float(d.max()), 0.0) / max(np.abs(ref).max(), 1e-30)
         assert d.max() <= rtol * max(np.abs(ref).max(), 1e-30), (name, float(d.max()), float(np.abs(ref).max()), what)
     if dtype is torch.float32:
         assert_step(st.U_nxt[:, :r].cpu().numpy(), U64, t['gU'], lr, rtol=rtol, what=f'U {what}', slack=sl['gU'] + fU)
@@ -130,6 +143,17 @@ def test_random_forms_against_the_closed_form(eng, monkeypatch, seed):
     # columns).  A zero pad gradient is what tmf_adam_fresh_rows / tmf_adam_state_rows, which step all ld columns, need to keep the
     # tables' pad columns zero.
     assert not bool(gU[:, r:].any()) and not bool(gV[:, r:].any()), what
+    worst['loss'] = abs(float(loss) / n_pos - mean) / max(abs(mean), 1e-30)
+    return worst   # relative errors beyond the slack, for reports: gU, gV, loss
+
+
+@pytest.mark.parametrize('seed', range(int(os.environ.get('TMF_FUZZ_SEEDS', '24'))))
+def test_random_forms_against_the_closed_form(eng, monkeypatch, seed):
+    m, n, r, S, idx, val, R, U, V, dtype, env = draw(seed)
+    plan, wplan, st, what = build_state(eng, monkeypatch, m, n, r, S, idx, val, R, U, V, dtype, env)
+    assert wplan.sliced and wplan.s5 is None and wplan.s7 is None, what
+    loss, loss2, gU, gV = gradient_and_step_epochs(eng, st, m, n, S)
+    assert_epochs_are_the_closed_form(st, loss, loss2, gU, gV, m, n, r, S, idx, val, R, dtype, what)
 
 
 def draw_medium(seed):
@@ -311,5 +335,6 @@ def test_captured_epochs_equal_launched_epochs_whatever_the_forms(monkeypatch, s
         model.fit(7, eye(m), eye(n), SparseInteractions(idx, val, (m, n)), lr=0.05)       # six captured epochs + one launched
         return model
     a, b = fit(False), fit(True)
+    assert a.graph_epochs_ == 6 and b.graph_epochs_ == 0, (a.graph_epochs_, b.graph_epochs_)   # one did replay a graph, the other did not
     assert a.loss_history_ == b.loss_history_, (env, a.loss_history_, b.loss_history_)
     assert torch.equal(a.user_embedding, b.user_embedding) and torch.equal(a.item_embedding, b.item_embedding), env

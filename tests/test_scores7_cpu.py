@@ -28,12 +28,19 @@ def _problem(m, n, S, nnz, seed, empty_user=None):
 
 
 def _check(E, lib, m, n, S, nnz, seed, slice_rows, slots=None, empty_user=None):
-    r, K = 128, E.Scores7Plan.K
+    return check_streams(E, lib, m, n, S, _problem(m, n, S, nnz, seed, empty_user), slice_bytes=slice_rows * 512, slots=slots,
+                         empty_user=empty_user)
+
+
+def check_streams(E, lib, m, n, S, problem, r=128, slice_bytes=None, slots=None, empty_user=None, item_slices=2):
+    """The brute-force invariants of the module's docstring for the Scores7Plan of ``problem`` = (idx [nnz, 2], val [nnz],
+    R [m, S]) as CPU tensors - any problem: COO pairs in any order, ids repeated inside a row of R, positives among the negatives."""
+    K = E.Scores7Plan.K
     UG, cap = lib.tmf_wmrb_scores7_users_per_group(), lib.tmf_wmrb_scores7_slots()
-    idx, val, R = _problem(m, n, S, nnz, seed, empty_user)
+    idx, val, R = problem
     plan = E.InteractionPlan(idx, val, m, n)
-    wplan = E.WmrbPlan(plan, R, item_slices=2, n_components=r, sliced=True)
-    s7 = E.Scores7Plan(plan, wplan, r, torch.float32, slice_bytes=slice_rows * 512, slots=slots)
+    wplan = E.WmrbPlan(plan, R, item_slices=item_slices, n_components=r, sliced=True)
+    s7 = E.Scores7Plan(plan, wplan, r, torch.float32, slice_bytes=slice_bytes, slots=slots)
     SL = slots or cap
     assert s7.slots == SL and s7.pad_slot == cap and s7.users_per_group == UG and K == 4
     ng, ns, width = s7.n_groups, s7.n_slices, s7.width
@@ -50,12 +57,16 @@ def _check(E, lib, m, n, S, nnz, seed, slice_rows, slots=None, empty_user=None):
     if empty_user is not None and m > 1:
         assert rowptr[empty_user] == rowptr[empty_user + 1]
     seen_sp, seen_p = np.zeros(m * S, dtype=np.int32), np.zeros(max(plan.nnz, 1), dtype=np.int32)
+    assert (np.repeat(np.arange(m), np.diff(rowptr)) == user_of).all()     # the CSR's two views of an interaction's user agree
+    # the chunk of every place by brute force: negative (u, s) -> place u * S + s, interaction k -> place ~k
+    all_places = np.concatenate([np.arange(m * S, dtype=np.int64), ~np.arange(plan.nnz, dtype=np.int64)])
+    all_chunks = np.concatenate([((Rs.astype(np.int64) // width) * ng + (np.arange(m, dtype=np.int64) // UG)[:, None]).reshape(-1),
+                                 (col.astype(np.int64) // width) * ng + user_of.astype(np.int64) // UG])
+    by_chunk = np.argsort(all_chunks, kind='stable')
+    chunk_edge = np.searchsorted(all_chunks[by_chunk], np.arange(ns * ng + 1))
     for c in range(ns * ng):
         sl, grp = divmod(c, ng)
-        want = set()    # the chunk's places by brute force
-        for u in range(grp * UG, min((grp + 1) * UG, m)):
-            want |= {int(u * S + s) for s in range(S) if Rs[u, s] // width == sl}
-            want |= {~int(k) for k in range(rowptr[u], rowptr[u + 1]) if col[k] // width == sl}
+        want = set(all_places[by_chunk[chunk_edge[c]:chunk_edge[c + 1]]].tolist())
         got = set()
         for sub in range(chunk_sub[c], chunk_sub[c + 1]):
             pl = place[sub_place[sub]:sub_place[sub + 1]]

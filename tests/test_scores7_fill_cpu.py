@@ -47,13 +47,13 @@ def _walk(s7, W):
     return processed, written
 
 
-def _check_fill(E, lib, m, n, S, nnz, seed, slice_rows=None, slots=None, empty_user=None, problem=None):
-    r = 128
+def _check_fill(E, lib, m, n, S, nnz, seed, slice_rows=None, slots=None, empty_user=None, problem=None, r=128, slice_bytes=None,
+                item_slices=2):
     W, cap = lib.tmf_wmrb_scores7_waves(), lib.tmf_wmrb_scores7_slots()
     idx, val, R = problem or _problem(m, n, S, nnz, seed, empty_user)
     plan = E.InteractionPlan(idx, val, m, n)
-    wplan = E.WmrbPlan(plan, R, item_slices=2, n_components=r, sliced=True)
-    kw = dict(slice_bytes=slice_rows * 512 if slice_rows else None, slots=slots)
+    wplan = E.WmrbPlan(plan, R, item_slices=item_slices, n_components=r, sliced=True)
+    kw = dict(slice_bytes=slice_rows * 512 if slice_rows else slice_bytes, slots=slots)
     a = E.Scores7Plan(plan, wplan, r, torch.float32, **kw)       # stays in item order
     b = E.Scores7Plan(plan, wplan, r, torch.float32, **kw)
     assert a.sub_wave is None and a.sub_fill is None
