@@ -118,6 +118,43 @@ int tmf_wmrb_entry_lists(const int32_t* user_of, const int32_t* col_u, const flo
                          const int32_t* R_sorted, int32_t n_users, int32_t n_samples, int32_t n_items, int32_t user_chunks,
                          int32_t* ent_row, int32_t* ent_id, int64_t* rowptr_e, void* workspace, size_t workspace_bytes,
                          void* stream);
+/* The streams of tmf_wmrb_scores7_f32 / tmf_wmrb_scores7_fill_f32 (below: steps, place, sub_step, sub_place, chunk_sub, sub_fill),
+ * built chunk by chunk from the CSR and the item-sorted negative table - no sort, scan or scatter over all entries or all steps.
+ * Inputs of all three calls: rowptr_u [n_users + 1], col_u [nnz] ascending inside every user (tmf_csr_build), R_sorted
+ * [n_users, n_samples] ascending inside every user (tmf_sort_samples), `width` = items per slice (n_slices = ceil(n_items / width),
+ * the n_slices handed to the scores kernel), `slots` = entries per sub-chunk, 1 .. tmf_wmrb_scores7_slots().  n_groups =
+ * ceil(n_users / tmf_wmrb_scores7_users_per_group()), n_chunks = n_slices * n_groups, E = nnz + n_users * n_samples.
+ * Order rules (an ENTRY: id e < nnz = interaction e, place ~e; e = nnz + u * n_samples + pos = negative pos of user u, place
+ * u * n_samples + pos):
+ *   chunk = (item / width) * n_groups + u / users_per_group; its entries go by (item, local user, e), so a user's interaction with
+ *     an item comes before its negative of that item and repeated ids keep ascending e
+ *   sub-chunk j of a chunk = entries [j * slots, (j + 1) * slots) of that order (neighbours may share their border item)
+ *   slot = rank inside the sub-chunk by (local user, e); place [E] is written sub-chunk after sub-chunk in slot order
+ *   steps: inside a sub-chunk every run of one item, in chunk order, is cut every 4 entries; pads repeat the step's first user and
+ *     carry the slot tmf_wmrb_scores7_slots().  fill_order == 0: a sub-chunk's steps in that (item) order; != 0: stably by descending
+ *     fill, as tmf_wmrb_scores7_fill_f32 wants them.  steps has n_steps + 1 records: the one behind the last is zero.
+ * The calls, in order, each enqueued on `stream`; the host reads two totals in between:
+ *   tmf_s7plan_chunks  -> chunk_ent [n_chunks + 1] first entry of every chunk, chunk_sub [n_chunks + 1]; n_sub = chunk_sub[n_chunks]
+ *   tmf_s7plan_subs    -> sub_fill [n_sub, 4] steps of fill 4, 3, 2, 1, sub_place, sub_step [n_sub + 1]; n_steps = sub_step[n_sub]
+ *   tmf_s7plan_streams -> steps [n_steps + 1] 16-byte records (16-byte aligned), place [E] (NULL: not written, as for a second call
+ *                         that only wants the other order of the steps)
+ * with chunk_ent, chunk_sub, sub_step handed on unchanged.  The workspace (tmf_s7plan_workspace_bytes(n_chunks) for _chunks,
+ * (n_sub) for _subs) is scratch of that call alone.  Limits: n_items < 2^24, nnz < 2^31, n_users * n_samples < 2^31 (int32
+ * places), n_chunks < 2^31, n_sub < 2^23 (one launch of 512 threads per sub-chunk; the caller's to check after _chunks).  A null list, a null output, slots outside
+ * [1, tmf_wmrb_scores7_slots()], width < 1, n_items outside [1, 2^24), a negative size, a size beyond the limits, a workspace that
+ * is null or too small: TMF_E_INVALID and nothing is launched.  n_users == 0 or n_sub == 0 is legal (empty streams). */
+size_t tmf_s7plan_workspace_bytes(int64_t n);
+int tmf_s7plan_chunks(const int64_t* rowptr_u, const int32_t* col_u, const int32_t* R_sorted, int64_t nnz, int64_t n_users,
+                      int32_t n_samples, int32_t n_items, int32_t width, int32_t slots, int64_t* chunk_ent, int32_t* chunk_sub,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int tmf_s7plan_subs(const int64_t* rowptr_u, const int32_t* col_u, const int32_t* R_sorted, int64_t nnz, int64_t n_users,
+                    int32_t n_samples, int32_t n_items, int32_t width, int32_t slots, const int64_t* chunk_ent,
+                    const int32_t* chunk_sub, int64_t n_sub, int32_t* sub_fill, int64_t* sub_place, int64_t* sub_step,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int tmf_s7plan_streams(const int64_t* rowptr_u, const int32_t* col_u, const int32_t* R_sorted, int64_t nnz, int64_t n_users,
+                       int32_t n_samples, int32_t n_items, int32_t width, int32_t slots, const int64_t* chunk_ent,
+                       const int32_t* chunk_sub, int64_t n_sub, const int64_t* sub_step, int64_t n_steps, int32_t fill_order,
+                       void* steps, int32_t* place, void* stream);
 
 /* K1+K2 / K3: one side of an MSE epoch (loss_graphs.py:47-52 forward; tape.gradient
  * matrix_factorization.py:170-171; Adam :176) evaluated sparsely:

@@ -717,6 +717,24 @@ def scores7_fill_wanted():
     return os.environ.get('TMF_S7_FILL', '1' if SCORES7_FILL else '0') != '0'
 
 
+def scores7_sub_wave(cnt, W):
+    """sub_wave [n_sub, W + 1] int32 of Scores7Plan.order_by_fill from the class counts cnt [n_sub, 4] int64 (steps of fill 4, 3, 2, 1)
+    alone, in integers - both builders of the plan come through here."""
+    K, dev, i64 = cnt.shape[1], cnt.device, torch.int64
+    n_sub = cnt.shape[0]
+    # wave w of W takes the steps between the points where the running cost passes w / W of the sub-chunk's; the running cost is
+    # piecewise linear in the step (one slope per class), so the points come from the class counts alone - in integers
+    zero = torch.zeros(n_sub, 1, dtype=i64, device=dev)
+    slope = torch.tensor([SCORES7_COST_STEP + SCORES7_COST_SLOT * f for f in range(K, 0, -1)], dtype=i64, device=dev)
+    step_edge = torch.cat([zero, torch.cumsum(cnt, 1)], 1)             # [n_sub, K + 1] first step of every class
+    cost_edge = torch.cat([zero, torch.cumsum(cnt * slope, 1)], 1) * W
+    target = cost_edge[:, K:] // W * torch.arange(1, W, device=dev, dtype=i64)       # [n_sub, W - 1], in units of 1 / W
+    cls = (target[:, :, None] >= cost_edge[:, None, 1:K]).sum(2)                     # the class the point falls in
+    cut = torch.gather(step_edge, 1, cls) + (target - torch.gather(cost_edge, 1, cls)) // (W * slope[cls])
+    cut = torch.minimum((cut + 4) // 8 * 8, step_edge[:, K:])
+    return torch.cat([zero, cut, step_edge[:, K:]], 1).to(torch.int32).contiguous()
+
+
 class Scores7Plan:
     """Streams of tmf_wmrb_scores7 (include/tmf.h), built once per fit from the sliced plan; the builder needs no GPU.
     Every (user, item) pair whose score the epoch needs - interaction k of the CSR (place ~k) and negative (u, pos) of the item-sorted
@@ -726,11 +744,14 @@ class Scores7Plan:
     sub-chunk by (local user, place order): the slots of a user are consecutive and so are their addresses in sp / p.
       steps [n_steps, 4] int32   item | K 8-bit local users | K 16-bit slots; pads: the step's first user, slot = pad_slot
       place [n_entries] int32    sub-chunk after sub-chunk, slot order
-      sub_step, sub_place [n_sub + 1] int64; chunk_sub [n_slices * n_groups + 1] int32"""
+      sub_step, sub_place [n_sub + 1] int64; chunk_sub [n_slices * n_groups + 1] int32
+    builder='torch': the global sorts of __init__ (any device).  builder='device': the same bits from the chunk-local kernels of
+    csrc/tmf_s7plan.hip (GPU tensors); steps and place are then written when first read or by order_by_fill().  None: TMF_S7_BUILD,
+    else 'device' on a GPU."""
 
     K = 4
 
-    def __init__(self, plan, wplan, n_components, dtype=torch.float32, slice_bytes=None, slots=None):
+    def __init__(self, plan, wplan, n_components, dtype=torch.float32, slice_bytes=None, slots=None, builder=None):
         lib = _lib.load_library()
         self.key = (int(n_components), dtype)
         dev, i32, i64, K = plan.col_u.device, torch.int32, torch.int64, self.K
@@ -747,6 +768,17 @@ class Scores7Plan:
         self.width = width = -(-n // ns)
         self.n_slices = ns = -(-n // width)
         nc = ns * ng
+        # builder: 'device' = the chunk-local kernels of csrc/tmf_s7plan.hip (GPU tensors, the shapes the scores kernel itself takes),
+        # 'torch' = the global sorts below (any device; the oracle of the kernels).  None: TMF_S7_BUILD, else 'device' where it exists
+        fits = n < 2 ** 24 and nnz < 2 ** 31 and m * S < 2 ** 31 and hasattr(lib, 'tmf_s7plan_chunks')   # (TMF_LIB_OLDER: an A/B library without them)
+        builder = builder or os.environ.get('TMF_S7_BUILD') or ('device' if dev.type == 'cuda' and fits else 'torch')
+        if builder not in ('device', 'torch'):
+            raise ValueError(f"Scores7Plan: builder={builder!r} is neither 'device' nor 'torch'")
+        if builder == 'device':
+            if dev.type != 'cuda':
+                raise ValueError(f"Scores7Plan: builder='device' needs the plan on a GPU, not on {dev} (builder='torch' runs anywhere)")
+            self.n_entries = E
+            return self._build_device(plan, wplan)
         ar = torch.arange(E, device=dev, dtype=i64)
         # entries in place order: e < nnz is interaction e, e >= nnz is negative e - nnz = u * S + pos
         user = torch.cat([plan.user_of.to(i64), torch.arange(m, device=dev, dtype=i64).repeat_interleave(S)])
@@ -813,6 +845,72 @@ class Scores7Plan:
         self.steps = steps
         self.n_entries = E
 
+    def _s7plan_call(self, fn, *tail):
+        rowptr, col, R, chunk_ent = self._dev[:4]
+        m, S = R.shape
+        _lib.check(fn(rowptr, col, R, col.numel(), m, S, self._n_items, self.width, self.slots, chunk_ent, self.chunk_sub, *tail,
+                      _lib.stream_ptr()))
+
+    def _build_device(self, plan, wplan):
+        """The same streams from tmf_s7plan_chunks / _subs / _streams (include/tmf.h): a workgroup per sub-chunk finds its borders in
+        the users' sorted lists, nothing of length E or n_steps is sorted.  Two device-to-host reads: n_sub and n_steps.  Holds on to
+        rowptr_u, col_u and R until order_by_fill() has run (or for good, where it never does)."""
+        lib = _lib.get()
+        dev, i32, i64 = plan.col_u.device, torch.int32, torch.int64
+        R = wplan.R.contiguous()
+        nc = self.n_slices * self.n_groups
+        self._n_items = plan.n_items
+        chunk_ent = torch.empty(nc + 1, dtype=i64, device=dev)
+        self.chunk_sub = torch.empty(nc + 1, dtype=i32, device=dev)
+        self._dev = (plan.rowptr_u, plan.col_u, R, chunk_ent, None)
+        ws = torch.empty(lib.tmf_s7plan_workspace_bytes(nc), dtype=torch.uint8, device=dev)
+        self._s7plan_call(lambda *a: lib.tmf_s7plan_chunks(*a[:-1], ws, ws.numel(), a[-1]))
+        self.n_sub = n_sub = int(self.chunk_sub[-1])
+        sub_fill = torch.empty(n_sub, 4, dtype=i32, device=dev)
+        self.sub_place = torch.empty(n_sub + 1, dtype=i64, device=dev)
+        self.sub_step = torch.empty(n_sub + 1, dtype=i64, device=dev)
+        ws = torch.empty(lib.tmf_s7plan_workspace_bytes(n_sub), dtype=torch.uint8, device=dev)
+        self._s7plan_call(lib.tmf_s7plan_subs, n_sub, sub_fill, self.sub_place, self.sub_step, ws, ws.numel())
+        self.n_steps = int(self.sub_step[-1])
+        self._dev = self._dev[:4] + (sub_fill,)
+        # steps and place are written when they are first asked for (_streams): a state that wants fill order (the default) calls
+        # order_by_fill() first, and the item-ordered steps, 7 GB at C4, are then never written at all
+
+    def _streams(self, fill_order):
+        """The third call, into fresh buffers: the steps in the order asked for and, where they are not there yet, the places."""
+        dev = self.chunk_sub.device
+        self._steps = None
+        steps = torch.empty(self.n_steps + 1, 4, dtype=torch.int32, device=dev)
+        place = torch.empty(self.n_entries, dtype=torch.int32, device=dev) if self._place is None else None
+        self._s7plan_call(_lib.get().tmf_s7plan_streams, self.n_sub, self.sub_step, self.n_steps, int(fill_order), steps, place)
+        self._steps = steps
+        if place is not None:
+            self._place = place
+
+    # steps / place: plain attributes of a torch-built plan; a device-built plan writes them on first use
+    _steps = _place = None
+
+    @property
+    def steps(self):
+        if self._steps is None and self._dev is not None:
+            self._streams(False)
+        return self._steps
+
+    @steps.setter
+    def steps(self, value):
+        self._steps = value
+
+    @property
+    def place(self):
+        if self._place is None and self._dev is not None:
+            self._streams(False)
+        return self._place
+
+    @place.setter
+    def place(self, value):
+        self._place = value
+
+    _dev = None                  # a device-built plan in item order: (rowptr_u, col_u, R, chunk_ent, sub_fill) for order_by_fill
     sub_wave = sub_fill = None   # the tables of tmf_wmrb_scores7_fill_f32: order_by_fill() builds them
 
     def order_by_fill(self):
@@ -828,6 +926,12 @@ class Scores7Plan:
         if self.sub_wave is not None:
             return self
         W = int(_lib.load_library().tmf_wmrb_scores7_waves())
+        if self._dev is not None:   # built on the device: the kernel writes the steps in fill order; places that are there stay
+            self._streams(True)
+            self.sub_fill = self._dev[4]
+            self.sub_wave = scores7_sub_wave(self.sub_fill.to(torch.int64), W)
+            self._dev = None
+            return self
         K, cap, n_steps, n_sub = self.K, self.pad_slot, self.n_steps, self.n_sub
         dev, i32, i64 = self.steps.device, torch.int32, torch.int64
         rec = self.steps[:n_steps]
@@ -852,17 +956,7 @@ class Scores7Plan:
         del order, rec, old64, new64
         self.steps = steps
         self.sub_fill = cnt.to(i32).contiguous()
-        # wave w of W takes the steps between the points where the running cost passes w / W of the sub-chunk's; the running cost is
-        # piecewise linear in the step (one slope per class), so the points come from the class counts alone - in integers
-        zero = torch.zeros(n_sub, 1, dtype=i64, device=dev)
-        slope = torch.tensor([SCORES7_COST_STEP + SCORES7_COST_SLOT * f for f in range(K, 0, -1)], dtype=i64, device=dev)
-        step_edge = torch.cat([zero, torch.cumsum(cnt, 1)], 1)             # [n_sub, K + 1] first step of every class
-        cost_edge = torch.cat([zero, torch.cumsum(cnt * slope, 1)], 1) * W
-        target = cost_edge[:, K:] // W * torch.arange(1, W, device=dev, dtype=i64)       # [n_sub, W - 1], in units of 1 / W
-        cls = (target[:, :, None] >= cost_edge[:, None, 1:K]).sum(2)                     # the class the point falls in
-        cut = torch.gather(step_edge, 1, cls) + (target - torch.gather(cost_edge, 1, cls)) // (W * slope[cls])
-        cut = torch.minimum((cut + 4) // 8 * 8, step_edge[:, K:])
-        self.sub_wave = torch.cat([zero, cut, step_edge[:, K:]], 1).to(i32).contiguous()
+        self.sub_wave = scores7_sub_wave(cnt, W)
         return self
 
 
@@ -1031,6 +1125,7 @@ class TrainState:
                         wplan.s7 = Scores7Plan(plan, wplan, self.r, dtype)
                     if scores7_fill_wanted():
                         wplan.s7.order_by_fill()   # a plan that has its tables stays as it is
+                    wplan.s7.steps                 # a device-built plan writes its streams here at the latest: inside the fallback
                 except torch.OutOfMemoryError:
                     # the default: streams of ~10 bytes per entry that do not fit leave the pass with scores3 / scores6
                     if os.environ.get('TMF_SCORES7') == '1':

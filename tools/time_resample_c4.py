@@ -6,8 +6,9 @@ bench.py's generator).
     as the median of ``--reps`` launches between device events after a warm-up, the torch function once between synchronisations
     after a small warm-up call.  The bound: the kernel is faster.  The two tables are compared (torch.equal).
 (b) one re-plan, split.  TrainState.set_negatives at C4 under WARPLoss, every part between synchronisations: the draw, WmrbPlan
-    (sort, slice offsets, entry lists), the scores plan the state wants (Scores7Plan at C4), sample_rank, and the rest (freeing the
-    old plan, sync words, rebinding).
+    (sort, slice offsets, entry lists), the scores plan the state wants (Scores7Plan at C4: its constructor - on the device the two
+    counting calls - and order_by_fill, where a device-built plan writes its streams), sample_rank, and the rest (freeing the old
+    plan, sync words, rebinding).
 (c) epoch time.  The WARP and BPR epoch on the static table, with this library and with the PARENT commit's (a child process of
     its own: a library is chosen when the package is imported), and the mean epoch of a fit that re-plans every epoch and every
     fifth.  No bound.
@@ -118,16 +119,19 @@ def child_epochs(args):
         if not args.static_only:
             if pairs == 'warp':   # (b): the parts of one re-plan
                 spans.clear()
-                saved = (_engine.WmrbPlan.__init__, _engine.Scores7Plan.__init__, _engine.Scores6Plan.__init__, _engine.WmrbPlan.sample_rank)
+                saved = (_engine.WmrbPlan.__init__, _engine.Scores7Plan.__init__, _engine.Scores6Plan.__init__, _engine.WmrbPlan.sample_rank,
+                         _engine.Scores7Plan.order_by_fill)
                 _engine.WmrbPlan.__init__ = timed('wmrb_plan', saved[0])
                 _engine.Scores7Plan.__init__ = timed('scores7_plan', saved[1])
                 _engine.Scores6Plan.__init__ = timed('scores6_plan', saved[2])
                 _engine.WmrbPlan.sample_rank = timed('sample_rank', saved[3])
+                _engine.Scores7Plan.order_by_fill = timed('scores7_order_by_fill', saved[4])
                 draw = timed('draw', lambda j: _ops.sample_negatives(n, m, S, seed=100 + j, device=dev))
                 rebind = timed('set_negatives', st.set_negatives)
                 for j in (1, 2):
                     rebind(draw(j))
-                _engine.WmrbPlan.__init__, _engine.Scores7Plan.__init__, _engine.Scores6Plan.__init__, _engine.WmrbPlan.sample_rank = saved
+                (_engine.WmrbPlan.__init__, _engine.Scores7Plan.__init__, _engine.Scores6Plan.__init__, _engine.WmrbPlan.sample_rank,
+                 _engine.Scores7Plan.order_by_fill) = saved
                 split = {k: median(v) for k, v in spans.items()}
                 split['rest_free_sync_rebind'] = split['set_negatives'] - sum(v for k, v in split.items() if k not in ('draw', 'set_negatives'))
                 split['replan_total'] = split['draw'] + split['set_negatives']
