@@ -425,6 +425,23 @@ int tmf_warp_pairs(const int64_t* rowptr, const float* val, const float* p, cons
 int tmf_warp_pairs_ranked(const int64_t* rowptr, const float* val, const float* p, const float* sp, const uint16_t* rank,
                           int32_t n_users, int32_t n_samples, int32_t n_items, float* delta, float* D, float* loss_part,
                           const int32_t* user_order, void* stream);
+/* KOSWARPLoss (an extension), the weights: omega[j] = the probability that the k'-th best of n' uniform draws with replacement from
+ * the P stored values > 0 of the entry's user is entry j - n' = min(n, P), k' = min(k, n'), 1 <= k <= n <= 64.  With a_j / b_j the
+ * number of the user's positives whose score p is above / not below p[j] (compared in fp32; a NaN orders below -inf and ties with
+ * the other NaNs) and B(q) = sum_{i < k'} C(n', i) q^i (1 - q)^(n' - i), B(0) = 1, B(1) = 0:
+ * omega[j] = (B(a_j / P) - B(b_j / P)) / (b_j - a_j), B in fp64, rounded to fp32 once; 0 for a stored value <= 0.  A tie block shares
+ * its probability equally, the weights of a user with P >= 1 sum to 1.  Every element of omega [nnz] is overwritten, whatever the
+ * buffer held.  Reads no table; one LDS sort of the user's scores and two bisections per entry, rows of any length (a row of more
+ * than 2048 positives is taken in segments).  n_users = 0 is legal, and so are NULL val / p / omega for a table without
+ * interactions.  No atomics; the outputs are bit-identical from run to run and do not depend on user_order (speed only). */
+int tmf_kos_weights(const int64_t* rowptr, const float* val, const float* p, int32_t n_users, int32_t k, int32_t n, float* omega,
+                    const int32_t* user_order, void* stream);
+/* tmf_warp_pairs (rank = NULL) or tmf_warp_pairs_ranked (with rank) with a weight per stored entry: w' = fl(omega[k] w), one fp32
+ * rounding, stands in w's place everywhere - delta[k] = -w', D[u, s*] += w', loss_part[u] = sum_k w' (1 - p[k] + sp[u, s*]), and an
+ * entry with w' = 0 (or not > 0) takes no part.  omega [nnz] is required.  omega = 1 everywhere gives the bits of the two above. */
+int tmf_warp_pairs_kos(const int64_t* rowptr, const float* val, const float* p, const float* sp, const uint16_t* rank,
+                       const float* omega, int32_t n_users, int32_t n_samples, int32_t n_items, float* delta, float* D,
+                       float* loss_part, const int32_t* user_order, void* stream);
 /* SampledSoftmaxLoss (an extension) in the same place, the arguments of tmf_wmrb_hinge2_ordered in their layout: for the stored
  * values > 0 of user u, with M = max_s sp[u, s], e_s = exp(sp[u, s] - M), Z = sum_s e_s, m = max(p[k], M), t = exp(M - m),
  * b = c Z t and den = exp(p[k] - m) + b:  loss_k = log(den) + (m - p[k]) = -log(exp(p[k]) / (exp(p[k]) + c sum_s exp(sp[u, s]))),

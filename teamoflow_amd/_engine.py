@@ -9,6 +9,7 @@ What replaces what (reference paths under /root/reference/src/teamoflow/mf/):
   epoch_logistic: LogisticLoss (mf/loss_graphs.py; an extension - the reference has no such loss)
   epoch_wmrb(pairs='bpr'): BPRLoss (mf/loss_graphs.py; an extension): the WMRB epoch with tmf_bpr_pairs in the hinge kernel's place
   epoch_wmrb(pairs='warp'): WARPLoss (mf/loss_graphs.py; an extension): the same epoch with tmf_warp_pairs there
+  epoch_wmrb(pairs='warp_kos'): KOSWARPLoss (an extension): tmf_kos_weights (csrc/tmf_kos.hip), then the weighted tmf_warp_pairs_kos
   epoch_wmrb(pairs='softmax'): SampledSoftmaxLoss (mf/loss_graphs.py; an extension): the same epoch with tmf_softmax_pairs there
   epoch_sides <- the same loop with plug-in sides: any loss above, then the step of every side that is an object (TrainState.sides:
                  PlainL2Side, BiasSide, FeatureSide, ReLUSide <- embedding_graphs.py:30-87)
@@ -521,6 +522,13 @@ class WmrbPlan:
                     rank[b:b + (1 << 16)] = torch.arange(S, device=rows.device).to(torch.int16)[None, :]
             self._rank = rank
         return self._rank
+
+    def kos_omega(self, nnz):
+        """The weights of a KOSWARPLoss fit: fp32, one slot per stored interaction (tmf_kos_weights fills it, tmf_warp_pairs_kos reads
+        it).  Allocated on first use - only this loss has it - and kept with the plan: the same buffer every epoch."""
+        if getattr(self, 'omega', None) is None:
+            self.omega = torch.empty(nnz, dtype=torch.float32, device=self.R.device)
+        return self.omega
 
     def D_in_model_order(self):
         """D[u, s] indexed like the model's random_ind (the sliced pass keeps every user's negatives sorted by item)."""
@@ -1521,13 +1529,13 @@ LOGISTIC_LOSSES = ('logistic', 'logistic_w')   # LogisticLoss(weighted=False) / 
 FULL_SOFTMAX_MAX_COMPONENTS = 128   # tmf_fsm_max_components: the widest table csrc/tmf_fullsoftmax.hip sweeps (fp32 only)
 
 
-SLICED_ONLY = ('bpr', 'warp', 'softmax')   # pair steps of the sliced user pass alone: the one-kernel pass has the hinge built in
-PAIR_LOSSES = ('wmrb', 'bpr', 'warp', 'softmax')   # the losses over the static negative table: WmrbPlan, sp / p / delta / D, denominator n_pos
+SLICED_ONLY = ('bpr', 'warp', 'warp_kos', 'softmax')   # pair steps of the sliced user pass alone: the one-kernel pass has the hinge built in
+PAIR_LOSSES = ('wmrb', 'bpr', 'warp', 'warp_kos', 'softmax')   # the losses over the static negative table: WmrbPlan, sp / p / delta / D, denominator n_pos
 
 
 def loss_name(loss_graph):
-    """The name run_epoch knows the loss of a fit by: 'mse', 'wmrb', 'kl', 'bpr', 'warp', 'softmax', 'full_softmax', 'logistic' or
-    'logistic_w' for exactly the eight built-in loss classes (not their subclasses: what a subclass computes is its own business, and
+    """The name run_epoch knows the loss of a fit by: 'mse', 'wmrb', 'kl', 'bpr', 'warp', 'warp_kos', 'softmax', 'full_softmax', 'logistic'
+    or 'logistic_w' for exactly the nine built-in loss classes (not their subclasses: what a subclass computes is its own business, and
     the generic path's).  Anything
     else raises - no loss trains as another one because a chain of isinstance tests fell through."""
     from .mf import loss_graphs as L
@@ -1535,10 +1543,10 @@ def loss_name(loss_graph):
     if kind is L.LogisticLoss:
         return 'logistic_w' if loss_graph.weighted else 'logistic'
     names = {L.MSELoss: 'mse', L.WMRBLoss: 'wmrb', L.KLDivergenceLoss: 'kl', L.BPRLoss: 'bpr', L.WARPLoss: 'warp',
-             L.SampledSoftmaxLoss: 'softmax', L.FullSoftmaxLoss: 'full_softmax'}
+             L.KOSWARPLoss: 'warp_kos', L.SampledSoftmaxLoss: 'softmax', L.FullSoftmaxLoss: 'full_softmax'}
     if kind not in names:
         raise TypeError(f'{kind.__name__} is not a loss the HIP engine trains (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, '
-                        f'BPRLoss, WARPLoss, SampledSoftmaxLoss, FullSoftmaxLoss)')
+                        f'BPRLoss, WARPLoss, KOSWARPLoss, SampledSoftmaxLoss, FullSoftmaxLoss)')
     return names[kind]
 
 
@@ -1569,16 +1577,16 @@ def checked_negatives(random_ind, n_rows, n_items, device, rows=None):
 
 def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM,
               user_out=None):
-    """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'bpr', 'warp', 'softmax' (c = 1 or n_items / n_samples), 'kl',
-    'logistic', 'logistic_w', 'mse' or 'full_softmax' (only on a state built with full_softmax=True) - on the state's tables: the ONE
+    """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'bpr', 'warp', 'warp_kos' (c = the pair (k, n) of the
+    KOSWARPLoss), 'softmax' (c = 1 or n_items / n_samples), 'kl', 'logistic', 'logistic_w', 'mse' or 'full_softmax' (only on a state built with full_softmax=True) - on the state's tables: the ONE
     place that maps a loss to its epoch.  The other arguments as
-    in epoch_mse.  'bpr', 'warp' and 'softmax' are epochs only of a state whose WmrbPlan is sliced (wmrb_plan_for(force_sliced=True)):
+    in epoch_mse.  'bpr', 'warp', 'warp_kos' and 'softmax' are epochs only of a state whose WmrbPlan is sliced (wmrb_plan_for(force_sliced=True)):
     the one-kernel user pass has the hinge built in.  On any other state they are refused like a name nobody knows - never run as
     WMRB."""
     if loss == 'wmrb':
         epoch_wmrb(st, adam, c, loss_out, item_epi, item_out, prof, user_epi, user_out)
     elif loss in SLICED_ONLY and getattr(getattr(st, 'wplan', None), 'sliced', False):
-        epoch_wmrb(st, adam, c if loss == 'softmax' else 0.0, loss_out, item_epi, item_out, prof, user_epi, user_out, pairs=loss)
+        epoch_wmrb(st, adam, c if loss in ('softmax', 'warp_kos') else 0.0, loss_out, item_epi, item_out, prof, user_epi, user_out, pairs=loss)
     elif loss == 'kl':
         epoch_kl(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
     elif loss in LOGISTIC_LOSSES:
@@ -1691,6 +1699,8 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
     pairs='warp': tmf_warp_pairs_ranked (csrc/tmf_warp.hip) there - those arguments, the plan's n_items (the weight's rank
     estimate) and WmrbPlan.sample_rank(): the one loss here that depends on the order of a user's samples tries them in the model's
     table order, whatever order the plan keeps them in.
+    pairs='warp_kos': two steps there - tmf_kos_weights (csrc/tmf_kos.hip) ranks every user's positives by the scores just computed
+    and leaves their weights in WmrbPlan.kos_omega(); tmf_warp_pairs_kos is the ranked WARP step with those weights.  c = (k, n).
     pairs='softmax': tmf_softmax_pairs (csrc/tmf_softmax.hip) there - the hinge kernel's arguments, c = 1 or n_items / n_samples; the
     loss does not depend on the order of a user's samples, so it takes sp and D as the plan keeps them."""
     p, w, r = st.plan, st.wplan, st.r
@@ -1734,6 +1744,14 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
                                                                      st.sp, rank, m, S, p.n_items,
                                                                      w.delta, w.D, st.loss_part,
                                                                      w.hinge_order, s))
+    elif pairs == 'warp_kos':
+        kos_k, kos_n = c
+        rank, omega = w.sample_rank(), w.kos_omega(p.nnz)
+        _timed(prof, 'kos_weights', lambda: lib.tmf_kos_weights(p.rowptr_u, p.val_u, st.pk, m, kos_k, kos_n, omega,
+                                                                w.hinge_order, s))
+        _timed(prof, 'warp_pairs', lambda: lib.tmf_warp_pairs_kos(p.rowptr_u, p.val_u, st.pk, st.sp, rank, omega, m, S,
+                                                                  p.n_items, w.delta, w.D, st.loss_part,
+                                                                  w.hinge_order, s))
     elif pairs == 'softmax':
         _timed(prof, 'softmax_pairs', lambda: lib.tmf_softmax_pairs(p.rowptr_u, p.val_u, st.pk, st.sp,
                                                                     m, S, c, w.delta, w.D,
@@ -1763,10 +1781,13 @@ def epoch_wmrb(st, adam, c, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, pro
     sum over positives of mean_s softplus(sp[u, s] - p_k).  Only on a sliced plan.
     pairs='warp': one WARPLoss epoch in the same way around tmf_warp_pairs; loss_out receives sum over positives of
     w_k (1 - p_k + sp[u, s*_k]).  Only on a sliced plan.
+    pairs='warp_kos': one KOSWARPLoss epoch (c = (k, n)) around tmf_kos_weights and tmf_warp_pairs_kos; loss_out receives sum over
+    positives of omega_k w_k (1 - p_k + sp[u, s*_k]), omega_k the probability that the k'-th best of n' draws from the user's
+    positives is k.  Only on a sliced plan.
     pairs='softmax': one SampledSoftmaxLoss epoch in the same way around tmf_softmax_pairs (c = 1, or n_items / n_samples); loss_out
     receives sum over positives of -log(exp(p_k) / (exp(p_k) + c sum_s exp(sp[u, s]))).  Only on a sliced plan."""
     if pairs not in ('hinge',) + SLICED_ONLY:
-        raise ValueError(f'epoch_wmrb: pairs={pairs!r} (hinge, bpr, warp or softmax)')
+        raise ValueError(f'epoch_wmrb: pairs={pairs!r} (hinge, bpr, warp, warp_kos or softmax)')
     if pairs != 'hinge' and not st.wplan.sliced:
         raise ValueError(f'epoch_wmrb: pairs={pairs} needs the sliced user pass (wmrb_plan_for(force_sliced=True))')
     lib, p, w, r = _lib.get(), st.plan, st.wplan, st.r

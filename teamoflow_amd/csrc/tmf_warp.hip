@@ -39,6 +39,10 @@
 // its sum at the place of s*, and D leaves as it lies; a longer row keeps D by table index and sends the segment out through the
 // map, Du[pos] = D[rank[pos]] - coalesced in global memory either way, and a long row is read once per segment.  Everything else is
 // the same code, and the same bits: rank = identity gives tmf_warp_pairs.
+//
+// tmf_warp_pairs_kos is the weighted form (KOSWARPLoss; tmf_kos.hip makes the weights): with omega[k] beside the entries, the weight
+// of an entry is w' = fl(omega_k w_k), one fp32 rounding, and w' stands wherever w stands above - the test w' > 0, delta, the sum
+// into D and the loss.  It is a second instance of the kernel template: the instance without omega is the code it was before.
 #include <math.h>
 
 #include "tmf_common.h"
@@ -63,11 +67,12 @@ __device__ __forceinline__ float wave_prefix_max(float v) {
     return v;
 }
 
+template <bool KOS>
 __global__ __launch_bounds__(64) void k_warp_pairs(const int64_t* __restrict__ rowptr, const float* __restrict__ val,
                                                    const float* __restrict__ p, const float* __restrict__ sp, int S, int cap,
                                                    int nm1, int64_t n_users, float* __restrict__ delta, float* __restrict__ D,
                                                    float* __restrict__ loss_part, const int32_t* __restrict__ order,
-                                                   const uint16_t* __restrict__ rank) {
+                                                   const uint16_t* __restrict__ rank, const float* __restrict__ omega) {
     extern __shared__ float wlds[];     // M[cap] | D[cap] | place[cap] (16 bits each; the ranked form only)
     float* Ml = wlds;
     float* Dl = wlds + cap;
@@ -162,6 +167,7 @@ __global__ __launch_bounds__(64) void k_warp_pairs(const int64_t* __restrict__ r
                     const int N = g0 + sstar + 1;
                     const int q = (N <= nm1) ? nm1 / N : 1;
                     w = (q > 1) ? logf((float)q) : 0.f;
+                    if (KOS) w = omega[cb + lane] * w;                 // w' = fl(omega w)
                 }
                 const bool act = hit && w > 0.f;
                 if (act) lacc += (double)w * ((double)Ml[sstar] - ((double)pk - 1.0));
@@ -205,30 +211,44 @@ __global__ __launch_bounds__(64) void k_warp_pairs(const int64_t* __restrict__ r
 
 using namespace tmf;
 
-static int warp_pairs(const int64_t* rowptr, const float* val, const float* p, const float* sp, const uint16_t* rank, int32_t n_users,
-                      int32_t n_samples, int32_t n_items, float* delta, float* D, float* loss_part, const int32_t* user_order,
-                      void* stream, const char* what) {
+static int warp_pairs(const int64_t* rowptr, const float* val, const float* p, const float* sp, const uint16_t* rank, const float* omega,
+                      int32_t n_users, int32_t n_samples, int32_t n_items, float* delta, float* D, float* loss_part,
+                      const int32_t* user_order, void* stream, const char* what) {
     if (n_users == 0) return TMF_OK;
     // val, p and delta are read only where a row has entries: a table without interactions may pass NULL for them
     TMF_REQUIRE(rowptr && sp && D && n_users > 0 && n_samples > 0 && n_items > 0, "%s: bad arguments", what);
     TMF_REQUIRE_LAUNCH(n_users, 64, what);
     const int cap = n_samples < WCAP ? (int)n_samples : WCAP;
     const size_t lds = (size_t)cap * (2 * sizeof(float) + (rank ? sizeof(uint16_t) : 0));
-    hipLaunchKernelGGL(k_warp_pairs, dim3((unsigned)n_users), dim3(64), lds, (hipStream_t)stream, rowptr,
-                       val, p, sp, (int)n_samples, cap, (int)n_items - 1, (int64_t)n_users, delta, D, loss_part, user_order, rank);
+    if (omega)
+        hipLaunchKernelGGL(k_warp_pairs<true>, dim3((unsigned)n_users), dim3(64), lds, (hipStream_t)stream, rowptr, val, p, sp,
+                           (int)n_samples, cap, (int)n_items - 1, (int64_t)n_users, delta, D, loss_part, user_order, rank, omega);
+    else
+        hipLaunchKernelGGL(k_warp_pairs<false>, dim3((unsigned)n_users), dim3(64), lds, (hipStream_t)stream, rowptr, val, p, sp,
+                           (int)n_samples, cap, (int)n_items - 1, (int64_t)n_users, delta, D, loss_part, user_order, rank, nullptr);
     return check_launch(what);
 }
 
 extern "C" int tmf_warp_pairs(const int64_t* rowptr, const float* val, const float* p, const float* sp, int32_t n_users,
                               int32_t n_samples, int32_t n_items, float* delta, float* D, float* loss_part,
                               const int32_t* user_order, void* stream) {
-    return warp_pairs(rowptr, val, p, sp, nullptr, n_users, n_samples, n_items, delta, D, loss_part, user_order, stream, "tmf_warp_pairs");
+    return warp_pairs(rowptr, val, p, sp, nullptr, nullptr, n_users, n_samples, n_items, delta, D, loss_part, user_order, stream,
+                      "tmf_warp_pairs");
 }
 
 extern "C" int tmf_warp_pairs_ranked(const int64_t* rowptr, const float* val, const float* p, const float* sp, const uint16_t* rank,
                                      int32_t n_users, int32_t n_samples, int32_t n_items, float* delta, float* D, float* loss_part,
                                      const int32_t* user_order, void* stream) {
     TMF_REQUIRE(n_users == 0 || (rank && n_samples <= 65536), "tmf_warp_pairs_ranked: bad arguments (ranks are 16 bits: n_samples <= 65536)");
-    return warp_pairs(rowptr, val, p, sp, rank, n_users, n_samples, n_items, delta, D, loss_part, user_order, stream,
+    return warp_pairs(rowptr, val, p, sp, rank, nullptr, n_users, n_samples, n_items, delta, D, loss_part, user_order, stream,
                       "tmf_warp_pairs_ranked");
+}
+
+extern "C" int tmf_warp_pairs_kos(const int64_t* rowptr, const float* val, const float* p, const float* sp, const uint16_t* rank,
+                                  const float* omega, int32_t n_users, int32_t n_samples, int32_t n_items, float* delta, float* D,
+                                  float* loss_part, const int32_t* user_order, void* stream) {
+    TMF_REQUIRE(n_users == 0 || (omega && (!rank || n_samples <= 65536)),
+                "tmf_warp_pairs_kos: bad arguments (omega is required; ranks are 16 bits: n_samples <= 65536)");
+    return warp_pairs(rowptr, val, p, sp, rank, omega, n_users, n_samples, n_items, delta, D, loss_part, user_order, stream,
+                      "tmf_warp_pairs_kos");
 }

@@ -1,7 +1,7 @@
 """Loss graphs (plug-in interface of /root/reference/src/teamoflow/mf/loss_graphs.py).
 
-``MSELoss``, ``WMRBLoss``, ``KLDivergenceLoss``, ``LogisticLoss``, ``BPRLoss``, ``WARPLoss``, ``SampledSoftmaxLoss`` and
-``FullSoftmaxLoss`` (extensions: the reference has no logistic loss, pointwise or pairwise, no first-violator ranking loss and no
+``MSELoss``, ``WMRBLoss``, ``KLDivergenceLoss``, ``LogisticLoss``, ``BPRLoss``, ``WARPLoss``, ``KOSWARPLoss``, ``SampledSoftmaxLoss``
+and ``FullSoftmaxLoss`` (extensions: the reference has no logistic loss, pointwise or pairwise, no first-violator ranking loss and no
 softmax, sampled or over the whole catalog - the last one reads no negative table: its partition is swept through the matrix cores,
 csrc/tmf_fullsoftmax.hip) with ``LinearEmbedding`` over indicator features are recognised by
 ``MatrixFactorization.fit`` (same isinstance dispatch as matrix_factorization.py:152-162) and run as
@@ -133,6 +133,75 @@ class WARPLoss(LossGraph):
             w = torch.where(found, torch.log(rank.to(pos.dtype)), torch.zeros_like(pos))
         margin = 1.0 - pos + sp.gather(1, first[:, None])[:, 0]
         return torch.where(w > 0.0, w * margin, torch.zeros_like(pos))
+
+
+class KOSWARPLoss(LossGraph):
+    """Extension (the k-th order statistic loss of Weston, Yee and Weiss, modelled on LightFM's 'warp-kos'; not in the reference):
+    WARPLoss pushes up every positive of a user, this loss the user's k-th best positive out of a draw of n.  LightFM draws the n
+    positives at random; here the loss is the EXPECTATION over that draw, a weighted WARP without a random number.  For user u let
+    E_u be its stored interactions with a value > 0 (duplicates as often as they are stored), P = |E_u|, n' = min(n, P) and
+    k' = min(k, n').  For entry j of E_u with score p_j (compared in the dtype of the scores; a NaN orders below -inf and ties with
+    the other NaNs):
+
+        a_j = #{i in E_u : p_i > p_j}        b_j = #{i in E_u : p_i >= p_j}        B(q) = sum_{i < k'} C(n', i) q^i (1 - q)^(n' - i)
+        omega_j = (B(a_j / P) - B(b_j / P)) / (b_j - a_j)        loss_j = omega_j w_j (1 - p_j + sp[u, s*_j])
+
+    B(q) is the probability that fewer than k' of n' uniform draws with replacement land in a set of share q (B(0) = 1, B(1) = 0), so
+    omega_j is the probability that the k'-th highest of the n' draws is j; a tie block shares its probability equally, and the
+    weights of a user sum to 1: a user counts once, however many positives it has.  s*_j and w_j are exactly WARPLoss's first
+    violator and weight.  omega_j and w_j are constants of the step (no_grad): d loss_j / d p_j = -omega_j w_j and
+    d loss_j / d sp[u, s*_j] = omega_j w_j.  A user without positives contributes nothing.  k = n = 1 gives omega_j = 1 / P: the
+    per-user mean of WARPLoss's terms.  1 <= k <= n <= 64 (ValueError)."""
+
+    def __init__(self, k=5, n=10):
+        for name, v in (('k', k), ('n', n)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f'KOSWARPLoss: {name}={v!r} is not an integer')
+        if not 1 <= k <= n <= 64:
+            raise ValueError(f'KOSWARPLoss: k={k}, n={n}: 1 <= k <= n <= 64')
+        self.k, self.n = k, n
+
+    def weights(self, users, pos, n_users):
+        """omega per positive (users [E] int64, pos [E] scores) - a and b by sorting within users, B from its sum in pos.dtype."""
+        with torch.no_grad():
+            E, dt = pos.shape[0], pos.dtype
+            if E == 0:
+                return torch.zeros_like(pos)
+            nan = torch.isnan(pos)
+            x = torch.where(nan, torch.full_like(pos, -math.inf), pos)
+            order = torch.sort(x, descending=True, stable=True)[1]               # by (user, a number before a NaN, score descending)
+            order = order[torch.sort(nan[order].to(torch.uint8), stable=True)[1]]
+            order = order[torch.sort(users[order], stable=True)[1]]
+            xs, ns, us = x[order], nan[order], users[order]
+            start = torch.ones(E, dtype=torch.bool, device=pos.device)           # the first entry of every tie block
+            start[1:] = (us[1:] != us[:-1]) | (ns[1:] != ns[:-1]) | (xs[1:] != xs[:-1])
+            block = torch.cumsum(start, 0) - 1
+            block_first = torch.nonzero(start)[:, 0]
+            block_size = torch.bincount(block)
+            P_user = torch.bincount(users, minlength=n_users)
+            user_first = torch.cumsum(P_user, 0) - P_user
+            a = block_first[block] - user_first[us]
+            b = a + block_size[block]
+            P = P_user[us]
+            np_, i = P.clamp(max=self.n), torch.arange(self.k, device=pos.device)
+            kp = np_.clamp(max=self.k)
+            comb = torch.tensor([[math.comb(m, j) for j in range(self.k)] for m in range(self.n + 1)], dtype=dt, device=pos.device)
+
+            def B(c):
+                q, r = (c.to(dt) / P.to(dt))[:, None], ((P - c).to(dt) / P.to(dt))[:, None]
+                terms = comb[np_] * q ** i * r ** (np_[:, None] - i).clamp(min=0)
+                return torch.where(i[None, :] < kp[:, None], terms, torch.zeros_like(terms)).sum(dim=1)
+            omega = ((B(a) - B(b)) / (b - a).to(dt)).clamp(min=0.0)
+            out = torch.empty_like(pos)
+            out[order] = omega
+            return out
+
+    def get_loss(self, tf_interactions, tf_sample_predictions, tf_prediction_serial, n_items, n_samples, predictions=None):
+        mask = tf_interactions.values > 0.0
+        users = tf_interactions.indices[:, 0][mask]
+        omega = self.weights(users, tf_prediction_serial[mask].detach(), tf_sample_predictions.shape[0])
+        return omega * WARPLoss().get_loss(tf_interactions=tf_interactions, tf_sample_predictions=tf_sample_predictions,
+                                           tf_prediction_serial=tf_prediction_serial, n_items=n_items, n_samples=n_samples)
 
 
 class SampledSoftmaxLoss(LossGraph):

@@ -3,7 +3,7 @@
 
 Dispatch (``MatrixFactorization._route``; same isinstance test the reference uses at :115,:136-162): a model made of
 (``LinearEmbedding`` | ``BiasedLinearEmbedding``) x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss`` |
-``LogisticLoss`` | ``BPRLoss`` | ``WARPLoss`` | ``SampledSoftmaxLoss`` | ``FullSoftmaxLoss``) - or ``LinearEmbedding`` over ``SparseFeatures`` on either side, or with ``relu_engine = True``
+``LogisticLoss`` | ``BPRLoss`` | ``WARPLoss`` | ``KOSWARPLoss`` | ``SampledSoftmaxLoss`` | ``FullSoftmaxLoss``) - or ``LinearEmbedding`` over ``SparseFeatures`` on either side, or with ``relu_engine = True``
 (off by default) a ``ReLUEmbedding`` side over either - trains on the HIP engine (``_engine.py`` -> libtmf.so); for unbiased MSE / WMRB it
 needs a GPU - there is no CPU fallback for them.  Any other combination of plug-ins (dense features, ReLU embeddings, user subclasses)
 trains through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins' own ``get_repr`` /
@@ -25,8 +25,8 @@ import torch
 from .. import _als, _engine, _lib, _ops
 from .embedding_graphs import BiasedLinearEmbedding, Embeddings, LinearEmbedding, ReLUEmbedding
 from .initializer_graphs import NormalInitializer
-from .loss_graphs import (BPRLoss, FullSoftmaxLoss, KLDivergenceLoss, LogisticLoss, LossGraph, MSELoss, SampledSoftmaxLoss, WARPLoss,
-                          WMRBLoss)
+from .loss_graphs import (BPRLoss, FullSoftmaxLoss, KLDivergenceLoss, KOSWARPLoss, LogisticLoss, LossGraph, MSELoss, SampledSoftmaxLoss,
+                          WARPLoss, WMRBLoss)
 from .sparse import IndicatorFeatures, SparseFeatures, SparseInteractions, default_device, is_indicator
 from .utils import gather_matrix_indices, random_sampler, random_sampler_device
 
@@ -38,10 +38,10 @@ GRAPH_MAX_WORK = 20_000_000    # interactions + sampled scores per epoch below w
 # What trains where (DESIGN.md prints this table; MatrixFactorization._route reads it).  A row is a feature of a fit, a column a
 # setting that leaves the single-GPU full-batch fp32 fresh-Adam fit: 'ok' = the engine has that form, 'generic' = fit() trains
 # through _fit_generic, 'refuse' = NotImplementedError before any weight is drawn or plan built.
-ENGINE_LOSSES = (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, BPRLoss, WARPLoss, SampledSoftmaxLoss,
+ENGINE_LOSSES = (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, BPRLoss, WARPLoss, KOSWARPLoss, SampledSoftmaxLoss,
                  FullSoftmaxLoss)   # exactly these types, no subclass
-TABLE_LOSSES = (WMRBLoss, BPRLoss, WARPLoss, SampledSoftmaxLoss)   # these and their subclasses read the static negative table
-PAIR_STEP_LOSSES = (BPRLoss, WARPLoss, SampledSoftmaxLoss)          # the route feature 'pair': a pair step of the sliced user pass
+TABLE_LOSSES = (WMRBLoss, BPRLoss, WARPLoss, KOSWARPLoss, SampledSoftmaxLoss)   # these and their subclasses read the static negative table
+PAIR_STEP_LOSSES = (BPRLoss, WARPLoss, KOSWARPLoss, SampledSoftmaxLoss)   # the route feature 'pair': a pair step of the sliced user pass
 PAIR_ROW_LOSSES = PAIR_STEP_LOSSES + (FullSoftmaxLoss,)             # the losses that answer by the row 'pair': single GPU, full batch
 _SETTINGS = {   # column -> (the attribute a refusal names, has the model left its default?), in the order refusals are met
     'relu_engine': ('relu_engine', lambda m: getattr(m, 'relu_engine', 0)     # counts beside a ReLUEmbedding side only
@@ -71,7 +71,7 @@ _BUILT = {'pair': 'only the single-GPU full-batch fit is built for this loss',
 
 
 class SampleTableMissing(AttributeError):
-    """WMRB, BPR, WARP and the sampled softmax need the static negative table: build the model with generate_sample=True
+    """WMRB, BPR, WARP, k-OS WARP and the sampled softmax need the static negative table: build the model with generate_sample=True
     (the reference fails with AttributeError inside gather_matrix_indices, matrix_factorization.py:153)."""
 
 
@@ -439,8 +439,8 @@ class MatrixFactorization:
 
     def _sparse_state(self, loss, n_users, n_items, interactions, U0, V0, dev, user_feat=None, item_feat=None):
         """(TrainState, c) of a single-GPU full-batch fit: the interaction plan, for the table losses the checked negative table and its
-        plan (BPR, WARP, softmax: always the sliced user pass), for WMRB c = n_items / n_samples (for the softmax that or 1), and the
-        starting bias of a BiasedLinearEmbedding side.  (None, 0.0) for KL with an empty class."""
+        plan (BPR, WARP, k-OS WARP, softmax: always the sliced user pass), for WMRB c = n_items / n_samples (for the softmax that or 1;
+        for KOSWARPLoss the pair (k, n) travels in c's place), and the starting bias of a BiasedLinearEmbedding side.  (None, 0.0) for KL with an empty class."""
         wmrb, kl = loss in _engine.PAIR_LOSSES, loss == 'kl'
         plan = _engine.InteractionPlan(interactions.indices, interactions.values, n_users, n_items,
                                        user_chunks=1 if wmrb else _engine.mse_user_chunks(), csc=not wmrb)
@@ -454,8 +454,11 @@ class MatrixFactorization:
             elif loss == 'softmax':
                 c = 1.0
             wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype, force_sliced=loss != 'wmrb')
-            if loss == 'warp':
+            if loss in ('warp', 'warp_kos'):
                 wplan.sample_rank()   # WARP tries the samples in the table's order: built here, before any epoch is captured
+            if loss == 'warp_kos':
+                c = (self.loss_graph.k, self.loss_graph.n)
+                wplan.kos_omega(plan.nnz)   # the weights' buffer: the same one every epoch
         r = self.n_components
         # a biased side starts from the bias an earlier fit left on the model, as in the reference (:139-146), else from zeros
         bias0 = [None if type(graph) is not BiasedLinearEmbedding else torch.zeros(r) if kept is None else kept
