@@ -2,19 +2,13 @@
 launch sequence.  Everything numeric runs in libtmf.so (HIP); torch is used for device memory,
 streams and the one-off index preparation (sort / bincount / cumsum).
 
-What replaces what (reference paths under /root/reference/src/teamoflow/mf/):
-  epoch_mse   <- matrix_factorization.py:130-176 with MSELoss  (loss_graphs.py:47-52)
-  epoch_wmrb  <- matrix_factorization.py:130-176 with WMRBLoss (loss_graphs.py:74-88, utils.py:94-105)
-  epoch_kl    <- matrix_factorization.py:130-176 with KLDivergenceLoss (loss_graphs.py:91-122)
-  epoch_logistic: LogisticLoss (mf/loss_graphs.py; an extension - the reference has no such loss)
-  epoch_wmrb(pairs='bpr'): BPRLoss (mf/loss_graphs.py; an extension): the WMRB epoch with tmf_bpr_pairs in the hinge kernel's place
-  epoch_wmrb(pairs='warp'): WARPLoss (mf/loss_graphs.py; an extension): the same epoch with tmf_warp_pairs there
-  epoch_wmrb(pairs='warp_kos'): KOSWARPLoss (an extension): tmf_kos_weights (csrc/tmf_kos.hip), then the weighted tmf_warp_pairs_kos
-  epoch_wmrb(pairs='softmax'): SampledSoftmaxLoss (mf/loss_graphs.py; an extension): the same epoch with tmf_softmax_pairs there
-  epoch_sides <- the same loop with plug-in sides: any loss above, then the step of every side that is an object (TrainState.sides:
-                 PlainL2Side, BiasSide, FeatureSide, ReLUSide <- embedding_graphs.py:30-87)
+What replaces what (reference paths under /root/reference/src/teamoflow/mf/): the epoch functions at the end of this file replace
+matrix_factorization.py:130-176 with one loss of loss_graphs.py each - LOSSES, the table behind them, is the ONE place that says what
+every loss the engine trains is made of - and epoch_sides the same loop with plug-in sides: any of those losses, then the step of
+every side that is an object (TrainState.sides: PlainL2Side, BiasSide, FeatureSide, ReLUSide <- embedding_graphs.py:30-87).
 """
 import ctypes
+import dataclasses
 import os
 
 import torch
@@ -480,6 +474,7 @@ class WmrbPlan:
         self._lists = None
         self.s5 = self.s6 = self.s7 = None   # Scores5Plan / Scores6Plan / Scores7Plan, built by the TrainState that wants that scores kernel (scores5_wanted ...)
         self.route = None   # wmrb_plan_for's keyword arguments where it built this plan: TrainState.set_negatives builds the next one alike
+        self.prepared = []   # (method, arguments) of what was built on this plan for its loss - sample_rank, kos_omega: set_negatives calls them on the next plan
 
     def release(self):
         """Drops every index structure (entry lists, sorted table, weights, score streams, slice lists, ranks) whoever still holds the
@@ -521,6 +516,7 @@ class WmrbPlan:
                 else:
                     rank[b:b + (1 << 16)] = torch.arange(S, device=rows.device).to(torch.int16)[None, :]
             self._rank = rank
+            self.prepared.append(('sample_rank', ()))
         return self._rank
 
     def kos_omega(self, nnz):
@@ -528,6 +524,7 @@ class WmrbPlan:
         it).  Allocated on first use - only this loss has it - and kept with the plan: the same buffer every epoch."""
         if getattr(self, 'omega', None) is None:
             self.omega = torch.empty(nnz, dtype=torch.float32, device=self.R.device)
+            self.prepared.append(('kos_omega', (nnz,)))
         return self.omega
 
     def D_in_model_order(self):
@@ -1165,8 +1162,9 @@ class TrainState:
 
     def set_negatives(self, R):
         """Another negative table (int32 [n_users, n_samples], the shape of the one it replaces) for a live state: the WmrbPlan is
-        rebuilt by the route that built it (wmrb_plan_for, same force_sliced; with the sample ranks when the old plan had them -
-        WARPLoss) and everything derived from it again by _adopt_wplan.  The tables, the side objects, l2, the gradient tables and
+        rebuilt by the route that built it (wmrb_plan_for, same force_sliced), with whatever was built on the old one for its loss
+        (WmrbPlan.prepared: the sample ranks, the omega buffer - by Loss.prepare, by hand or by an epoch; no epoch after this call
+        allocates) and everything derived from it again by _adopt_wplan.  The tables, the side objects, l2, the gradient tables and
         moments of persistent Adam and the InteractionPlan are not touched.  The old plan - its entry lists, score streams, slice
         lists and ranks - is dropped BEFORE the new one is built, so the peak stays that of building the state.  ``sp`` / ``pk`` /
         ``part`` keep their sizes (m, S and nnz do not change); the slab grows when the new lists need more, and the sync words are
@@ -1180,7 +1178,7 @@ class TrainState:
         R = torch.as_tensor(R).to(device=self.plan.col_u.device, dtype=torch.int32).contiguous()
         if tuple(R.shape) != tuple(old.R_model.shape):
             raise ValueError(f'the new table has shape {tuple(R.shape)}, the one it replaces {tuple(old.R_model.shape)}')
-        route, ranked = old.route, getattr(old, '_rank', None) is not None
+        route, prepared = old.route, old.prepared
         self.wplan = None
         self.sp = self.pk = self.part = None
         for name in ('g4_sync', 'rows4_sync'):
@@ -1188,8 +1186,8 @@ class TrainState:
         old.release()
         del old
         self.wplan = wmrb_plan_for(self.plan, R, self.r, self.dtype, **route)
-        if ranked:
-            self.wplan.sample_rank()
+        for build, args in prepared:
+            getattr(self.wplan, build)(*args)
         need = dict(self._need)
         need.update(self._adopt_wplan())
         if need['slab'] > self._bufs['slab'].numel():
@@ -1525,39 +1523,27 @@ def _timed(prof, name, call):
         prof.stop(name)
 
 
-LOGISTIC_LOSSES = ('logistic', 'logistic_w')   # LogisticLoss(weighted=False) / LogisticLoss(weighted=True)
 FULL_SOFTMAX_MAX_COMPONENTS = 128   # tmf_fsm_max_components: the widest table csrc/tmf_fullsoftmax.hip sweeps (fp32 only)
 
 
-SLICED_ONLY = ('bpr', 'warp', 'warp_kos', 'softmax')   # pair steps of the sliced user pass alone: the one-kernel pass has the hinge built in
-PAIR_LOSSES = ('wmrb', 'bpr', 'warp', 'warp_kos', 'softmax')   # the losses over the static negative table: WmrbPlan, sp / p / delta / D, denominator n_pos
-
-
 def loss_name(loss_graph):
-    """The name run_epoch knows the loss of a fit by: 'mse', 'wmrb', 'kl', 'bpr', 'warp', 'warp_kos', 'softmax', 'full_softmax', 'logistic'
-    or 'logistic_w' for exactly the nine built-in loss classes (not their subclasses: what a subclass computes is its own business, and
-    the generic path's).  Anything
-    else raises - no loss trains as another one because a chain of isinstance tests fell through."""
-    from .mf import loss_graphs as L
-    kind = type(loss_graph)
-    if kind is L.LogisticLoss:
-        return 'logistic_w' if loss_graph.weighted else 'logistic'
-    names = {L.MSELoss: 'mse', L.WMRBLoss: 'wmrb', L.KLDivergenceLoss: 'kl', L.BPRLoss: 'bpr', L.WARPLoss: 'warp',
-             L.KOSWARPLoss: 'warp_kos', L.SampledSoftmaxLoss: 'softmax', L.FullSoftmaxLoss: 'full_softmax'}
-    if kind not in names:
-        raise TypeError(f'{kind.__name__} is not a loss the HIP engine trains (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, '
-                        f'BPRLoss, WARPLoss, KOSWARPLoss, SampledSoftmaxLoss, FullSoftmaxLoss)')
-    return names[kind]
+    """The LOSSES name of a fit's loss, for exactly the built-in loss classes (not their subclasses: what a subclass computes is its
+    own business, and the generic path's).  Anything else raises - no loss trains as another one because a test fell through."""
+    for rec in LOSSES.values():
+        if rec.cls is type(loss_graph) and (rec.weighted is None or rec.weighted == bool(loss_graph.weighted)):
+            return rec.name
+    raise TypeError(f'{type(loss_graph).__name__} is not a loss the HIP engine trains '
+                    f'({", ".join(dict.fromkeys(rec.kind for rec in LOSSES.values()))})')
 
 
 def form_loss(model, form, optimizer_text):
     """loss_name at the door of a fit that is a form of its own (``form``: 'mini-batch', 'multi-GPU'): such a fit steps by the
-    reference's fresh Adam only (ValueError(optimizer_text)) and has no KLDivergenceLoss."""
+    reference's fresh Adam only (ValueError(optimizer_text)) and has no loss whose moments are global (KLDivergenceLoss)."""
     if getattr(model, 'optimizer', 'fresh_adam') != 'fresh_adam':
         raise ValueError(optimizer_text)
     loss = loss_name(model.loss_graph)
-    if loss == 'kl':
-        raise ValueError(f'KLDivergenceLoss has no {form} form (its moments are global)')
+    if LOSSES[loss].global_moments:
+        raise ValueError(f'{LOSSES[loss].kind} has no {form} form (its moments are global)')
     return loss
 
 
@@ -1577,27 +1563,20 @@ def checked_negatives(random_ind, n_rows, n_items, device, rows=None):
 
 def run_epoch(st, adam, loss_out, loss, c=0.0, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM,
               user_out=None):
-    """One epoch of ``loss`` - 'wmrb' (c = n_items / n_samples), 'bpr', 'warp', 'warp_kos' (c = the pair (k, n) of the
-    KOSWARPLoss), 'softmax' (c = 1 or n_items / n_samples), 'kl', 'logistic', 'logistic_w', 'mse' or 'full_softmax' (only on a state built with full_softmax=True) - on the state's tables: the ONE
-    place that maps a loss to its epoch.  The other arguments as
-    in epoch_mse.  'bpr', 'warp', 'warp_kos' and 'softmax' are epochs only of a state whose WmrbPlan is sliced (wmrb_plan_for(force_sliced=True)):
-    the one-kernel user pass has the hinge built in.  On any other state they are refused like a name nobody knows - never run as
-    WMRB."""
-    if loss == 'wmrb':
-        epoch_wmrb(st, adam, c, loss_out, item_epi, item_out, prof, user_epi, user_out)
-    elif loss in SLICED_ONLY and getattr(getattr(st, 'wplan', None), 'sliced', False):
-        epoch_wmrb(st, adam, c if loss in ('softmax', 'warp_kos') else 0.0, loss_out, item_epi, item_out, prof, user_epi, user_out, pairs=loss)
-    elif loss == 'kl':
-        epoch_kl(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
-    elif loss in LOGISTIC_LOSSES:
-        epoch_logistic(st, adam, loss_out, loss == 'logistic_w', item_epi, item_out, prof, user_epi, user_out)
-    elif loss == 'mse':
-        epoch_mse(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
-    elif loss == 'full_softmax' and getattr(st, 'fsm_lse', None) is not None:
-        epoch_full_softmax(st, adam, loss_out, item_epi, item_out, prof, user_epi, user_out)
-    else:
-        raise ValueError(f'run_epoch: unknown loss {loss!r}' + (' on a state without a sliced WmrbPlan' if loss in SLICED_ONLY else '')
-                         + (' on a state built without full_softmax=True' if loss == 'full_softmax' else ''))
+    """One epoch of ``loss`` - a name of LOSSES, c = what its record's ``param`` gives for the model - on the state's tables: the ONE
+    place that maps a loss to its epoch.  The other arguments as in epoch_mse.  A sliced-only loss is an epoch only of a state whose
+    WmrbPlan is sliced (wmrb_plan_for(force_sliced=True)), a 'catalog' loss only of one built with full_softmax=True.  On any other
+    state they are refused like a name nobody knows - never run as WMRB."""
+    rec = LOSSES.get(loss)
+    unsliced = rec is not None and rec.sliced_only and not getattr(getattr(st, 'wplan', None), 'sliced', False)
+    unswept = rec is not None and rec.family == 'catalog' and getattr(st, 'fsm_lse', None) is None
+    if rec is None or unsliced or unswept:
+        raise ValueError(f'run_epoch: unknown loss {loss!r}' + ' on a state without a sliced WmrbPlan' * unsliced
+                         + ' on a state built without full_softmax=True' * unswept)
+    tail = (item_epi, item_out, prof, user_epi, user_out)
+    if rec.table:
+        return rec.epoch(st, adam, c, loss_out, *tail, pairs=rec.pairs)
+    rec.epoch(st, adam, loss_out, *(() if rec.weighted is None else (rec.weighted,)), *tail)
 
 
 def _row_pass_finish(lib, seg, slab, X_old, X_out, r, epi, adam, stream, sfx='_f32'):
@@ -1693,19 +1672,49 @@ def epoch_full_softmax(st, adam, loss_out, item_epi=_lib.EPI_ADAM, item_out=None
         st.V, st.V_nxt = st.V_nxt, st.V
 
 
+# The pair steps of the sliced user pass: from the scores just computed - pk of the interactions, sp of the negatives, in the plan's order
+# (every user's negatives sorted by item) - to the weights delta / D in the same layout and every user's loss in loss_part, whose sum over
+# the positives epoch_wmrb leaves in loss_out.  step(lib, st, c, prof, head, tail): c = the loss's parameter (LOSSES), head = (rowptr_u,
+# val_u, pk, sp) and tail = (delta, D, loss_part, hinge_order, stream) open and close every launch.
+def hinge_pairs(lib, st, c, prof, head, tail):
+    """WMRBLoss (csrc/tmf_hinge.hip), c = n_items / n_samples: log(1 + M_k) per positive.  The step the one-kernel user pass has built in."""
+    _timed(prof, 'wmrb_hinge', lambda: lib.tmf_wmrb_hinge2_ordered(*head, st.plan.n_users, st.wplan.S, c, *tail))
+
+
+def bpr_pairs(lib, st, c, prof, head, tail):
+    """BPRLoss (csrc/tmf_bpr.hip), the hinge kernel's arguments but c: mean_s softplus(sp[u, s] - p_k) per positive."""
+    _timed(prof, 'bpr_pairs', lambda: lib.tmf_bpr_pairs(*head, st.plan.n_users, st.wplan.S, *tail))
+
+
+def warp_pairs(lib, st, c, prof, head, tail):
+    """WARPLoss (csrc/tmf_warp.hip), c unused: w_k (1 - p_k + sp[u, s*_k]) per positive, s*_k its first violator.  Takes the plan's
+    n_items (the weight's rank estimate) and WmrbPlan.sample_rank(): the losses of this kind depend on the order of a user's samples
+    and try them in the model's table order, whatever order the plan keeps them in."""
+    p, rank = st.plan, st.wplan.sample_rank()
+    _timed(prof, 'warp_pairs', lambda: lib.tmf_warp_pairs_ranked(*head, rank, p.n_users, st.wplan.S, p.n_items, *tail))
+
+
+def kos_pairs(lib, st, c, prof, head, tail):
+    """KOSWARPLoss, c = (k, n): two steps.  tmf_kos_weights (csrc/tmf_kos.hip) ranks every user's positives by pk and leaves in
+    WmrbPlan.kos_omega() the probability omega_k that the k-th best of n draws from them is this one; tmf_warp_pairs_kos is the ranked
+    WARP step with those weights: omega_k w_k (1 - p_k + sp[u, s*_k]) per positive."""
+    p, w = st.plan, st.wplan
+    rank, omega = w.sample_rank(), w.kos_omega(p.nnz)
+    _timed(prof, 'kos_weights', lambda: lib.tmf_kos_weights(p.rowptr_u, p.val_u, st.pk, p.n_users, *c, omega, w.hinge_order,
+                                                            _lib.stream_ptr()))
+    _timed(prof, 'warp_pairs', lambda: lib.tmf_warp_pairs_kos(*head, rank, omega, p.n_users, w.S, p.n_items, *tail))
+
+
+def softmax_pairs(lib, st, c, prof, head, tail):
+    """SampledSoftmaxLoss (csrc/tmf_softmax.hip), the hinge kernel's arguments, c = 1 or n_items / n_samples:
+    -log(exp(p_k) / (exp(p_k) + c sum_s exp(sp[u, s]))) per positive.  No dependence on the order of a user's samples."""
+    _timed(prof, 'softmax_pairs', lambda: lib.tmf_softmax_pairs(*head, st.plan.n_users, st.wplan.S, c, *tail))
+
+
 def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, U_out=None, pairs='hinge'):
-    """Sliced user pass: scores -> hinge -> gradU (+ weights into entry order) -> finish (csrc/tmf_wmrb.hip, tmf_hinge.hip).
-    pairs='bpr': tmf_bpr_pairs (csrc/tmf_bpr.hip) in the hinge kernel's place - same arguments but c, same layout of delta and D.
-    pairs='warp': tmf_warp_pairs_ranked (csrc/tmf_warp.hip) there - those arguments, the plan's n_items (the weight's rank
-    estimate) and WmrbPlan.sample_rank(): the one loss here that depends on the order of a user's samples tries them in the model's
-    table order, whatever order the plan keeps them in.
-    pairs='warp_kos': two steps there - tmf_kos_weights (csrc/tmf_kos.hip) ranks every user's positives by the scores just computed
-    and leaves their weights in WmrbPlan.kos_omega(); tmf_warp_pairs_kos is the ranked WARP step with those weights.  c = (k, n).
-    pairs='softmax': tmf_softmax_pairs (csrc/tmf_softmax.hip) there - the hinge kernel's arguments, c = 1 or n_items / n_samples; the
-    loss does not depend on the order of a user's samples, so it takes sp and D as the plan keeps them."""
+    """Sliced user pass: scores -> the pair step PAIRS[pairs] -> gradU (+ weights into entry order) -> finish (csrc/tmf_wmrb.hip)."""
     p, w, r = st.plan, st.wplan, st.r
-    m, S, ns = p.n_users, w.S, w.n_slices
-    s = _lib.stream_ptr()
+    m, s = p.n_users, _lib.stream_ptr()
     lists = w.lists(p)
     s5, s6, s7 = w.s5, w.s6, w.s7
     if s7 is not None and s7.sub_wave is not None:
@@ -1733,33 +1742,7 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
     else:
         _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores3' + st.sfx)(lists, st.U, st.V, st.sp,
                                                                                 st.pk, r, s))
-    if pairs == 'bpr':
-        _timed(prof, 'bpr_pairs', lambda: lib.tmf_bpr_pairs(p.rowptr_u, p.val_u, st.pk, st.sp,
-                                                            m, S, w.delta, w.D, st.loss_part,
-                                                            w.hinge_order, s))
-    elif pairs == 'warp':
-        # sp and D are in the plan's order (every user's negatives sorted by item); the trials run in the model's table order
-        rank = w.sample_rank()
-        _timed(prof, 'warp_pairs', lambda: lib.tmf_warp_pairs_ranked(p.rowptr_u, p.val_u, st.pk,
-                                                                     st.sp, rank, m, S, p.n_items,
-                                                                     w.delta, w.D, st.loss_part,
-                                                                     w.hinge_order, s))
-    elif pairs == 'warp_kos':
-        kos_k, kos_n = c
-        rank, omega = w.sample_rank(), w.kos_omega(p.nnz)
-        _timed(prof, 'kos_weights', lambda: lib.tmf_kos_weights(p.rowptr_u, p.val_u, st.pk, m, kos_k, kos_n, omega,
-                                                                w.hinge_order, s))
-        _timed(prof, 'warp_pairs', lambda: lib.tmf_warp_pairs_kos(p.rowptr_u, p.val_u, st.pk, st.sp, rank, omega, m, S,
-                                                                  p.n_items, w.delta, w.D, st.loss_part,
-                                                                  w.hinge_order, s))
-    elif pairs == 'softmax':
-        _timed(prof, 'softmax_pairs', lambda: lib.tmf_softmax_pairs(p.rowptr_u, p.val_u, st.pk, st.sp,
-                                                                    m, S, c, w.delta, w.D,
-                                                                    st.loss_part, w.hinge_order, s))
-    else:
-        _timed(prof, 'wmrb_hinge', lambda: lib.tmf_wmrb_hinge2_ordered(p.rowptr_u, p.val_u, st.pk, st.sp,
-                                                                m, S, c, w.delta, w.D, st.loss_part,
-                                                                w.hinge_order, s))
+    PAIRS[pairs].pair_step(lib, st, c, prof, (p.rowptr_u, p.val_u, st.pk, st.sp), (w.delta, w.D, st.loss_part, w.hinge_order, s))
     if st.row_stationary:
         # gradU + finish in one row-stationary kernel (lane groups own users and walk the slices; no partial rows)
         _timed(prof, 'wmrb_gradu', lambda: getattr(lib, 'tmf_wmrb_gradu4' + st.sfx)(
@@ -1776,19 +1759,12 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
 
 def epoch_wmrb(st, adam, c, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, prof=None, user_epi=_lib.EPI_ADAM, user_out=None,
                pairs='hinge'):
-    """One WMRB epoch.  loss_out receives sum over positives of log(1 + M_k).  item_epi / user_epi as in epoch_mse.
-    pairs='bpr': one BPRLoss epoch - the same scores, gathers and item pass around tmf_bpr_pairs (c is unused); loss_out receives
-    sum over positives of mean_s softplus(sp[u, s] - p_k).  Only on a sliced plan.
-    pairs='warp': one WARPLoss epoch in the same way around tmf_warp_pairs; loss_out receives sum over positives of
-    w_k (1 - p_k + sp[u, s*_k]).  Only on a sliced plan.
-    pairs='warp_kos': one KOSWARPLoss epoch (c = (k, n)) around tmf_kos_weights and tmf_warp_pairs_kos; loss_out receives sum over
-    positives of omega_k w_k (1 - p_k + sp[u, s*_k]), omega_k the probability that the k'-th best of n' draws from the user's
-    positives is k.  Only on a sliced plan.
-    pairs='softmax': one SampledSoftmaxLoss epoch in the same way around tmf_softmax_pairs (c = 1, or n_items / n_samples); loss_out
-    receives sum over positives of -log(exp(p_k) / (exp(p_k) + c sum_s exp(sp[u, s]))).  Only on a sliced plan."""
-    if pairs not in ('hinge',) + SLICED_ONLY:
-        raise ValueError(f'epoch_wmrb: pairs={pairs!r} (hinge, bpr, warp, warp_kos or softmax)')
-    if pairs != 'hinge' and not st.wplan.sliced:
+    """One epoch of a loss over the static negative table: the same scores, gathers and item pass around the pair step ``pairs`` (a key of
+    PAIRS; 'hinge' = one WMRB epoch), c = that loss's parameter.  loss_out receives the sum over positives of what the pair step's
+    function states.  Every pair step but the hinge exists only on a sliced plan.  item_epi / user_epi as in epoch_mse."""
+    if pairs not in PAIRS:
+        raise ValueError(f'epoch_wmrb: pairs={pairs!r} ({", ".join(list(PAIRS)[:-1])} or {list(PAIRS)[-1]})')
+    if PAIRS[pairs].sliced_only and not st.wplan.sliced:
         raise ValueError(f'epoch_wmrb: pairs={pairs} needs the sliced user pass (wmrb_plan_for(force_sliced=True))')
     lib, p, w, r = _lib.get(), st.plan, st.wplan, st.r
     s = _lib.stream_ptr()
@@ -1820,6 +1796,112 @@ def epoch_wmrb(st, adam, c, loss_out, item_epi=_lib.EPI_ADAM, item_out=None, pro
             w.rowptr_e, p.n_items, w.user_chunks, w.ent_row, w.ent_w, w.wbuf, st.U,
             st.V, V_out, r, item_epi, adam, st.rows4_per_launch, st.rows4_sync,
             st.rows4_sync.numel() * 4, s))
+
+
+def no_param(model):
+    return 0.0
+
+
+def catalog_ratio(model):
+    return model.n_items / model.n_samples   # the constructor ints, true division (the reference's matrix_factorization.py:167)
+
+
+def softmax_scale(model):
+    return catalog_ratio(model) if model.loss_graph.catalog_scale else 1.0
+
+
+def kos_k_n(model):
+    return model.loss_graph.k, model.loss_graph.n
+
+
+@dataclasses.dataclass(frozen=True)
+class Loss:
+    """What one loss the engine trains is made of: a row of LOSSES, which DESIGN.md ("What a loss is made of") prints.  Every dispatch on a
+    loss - here, in mf/matrix_factorization.py and in the forms (_minibatch.py, _windowed.py, dist.py) - reads these fields."""
+    name: str                  # what run_epoch and the forms know it by
+    kind: str                  # its class in mf.loss_graphs, matched by exact type (``cls``): a subclass is not an engine loss
+    family: str                # 'list': two passes over the interaction lists | 'table': the static negative table (WmrbPlan; sp / pk /
+    #                            delta / D) | 'catalog': every item of the catalog for every user
+    epoch: object              # its epoch function (run_epoch calls it; the table family shares epoch_wmrb, told apart by ``pairs``)
+    prose: str
+    weighted: object = None    # the ``weighted`` of the LogisticLoss it stands for; None: the class has one record
+    pair_step: object = None   # family 'table': its step of the sliced user pass ...
+    sliced_only: bool = False  # ... which is then the only user pass it has: the one-kernel pass has the hinge built in
+    ranked: bool = False       # the pair step tries a user's samples in the model's table order: WmrbPlan.sample_rank()
+    plan_needs: tuple = ()     # the WmrbPlan methods (of nnz) that build what else the pair step reads
+    param: object = no_param   # model -> what travels in the slot ``c`` of run_epoch and epoch_wmrb
+    flag: str = None           # the TrainState keyword the epoch needs set
+    global_moments: bool = False   # the loss is a function of moments over ALL interactions: no mini-batch or multi-GPU form, and
+    #                            no fit at all where a class of the interactions is empty
+    denom: str = 'nnz'         # loss_history_ = an epoch's loss sum / plan.nnz | plan.n_pos | 1 (the loss is one scalar)
+    route: str = None          # the ROUTES row (mf/matrix_factorization.py) a fit of it answers by
+    feeds: str = 'dense'       # what _fit_generic hands get_loss, of this class and its subclasses: 'samples' (sample and serial
+    #                            predictions) | 'serial' | 'dense' (the [n_users, n_items] matrix)
+
+    @property
+    def cls(self):   # looked up when asked for: mf imports this module
+        from .mf import loss_graphs
+        return getattr(loss_graphs, self.kind)
+
+    @property
+    def table(self):
+        return self.family == 'table'
+
+    @property
+    def hinge(self):
+        """The one loss of the table family that every user pass and every form of a fit has (the others: SLICED_ONLY)."""
+        return self.table and not self.sliced_only
+
+    @property
+    def pairs(self):
+        """Its value of epoch_wmrb's ``pairs`` (None outside the table family)."""
+        return 'hinge' if self.hinge else self.name if self.table else None
+
+    def plan_form(self):
+        """The InteractionPlan keywords of a fit: the table family reads no CSC lists; the others may block theirs by users."""
+        return dict(user_chunks=1 if self.table else mse_user_chunks(), csc=not self.table)
+
+    def prepare(self, wplan, plan):
+        """Builds on ``wplan`` what the pair step reads beside the table - now, before any epoch runs or is captured.  The plan notes
+        what was built on it (WmrbPlan.prepared), and TrainState.set_negatives builds the same on the plan of the next table."""
+        if self.ranked:
+            wplan.sample_rank()
+        for build in self.plan_needs:
+            getattr(wplan, build)(plan.nnz)
+
+    def denominator(self, plan):
+        return 1 if self.denom == '1' else getattr(plan, self.denom)
+
+    def work(self, plan, wplan):
+        """Scores per epoch: what _fit_sparse weighs against GRAPH_MAX_WORK (the catalog family forms every score, five times)."""
+        return plan.nnz + (plan.n_users * wplan.S if self.table else 0) + (plan.n_users * plan.n_items if self.family == 'catalog' else 0)
+
+
+_TABLE = dict(denom='n_pos', feeds='samples')
+_PAIR = dict(_TABLE, sliced_only=True, route='pair')
+LOSSES = {rec.name: rec for rec in (
+    Loss('mse', 'MSELoss', 'list', epoch_mse, 'squared error of every stored interaction'),
+    Loss('wmrb', 'WMRBLoss', 'table', epoch_wmrb, 'log of one plus the scaled hinge sum of a positive against the sampled negatives',
+         pair_step=hinge_pairs, param=catalog_ratio, **_TABLE),
+    Loss('kl', 'KLDivergenceLoss', 'list', epoch_kl, 'KL divergence between the score distributions of the two classes: one scalar',
+         flag='kl', global_moments=True, denom='1', route='kl', feeds='serial'),
+    Loss('logistic', 'LogisticLoss', 'list', epoch_logistic, 'log(1 + exp(-y p)) of every stored interaction, y the sign of its value',
+         weighted=False, route='logistic'),
+    Loss('logistic_w', 'LogisticLoss', 'list', epoch_logistic, 'the same, weighted by |value|', weighted=True, route='logistic'),
+    Loss('bpr', 'BPRLoss', 'table', epoch_wmrb, 'mean softplus of sampled negative minus positive', pair_step=bpr_pairs, **_PAIR),
+    Loss('warp', 'WARPLoss', 'table', epoch_wmrb, 'rank-weighted hinge against the first violating sample, in table order',
+         pair_step=warp_pairs, ranked=True, **_PAIR),
+    Loss('warp_kos', 'KOSWARPLoss', 'table', epoch_wmrb, 'WARP with every positive weighted as the k-th best of n draws',
+         pair_step=kos_pairs, ranked=True, plan_needs=('kos_omega',), param=kos_k_n, **_PAIR),
+    Loss('softmax', 'SampledSoftmaxLoss', 'table', epoch_wmrb, 'softmax of a positive over itself and the sampled negatives',
+         pair_step=softmax_pairs, param=softmax_scale, **_PAIR),
+    Loss('full_softmax', 'FullSoftmaxLoss', 'catalog', epoch_full_softmax, 'softmax of a positive over the whole catalog',
+         flag='full_softmax', denom='n_pos', route='pair'),   # answers by the row 'pair' without being a pair step
+)}
+PAIRS = {rec.pairs: rec for rec in LOSSES.values() if rec.table}   # epoch_wmrb's pairs= -> the record whose pair step it runs
+LOGISTIC_LOSSES = tuple(name for name, rec in LOSSES.items() if rec.weighted is not None)
+SLICED_ONLY = tuple(name for name, rec in LOSSES.items() if rec.sliced_only)
+PAIR_LOSSES = tuple(name for name, rec in LOSSES.items() if rec.table)
 
 
 def adam_constants(lr):

@@ -19,7 +19,8 @@ def fit_minibatch(model, epochs, n_users, n_items, interactions, lr, U0, V0, bat
     dev = interactions.device
     loss = _engine.form_loss(model, 'mini-batch',
                              "batch_users needs optimizer='fresh_adam' (every batch step is the reference's first Adam step)")
-    wmrb = loss == 'wmrb'
+    rec = _engine.LOSSES[loss]
+    wmrb = rec.hinge   # the other losses of the table family have no such form: the route refuses them, and so does run_epoch below
     B = int(batch_users)
     if B <= 0:
         raise ValueError(f'batch_users={batch_users}')
@@ -28,7 +29,7 @@ def fit_minibatch(model, epochs, n_users, n_items, interactions, lr, U0, V0, bat
     ld = _lib.padded_ld(r, dtype)
     u = interactions.indices[:, 0]
     R = _engine.checked_negatives(model.random_ind, n_users, n_items, dev) if wmrb else None
-    c = model.n_items / model.n_samples if wmrb else 0.0
+    c = rec.param(model)
     U0 = torch.as_tensor(U0).detach()
     V = torch.zeros(n_items, ld, dtype=dtype, device=dev)
     V[:, :r] = torch.as_tensor(V0).detach().to(device=dev, dtype=torch.float32)
@@ -37,8 +38,7 @@ def fit_minibatch(model, epochs, n_users, n_items, interactions, lr, U0, V0, bat
     for b0, b1 in zip(bounds[:-1], bounds[1:]):
         keep = (u >= b0) & (u < b1)
         idx, val = _engine.take_interactions(interactions.indices, interactions.values, keep, user_offset=b0)
-        plan = _engine.InteractionPlan(idx, val, b1 - b0, n_items,
-                                       user_chunks=1 if wmrb else _engine.mse_user_chunks(), csc=not wmrb)
+        plan = _engine.InteractionPlan(idx, val, b1 - b0, n_items, **rec.plan_form())
         wplan = None
         if wmrb:
             ns, sliced = _engine.choose_wmrb_user_pass(b1 - b0, n_items, ld, int(R.shape[1]), plan.n_pos, r,
@@ -50,7 +50,7 @@ def fit_minibatch(model, epochs, n_users, n_items, interactions, lr, U0, V0, bat
     adam = _engine.adam_constants(lr)
     nb = len(states)
     sums = torch.zeros(max(epochs, 1), nb, dtype=torch.float64, device=dev)
-    denom = sum(st.plan.n_pos if wmrb else st.plan.nnz for st in states)
+    denom = sum(rec.denominator(st.plan) for st in states)
     torch.cuda.synchronize(dev)
     t0 = timeit.default_timer()
     model.plan_seconds_ = t0 - t_plan

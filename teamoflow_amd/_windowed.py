@@ -52,7 +52,9 @@ class WindowedHipBackend:
         lib = _lib.get()
         dev = indices.device
         self.loss, self.c, self.r, self.T = loss, float(c), int(n_components), int(n_windows)
-        self.two_phase = loss == 'wmrb'
+        rec = _engine.LOSSES.get(loss)   # None: a name nobody knows, refused by grads_window
+        self.two_phase = self.hinge = rec is not None and rec.hinge   # any other loss of the table family is refused by grads_window
+        self.weighted = int(bool(rec is not None and rec.weighted))
         self.dtype = dtype
         self.sfx = '_bf16' if dtype is torch.bfloat16 else '_f32'
         self.ld = ld = _lib.padded_ld(self.r, dtype)
@@ -65,7 +67,7 @@ class WindowedHipBackend:
         self.V_shard = V_own   # [rows owned, ld] table dtype, or None on a rank that owns nothing
         self.loss_out = torch.zeros(1, dtype=torch.float64, device=dev)
         self.part = torch.empty(2 * max(m, 1), ld, dtype=torch.float32, device=dev)   # layer 0 sums, layer 1 = one window (MSE)
-        if loss == 'wmrb':
+        if self.hinge:
             self.plan = _engine.InteractionPlan(indices, values, m, self.n_pad, csc=False)
             # user blocks as the resident pass would choose them for the whole catalog: more blocks would fit the slab of one
             # window but leave a handful of entries per (block, item) list
@@ -121,7 +123,7 @@ class WindowedHipBackend:
         """Adds the window's part of the user gradient to layer 0 of ``part`` and writes the raw item gradient of the
         window's rows (this rank's users only) into ``out`` [rows, ld] fp32."""
         lib, s, r = _lib.get(), _lib.stream_ptr(), self.r
-        if self.loss == 'wmrb':
+        if self.hinge:
             w = self.wplan
             if self.m:
                 _lib.check(getattr(lib, 'tmf_wmrb_gradu3' + self.sfx)(ctypes.byref(self.lists[t]), w.D, w.delta,
@@ -135,7 +137,7 @@ class WindowedHipBackend:
         p = self.sub[t]
         # the losses that are separable per interaction differ in the pass alone
         if self.loss in _engine.LOGISTIC_LOSSES:
-            lg_pass, wt = getattr(lib, 'tmf_logistic_pass' + self.sfx), int(self.loss == 'logistic_w')
+            lg_pass, wt = getattr(lib, 'tmf_logistic_pass' + self.sfx), self.weighted
 
             def row_pass(*args):   # tmf_mse_pass's arguments; `weighted` stands before the stream
                 return lg_pass(*args[:-1], wt, args[-1])
@@ -162,7 +164,7 @@ class WindowedHipBackend:
         if self.m:
             _lib.check(getattr(lib, 'tmf_wmrb_finish' + self.sfx)(self.part, 1, self.m, self.U,
                                                                   self.U_nxt, self.r, _lib.EPI_ADAM, self.adam, s), lib)
-        if self.loss == 'wmrb':
+        if self.hinge:
             _lib.check(lib.tmf_sum_f32(self.loss_part, self.m, self.loss_out, s), lib)
         else:
             self.loss_out[0] = self.loss_w.sum()

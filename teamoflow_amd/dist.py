@@ -373,7 +373,8 @@ def fit_item_sharded(model, epochs, n_users, n_items, interactions, lr, U0, V0, 
     loss = _engine.form_loss(model, 'multi-GPU', OPTIMIZER_TEXT)
     world, rank = _world(group)
     dev = interactions.device
-    wmrb = loss == 'wmrb'
+    rec = _engine.LOSSES[loss]
+    wmrb = rec.hinge   # the other losses of the table family have no such form: the route refuses them, and so does the epoch
     T = world * max(1, int(windows_per_rank))
     r, dtype = model.n_components, model.factor_dtype
     ld = _lib.padded_ld(r, dtype)
@@ -381,10 +382,9 @@ def fit_item_sharded(model, epochs, n_users, n_items, interactions, lr, U0, V0, 
     local = getattr(model, 'local_users', None)
     S = int(model.random_ind.shape[1]) if wmrb and local is None else 0   # a WMRB user also costs its negatives
     b, e, idx, val = rank_user_block(model, interactions, n_users, world, rank, S)
-    R, c = None, 0.0
+    R, c = None, rec.param(model)
     if wmrb:
         R = rank_negatives(model, b, e, n_users, n_items, dev)
-        c = model.n_items / model.n_samples
     mine = owned_item_rows(rows, T, world, rank, dev)          # global ids of the owned rows of the padded catalog
     blocks = owned_blocks(rows, T, world, rank, n_items)       # the same as slices: (local row, global row, count) per window
     n_valid = sum(cnt for _, _, cnt in blocks)
@@ -487,19 +487,19 @@ def fit_data_parallel(model, epochs, n_users, n_items, interactions, lr, U0, V0,
     loss = _engine.form_loss(model, 'multi-GPU', OPTIMIZER_TEXT)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     dev = interactions.device
-    wmrb = loss == 'wmrb'
+    rec = _engine.LOSSES[loss]
+    wmrb = rec.hinge   # the other losses of the table family have no such form: the route refuses them, and so does the epoch
     local = getattr(model, 'local_users', None)
     S = int(model.random_ind.shape[1]) if wmrb and local is None else 0   # a WMRB user also costs its negatives
     b, e, idx, val = rank_user_block(model, interactions, n_users, world, rank, S)
     if local is not None and tuple(torch.as_tensor(U0).shape)[0] != e - b:
         raise ValueError(f'local_users = {local}: the user initialiser must return the {e - b} rows of this block')
     n_pad = padded_rows(n_items, world)
-    plan = _engine.InteractionPlan(idx, val, e - b, n_pad, user_chunks=1 if wmrb else _engine.mse_user_chunks(), csc=not wmrb)
+    plan = _engine.InteractionPlan(idx, val, e - b, n_pad, **rec.plan_form())
     ld = _lib.padded_ld(model.n_components, model.factor_dtype)
-    wplan, c = None, 0.0
+    wplan, c = None, rec.param(model)
     if wmrb:
         R = rank_negatives(model, b, e, n_users, n_items, dev)
-        c = model.n_items / model.n_samples
         wplan = _engine.wmrb_plan_for(plan, R, model.n_components, model.factor_dtype)
     V0p = torch.zeros(n_pad, model.n_components, dtype=torch.float32, device=dev)
     V0p[:n_items] = torch.as_tensor(V0).detach().to(device=dev, dtype=torch.float32)
@@ -507,7 +507,7 @@ def fit_data_parallel(model, epochs, n_users, n_items, interactions, lr, U0, V0,
     st = _engine.TrainState(U_blk, V0p, plan, model.n_components, wplan, dtype=model.factor_dtype)
     adam = _engine.adam_constants(lr)
     backend = HipBackend(st, loss, c, adam)
-    dp = DataParallelEpoch(backend, plan.n_pos if wmrb else plan.nnz, group=group)
+    dp = DataParallelEpoch(backend, rec.denominator(plan), group=group)
     losses = torch.zeros(max(epochs, 1), dtype=torch.float64, device=dev)
     for epoch in range(epochs):
         losses[epoch] = dp.step()

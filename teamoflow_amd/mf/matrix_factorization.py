@@ -2,8 +2,8 @@
 /root/reference/src/teamoflow/mf/matrix_factorization.py:23-475, computed sparsely on MI355X.
 
 Dispatch (``MatrixFactorization._route``; same isinstance test the reference uses at :115,:136-162): a model made of
-(``LinearEmbedding`` | ``BiasedLinearEmbedding``) x indicator features x (``MSELoss`` | ``WMRBLoss`` | ``KLDivergenceLoss`` |
-``LogisticLoss`` | ``BPRLoss`` | ``WARPLoss`` | ``KOSWARPLoss`` | ``SampledSoftmaxLoss`` | ``FullSoftmaxLoss``) - or ``LinearEmbedding`` over ``SparseFeatures`` on either side, or with ``relu_engine = True``
+(``LinearEmbedding`` | ``BiasedLinearEmbedding``) x indicator features x a loss of the table ``_engine.LOSSES`` (``ENGINE_LOSSES``) - or
+``LinearEmbedding`` over ``SparseFeatures`` on either side, or with ``relu_engine = True``
 (off by default) a ``ReLUEmbedding`` side over either - trains on the HIP engine (``_engine.py`` -> libtmf.so); for unbiased MSE / WMRB it
 needs a GPU - there is no CPU fallback for them.  Any other combination of plug-ins (dense features, ReLU embeddings, user subclasses)
 trains through ``_fit_generic``: the reference's dense loop written with torch autograd around the plug-ins' own ``get_repr`` /
@@ -25,8 +25,7 @@ import torch
 from .. import _als, _engine, _lib, _ops
 from .embedding_graphs import BiasedLinearEmbedding, Embeddings, LinearEmbedding, ReLUEmbedding
 from .initializer_graphs import NormalInitializer
-from .loss_graphs import (BPRLoss, FullSoftmaxLoss, KLDivergenceLoss, KOSWARPLoss, LogisticLoss, LossGraph, MSELoss, SampledSoftmaxLoss,
-                          WARPLoss, WMRBLoss)
+from .loss_graphs import LossGraph, MSELoss  # noqa: F401  (what the engine knows of every other loss is _engine.LOSSES)
 from .sparse import IndicatorFeatures, SparseFeatures, SparseInteractions, default_device, is_indicator
 from .utils import gather_matrix_indices, random_sampler, random_sampler_device
 
@@ -35,14 +34,19 @@ HOST_SAMPLER_MAX_WORK = 2_000_000_000  # n_users * n_items above which generate_
 GRAPH_EPOCHS = 50              # epochs captured per hipGraph on launch-bound problems
 GRAPH_MAX_WORK = 20_000_000    # interactions + sampled scores per epoch below which fit() uses graphs
 
+
+def _loss_classes(keep=lambda rec: True):
+    return tuple(dict.fromkeys(rec.cls for rec in _engine.LOSSES.values() if keep(rec)))   # in the table's order, each class once
+
+
 # What trains where (DESIGN.md prints this table; MatrixFactorization._route reads it).  A row is a feature of a fit, a column a
 # setting that leaves the single-GPU full-batch fp32 fresh-Adam fit: 'ok' = the engine has that form, 'generic' = fit() trains
 # through _fit_generic, 'refuse' = NotImplementedError before any weight is drawn or plan built.
-ENGINE_LOSSES = (MSELoss, WMRBLoss, KLDivergenceLoss, LogisticLoss, BPRLoss, WARPLoss, KOSWARPLoss, SampledSoftmaxLoss,
-                 FullSoftmaxLoss)   # exactly these types, no subclass
-TABLE_LOSSES = (WMRBLoss, BPRLoss, WARPLoss, KOSWARPLoss, SampledSoftmaxLoss)   # these and their subclasses read the static negative table
-PAIR_STEP_LOSSES = (BPRLoss, WARPLoss, KOSWARPLoss, SampledSoftmaxLoss)   # the route feature 'pair': a pair step of the sliced user pass
-PAIR_ROW_LOSSES = PAIR_STEP_LOSSES + (FullSoftmaxLoss,)             # the losses that answer by the row 'pair': single GPU, full batch
+ENGINE_LOSSES = _loss_classes()                                     # exactly these types, no subclass
+TABLE_LOSSES = _loss_classes(lambda rec: rec.table)                 # these and their subclasses read the static negative table
+PAIR_STEP_LOSSES = _loss_classes(lambda rec: rec.sliced_only)       # the route feature 'pair': a pair step of the sliced user pass
+PAIR_ROW_LOSSES = _loss_classes(lambda rec: rec.route == 'pair')    # the losses that answer by the row 'pair': single GPU, full batch
+_FEEDS = {feeds: _loss_classes(lambda rec: rec.feeds == feeds) for feeds in ('samples', 'serial')}   # Loss.feeds -> these and their subclasses
 _SETTINGS = {   # column -> (the attribute a refusal names, has the model left its default?), in the order refusals are met
     'relu_engine': ('relu_engine', lambda m: getattr(m, 'relu_engine', 0)     # counts beside a ReLUEmbedding side only
                     and ReLUEmbedding in (type(m.user_repr_graph), type(m.item_repr_graph))),
@@ -71,7 +75,7 @@ _BUILT = {'pair': 'only the single-GPU full-batch fit is built for this loss',
 
 
 class SampleTableMissing(AttributeError):
-    """WMRB, BPR, WARP, k-OS WARP and the sampled softmax need the static negative table: build the model with generate_sample=True
+    """The losses of the table family (TABLE_LOSSES) need the static negative table: build the model with generate_sample=True
     (the reference fails with AttributeError inside gather_matrix_indices, matrix_factorization.py:153)."""
 
 
@@ -192,8 +196,10 @@ class MatrixFactorization:
         its aux width 5 r fits a table row) when no feature of the fit answers 'generic'.  Unbiased MSE / WMRB have no row in ROUTES:
         every setting is a form of theirs, and without a GPU they fail in _fit_sparse - there is no CPU fallback."""
         loss, kinds = type(self.loss_graph), (type(self.user_repr_graph), type(self.item_repr_graph))
+        rec = next((rec for rec in _engine.LOSSES.values() if rec.cls is loss), None)   # a class's records share route and family
+        row = rec.route if rec else None
         # the refusals, in the order a model that meets several has always met them
-        answers = [self._answer('pair', loss.__name__)] if loss in PAIR_ROW_LOSSES else []
+        answers = [self._answer('pair', loss.__name__)] if row == 'pair' else []
         if any(self._alphas()):
             self._answer('l2', 'user_alpha / item_alpha > 0')
         every = self._resample_setting()[0]
@@ -207,11 +213,10 @@ class MatrixFactorization:
                         for kind, f, sparse in zip(kinds, (user_features, item_features), featured))):
             return 'generic'
         structured = any(featured) or BiasedLinearEmbedding in kinds or ReLUEmbedding in kinds
-        answers += [self._answer(feature) for feature, there in (('kl', loss is KLDivergenceLoss), ('logistic', loss is LogisticLoss),
-                                                                 ('side', structured)) if there]
+        answers += [self._answer(feature) for feature, there in ((row, row not in (None, 'pair')), ('side', structured)) if there]
         if 'generic' in answers:
             return 'generic'
-        if loss is FullSoftmaxLoss:
+        if rec.family == 'catalog':
             # the sweep kernels' own limits.  Refused, not handed to the generic loop: its [m, n] matrix is what this loss avoids
             if self.factor_dtype is not torch.float32:
                 raise NotImplementedError(f'FullSoftmaxLoss with factor_dtype={self.factor_dtype}: its kernels sweep float32 tables '
@@ -397,7 +402,8 @@ class MatrixFactorization:
         if interactions.device != dev:
             interactions = interactions.to(dev)
         loss = _engine.loss_name(self.loss_graph)
-        if loss in _engine.PAIR_LOSSES and self.random_ind is None:
+        rec = _engine.LOSSES[loss]
+        if rec.table and self.random_ind is None:
             raise SampleTableMissing(f'{type(self.loss_graph).__name__} needs generate_sample=True (random_ind is None)')
         form = self._engine_form()
         if form == 'batch_users':
@@ -414,18 +420,16 @@ class MatrixFactorization:
         st, c = self._sparse_state(loss, n_users, n_items, interactions, U0, V0, dev, user_feat, item_feat)
         if st is None:
             return False   # an empty class: no moments to take (the reference's arithmetic gives NaN; the generic path keeps that)
-        # KL: the loss is one scalar, its mean is itself; the losses over positives: their number
-        denom = st.plan.n_pos if loss in _engine.PAIR_LOSSES + ('full_softmax',) else 1 if loss == 'kl' else st.plan.nnz
+        denom = rec.denominator(st.plan)   # a loss over positives: their number; one that is a single scalar: its mean is itself
         self.loss_history_ = []
         step = self._sparse_step(st, loss, c, lr)
         # Launch-bound problems (a few hundred microseconds of kernels per epoch): capture an even number of
         # epochs into one hipGraph and replay it - the per-launch host cost disappears from the loop.
-        work = st.plan.nnz + (st.plan.n_users * st.wplan.S if loss in _engine.PAIR_LOSSES else 0) \
-            + (st.plan.n_users * st.plan.n_items if loss == 'full_softmax' else 0)   # every score of the catalog, five times an epoch
         G = min(epochs - epochs % 2, GRAPH_EPOCHS)
-        use_graph = G >= 4 and work <= GRAPH_MAX_WORK and os.environ.get('TMF_NO_GRAPH') is None and self.optimizer != 'adam'
+        use_graph = G >= 4 and rec.work(st.plan, st.wplan) <= GRAPH_MAX_WORK and os.environ.get('TMF_NO_GRAPH') is None \
+            and self.optimizer != 'adam'
         every = self._resample_setting()[0]   # 0 for a loss that reads no table
-        self.resample_rounds_ = int(loss in _engine.PAIR_LOSSES)
+        self.resample_rounds_ = int(rec.table)
         resample = None
         if every and epochs > every:   # more than one round: no graph (a captured graph holds the plan's pointers)
             use_graph = False
@@ -438,27 +442,18 @@ class MatrixFactorization:
         return True
 
     def _sparse_state(self, loss, n_users, n_items, interactions, U0, V0, dev, user_feat=None, item_feat=None):
-        """(TrainState, c) of a single-GPU full-batch fit: the interaction plan, for the table losses the checked negative table and its
-        plan (BPR, WARP, k-OS WARP, softmax: always the sliced user pass), for WMRB c = n_items / n_samples (for the softmax that or 1;
-        for KOSWARPLoss the pair (k, n) travels in c's place), and the starting bias of a BiasedLinearEmbedding side.  (None, 0.0) for KL with an empty class."""
-        wmrb, kl = loss in _engine.PAIR_LOSSES, loss == 'kl'
-        plan = _engine.InteractionPlan(interactions.indices, interactions.values, n_users, n_items,
-                                       user_chunks=1 if wmrb else _engine.mse_user_chunks(), csc=not wmrb)
-        if kl and (plan.n_pos == 0 or int((plan.val_u <= 0).sum()) == 0):
+        """(TrainState, c) of a single-GPU full-batch fit, by the record of ``loss`` in _engine.LOSSES: the interaction plan, for the table
+        family the checked negative table and its plan, prepared for the loss, c = the loss's parameter for this model, and the starting
+        bias of a BiasedLinearEmbedding side.  (None, 0.0) for KL with an empty class."""
+        rec = _engine.LOSSES[loss]
+        plan = _engine.InteractionPlan(interactions.indices, interactions.values, n_users, n_items, **rec.plan_form())
+        if rec.global_moments and (plan.n_pos == 0 or int((plan.val_u <= 0).sum()) == 0):
             return None, 0.0
-        wplan, c = None, 0.0
-        if wmrb:
+        wplan = None
+        if rec.table:
             R = _engine.checked_negatives(self.random_ind, n_users, n_items, dev)
-            if loss == 'wmrb' or (loss == 'softmax' and self.loss_graph.catalog_scale):
-                c = self.n_items / self.n_samples  # constructor ints, true division (:167)
-            elif loss == 'softmax':
-                c = 1.0
-            wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype, force_sliced=loss != 'wmrb')
-            if loss in ('warp', 'warp_kos'):
-                wplan.sample_rank()   # WARP tries the samples in the table's order: built here, before any epoch is captured
-            if loss == 'warp_kos':
-                c = (self.loss_graph.k, self.loss_graph.n)
-                wplan.kos_omega(plan.nnz)   # the weights' buffer: the same one every epoch
+            wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype, force_sliced=rec.sliced_only)
+            rec.prepare(wplan, plan)   # before any epoch runs or is captured
         r = self.n_components
         # a biased side starts from the bias an earlier fit left on the model, as in the reference (:139-146), else from zeros
         bias0 = [None if type(graph) is not BiasedLinearEmbedding else torch.zeros(r) if kept is None else kept
@@ -475,13 +470,13 @@ class MatrixFactorization:
                                    Wr0=torch.randn(n_features, aux, device=dev) if kept_w is None else kept_w,
                                    b0=torch.zeros(aux, device=dev) if kept_b is None else kept_b)
                 feat[side] = None
-        st = _engine.TrainState(U0, V0, plan, r, wplan, dtype=self.factor_dtype, kl=kl, user_bias=bias0[0], item_bias=bias0[1],
+        st = _engine.TrainState(U0, V0, plan, r, wplan, dtype=self.factor_dtype, user_bias=bias0[0], item_bias=bias0[1],
                                 user_feat=feat[0], item_feat=feat[1], user_relu=relu0[0], item_relu=relu0[1],
-                                full_softmax=loss == 'full_softmax')
+                                **({rec.flag: True} if rec.flag else {}))
         alphas = self._alphas()
         if any(alphas):   # never called with zeros: an unpenalised fit is today's state, launch for launch
             st.set_l2(*alphas)
-        return st, c
+        return st, rec.param(self)
 
     def _sparse_step(self, st, loss, c, lr):
         """step(epoch, out): one epoch, its loss sum into ``out``, by the reference's fresh Adam or by optimizer='adam' (kept moments)."""
@@ -603,6 +598,7 @@ class MatrixFactorization:
         user_alpha, item_alpha = self._alphas()
         every = self._resample_setting()[0]
         self.resample_rounds_ = int(isinstance(self.loss_graph, TABLE_LOSSES) and random_ind is not None)
+        feeds = next((feeds for feeds, classes in _FEEDS.items() if isinstance(self.loss_graph, classes)), 'dense')   # Loss.feeds
         for epoch in range(epochs):
             start = timeit.default_timer()
             if every and epoch and epoch % every == 0 and random_ind is not None:   # round epoch // every: its own table, random_ind stays
@@ -620,13 +616,11 @@ class MatrixFactorization:
             self._keep_aux_variables()
             predictions = user_embedding @ item_embedding.T
             tf_sample_predictions = tf_prediction_serial = None
-            if isinstance(self.loss_graph, TABLE_LOSSES):
+            if feeds == 'samples':
                 if random_ind is None:
                     raise SampleTableMissing(f'{type(self.loss_graph).__name__} needs generate_sample=True (random_ind is None)')
                 tf_sample_predictions = torch.gather(predictions, 1, random_ind.to(torch.int64))
-                tf_prediction_serial = predictions[idx[:, 0], idx[:, 1]]
-                predictions = None
-            elif isinstance(self.loss_graph, KLDivergenceLoss):
+            if feeds != 'dense':
                 tf_prediction_serial = predictions[idx[:, 0], idx[:, 1]]
                 predictions = None
             loss_fn = self.loss_graph.get_loss(tf_interactions=interactions, tf_sample_predictions=tf_sample_predictions,

@@ -1,5 +1,6 @@
-"""The KernelTimer span names of every epoch - what bench.py and tools/time_*.py read - pinned as exact sets, and
-_engine.run_epoch against the direct epoch_* call: same loss and same tables, bit for bit, from equal starting tables.
+"""The KernelTimer span names of every epoch - what bench.py and tools/time_*.py read - pinned as exact sets for all ten engine
+names, and _engine.run_epoch against the direct epoch_* call: same loss and same tables, bit for bit, from equal starting tables.
+TrainState.set_negatives of a KOSWARPLoss state: a fresh state's bits, and nothing allocated by the epoch after it.
 _engine.epoch_sides over every pair of side forms: the span names in launch order.
 96 users x 64 items, r = 16, S = 8, ~600 interactions of which user 0 has 300 (a row cut into three segments at chunk = 128)."""
 import pytest
@@ -12,7 +13,14 @@ MSE = {'mse_user_pass', 'mse_item_pass'}
 KL = {'kl_moments', 'kl_coeffs', 'kl_user_pass', 'kl_item_pass'}
 FUSED = {'wmrb_user_pass', 'wmrb_item_pass', 'wmrb_combine'}
 SLICED = FUSED | {'wmrb_scores', 'wmrb_hinge', 'wmrb_gradu', 'wmrb_finish'}
+LOGISTIC = {'logistic_user_pass', 'logistic_item_pass'}
+FSM = {'fsm_lse', 'fsm_user_pass', 'fsm_item_pass', 'fsm_wsum_user', 'fsm_wsum_item', 'fsm_user_step', 'fsm_item_step'}
+PAIRS = ('wmrb', 'bpr', 'warp', 'warp_kos', 'softmax')   # the losses over the negative table; all but 'wmrb' on the sliced pass alone
 BIAS = {side + name for side in ('user_', 'item_') for name in ('bias_colsum', 'bias_adam', 'adam_bias_rows')}
+
+
+def pair_spans(*pair_step):
+    return (SLICED - {'wmrb_hinge'}) | set(pair_step)
 
 
 @pytest.fixture(scope='module')
@@ -34,13 +42,15 @@ def prob():
 
 
 def state(eng, prob, loss, sliced=None, biased=False):
-    plan = eng.InteractionPlan(prob['idx'], prob['val'], M, N, chunk=CHUNK, csc=loss != 'wmrb')
+    table = loss in PAIRS
+    plan = eng.InteractionPlan(prob['idx'], prob['val'], M, N, chunk=CHUNK, csc=not table)
     assert plan.seg_u.n_long >= 1 and int(plan.rowptr_u[1]) == 300    # user 0's row is cut
     wplan = None
-    if loss == 'wmrb':
+    if table:
         wplan = eng.WmrbPlan(plan, prob['R'], chunk=CHUNK, item_slices=2 if sliced else 1, n_components=R_, sliced=sliced)
     bias = torch.zeros(R_) if biased else None
-    return eng.TrainState(prob['U0'], prob['V0'], plan, R_, wplan, kl=loss == 'kl', user_bias=bias, item_bias=bias)
+    return eng.TrainState(prob['U0'], prob['V0'], plan, R_, wplan, kl=loss == 'kl', user_bias=bias, item_bias=bias,
+                          full_softmax=loss == 'full_softmax')
 
 
 def run(eng, st, call):
@@ -58,19 +68,111 @@ def same(a, b):
     return a[0] == b[0] and torch.equal(a[1], b[1]) and len(a[2]) == len(b[2]) and all(torch.equal(x, y) for x, y in zip(a[2], b[2]))
 
 
-@pytest.mark.parametrize('loss,sliced,names', [('mse', None, MSE), ('kl', None, KL), ('wmrb', False, FUSED), ('wmrb', True, SLICED)],
-                         ids=['mse', 'kl', 'wmrb_fused', 'wmrb_sliced'])
+KOS = (3, 4)   # KOSWARPLoss(k=3, n=4)
+CASES = [('mse', None, MSE), ('kl', None, KL), ('wmrb', False, FUSED), ('wmrb', True, SLICED), ('logistic', None, LOGISTIC),
+         ('logistic_w', None, LOGISTIC), ('bpr', True, pair_spans('bpr_pairs')), ('warp', True, pair_spans('warp_pairs')),
+         ('warp_kos', True, pair_spans('kos_weights', 'warp_pairs')), ('softmax', True, pair_spans('softmax_pairs')),
+         ('full_softmax', None, FSM)]
+
+
+@pytest.mark.parametrize('loss,sliced,names', CASES, ids=['mse', 'kl', 'wmrb_fused', 'wmrb_sliced'] + [case[0] for case in CASES[4:]])
 def test_span_names_and_run_epoch(eng, prob, monkeypatch, loss, sliced, names):
+    """Every engine name: the exact span-name set (pinned from a run of the commit before the loss table existed), and run_epoch
+    against the direct epoch call from equal starting tables - the same loss and the same tables, bit for bit."""
     for name in ('TMF_ROW_STATIONARY', 'TMF_SCORES5', 'TMF_SCORES6', 'TMF_ROWS4'):
         monkeypatch.delenv(name, raising=False)
-    c = N / S
-    direct = {'mse': lambda st, adam, out, prof: eng.epoch_mse(st, adam, out, prof=prof),
-              'kl': lambda st, adam, out, prof: eng.epoch_kl(st, adam, out, prof=prof),
-              'wmrb': lambda st, adam, out, prof: eng.epoch_wmrb(st, adam, c, out, prof=prof)}[loss]
+    c = {'wmrb': N / S, 'softmax': N / S, 'warp_kos': KOS}.get(loss, 0.0)   # what travels in c's slot for each loss
+    if loss in PAIRS:
+        pairs = 'hinge' if loss == 'wmrb' else loss
+
+        def direct(st, adam, out, prof):
+            eng.epoch_wmrb(st, adam, c, out, prof=prof, pairs=pairs)
+    else:
+        direct = {'mse': lambda st, adam, out, prof: eng.epoch_mse(st, adam, out, prof=prof),
+                  'kl': lambda st, adam, out, prof: eng.epoch_kl(st, adam, out, prof=prof),
+                  'logistic': lambda st, adam, out, prof: eng.epoch_logistic(st, adam, out, False, prof=prof),
+                  'logistic_w': lambda st, adam, out, prof: eng.epoch_logistic(st, adam, out, True, prof=prof),
+                  'full_softmax': lambda st, adam, out, prof: eng.epoch_full_softmax(st, adam, out, prof=prof)}[loss]
     a = run(eng, state(eng, prob, loss, sliced), direct)
     b = run(eng, state(eng, prob, loss, sliced), lambda st, adam, out, prof: eng.run_epoch(st, adam, out, loss, c, prof=prof))
     assert a[0] == names and b[0] == names
     assert float(a[1]) > 0 and same(a, b)
+
+
+def test_set_negatives_of_a_kos_state_prepares_the_new_plan(eng, prob):
+    """A live KOSWARPLoss state as _fit_sparse builds it, one epoch, set_negatives(second table), one epoch: the bits of a state built
+    fresh on that table from the tables the first epoch left (tests/test_gpu_resample.py does this for WARPLoss), and the epoch after
+    set_negatives allocates nothing - the rebuilt plan has its sample ranks and its omega buffer before it runs."""
+    from teamoflow_amd.mf.loss_graphs import KOSWARPLoss
+    from teamoflow_amd.mf.matrix_factorization import MatrixFactorization
+    from teamoflow_amd.mf.sparse import SparseInteractions
+    dev = torch.device('cuda', torch.cuda.current_device())
+    inter = SparseInteractions(prob['idx'], prob['val'], (M, N)).to(dev)
+    g = torch.Generator().manual_seed(21)
+    T = torch.stack([torch.randperm(N, generator=g)[:S] for _ in range(M)]).to(torch.int32)
+
+    def live(R, U0, V0):
+        model = MatrixFactorization(R_, loss_graph=KOSWARPLoss(*KOS), n_users=M, n_items=N, n_samples=S)
+        model.random_ind = R
+        st, c = model._sparse_state('warp_kos', M, N, inter, U0, V0, dev)
+        assert c == KOS and st.wplan.sliced and st.wplan._rank is not None and st.wplan.omega.shape == (st.plan.nnz,)
+        return st, model._sparse_step(st, 'warp_kos', c, LR)
+
+    def epoch(st, step, out):
+        step(0, out)
+        torch.cuda.synchronize()
+        allocated = torch.cuda.memory_allocated()   # before the copies below
+        return st.U[:, :R_].clone(), st.V[:, :R_].clone(), float(out), allocated
+    out = torch.zeros(1, dtype=torch.float64, device='cuda')
+    st, step = live(prob['R'], prob['U0'], prob['V0'])
+    U1, V1, _, _ = epoch(st, step, out)
+    st.set_negatives(T.cuda())
+    torch.cuda.synchronize()
+    before = torch.cuda.memory_allocated()
+    got = epoch(st, step, out)
+    after = got[3]
+    fresh, fresh_step = live(T, U1.cpu(), V1.cpu())
+    want = epoch(fresh, fresh_step, out)
+    assert got[2] == want[2] and got[2] > 0 and torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    assert not torch.equal(got[0], U1) and torch.equal(st.wplan._rank, fresh.wplan._rank)
+    assert st.wplan.omega is not None
+    assert after == before, (before, after)
+
+
+@pytest.mark.parametrize('by_hand', [True, False], ids=['ranked_by_hand', 'ranked_by_the_first_epoch'])
+def test_set_negatives_of_a_hand_built_ranked_state(eng, prob, by_hand):
+    """A WARP state built without MatrixFactorization, as tools/time_resample_c4.py builds it: wmrb_plan_for(force_sliced=True), then
+    sample_rank() by hand - or left to the first epoch -, then TrainState.  set_negatives builds the ranks of the next plan itself: they
+    are there straight after the call, the epoch after it allocates nothing, and its bits are those of a state built fresh."""
+    g = torch.Generator().manual_seed(22)
+    T = torch.stack([torch.randperm(N, generator=g)[:S] for _ in range(M)]).to(torch.int32).cuda()
+    plan = eng.InteractionPlan(prob['idx'], prob['val'], M, N, chunk=CHUNK, csc=False)
+    adam, out = eng.adam_constants(LR), torch.zeros(1, dtype=torch.float64, device='cuda')
+
+    def build(R, U0, V0, ranked):
+        wplan = eng.wmrb_plan_for(plan, R, R_, force_sliced=True)
+        if ranked:
+            wplan.sample_rank()
+        return eng.TrainState(U0, V0, plan, R_, wplan)
+
+    def epoch(st):
+        eng.epoch_wmrb(st, adam, 0.0, out, pairs='warp')
+        st.swap()
+        torch.cuda.synchronize()
+        return torch.cuda.memory_allocated()
+    st = build(prob['R'], prob['U0'], prob['V0'], by_hand)
+    epoch(st)
+    U1, V1 = st.U[:, :R_].cpu(), st.V[:, :R_].cpu()
+    st.set_negatives(T)
+    assert st.wplan._rank is not None and st.wplan.prepared == [('sample_rank', ())]
+    torch.cuda.synchronize()
+    before = torch.cuda.memory_allocated()
+    assert epoch(st) == before
+    got = float(out)
+    fresh = build(T, U1, V1, True)
+    epoch(fresh)
+    assert float(out) == got and got > 0 and torch.equal(st.U, fresh.U) and torch.equal(st.V, fresh.V)
+    assert torch.equal(st.wplan._rank, fresh.wplan._rank)
 
 
 def test_span_names_of_a_biased_epoch(eng, prob):
