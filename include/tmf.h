@@ -891,6 +891,36 @@ int tmf_fsm_wsum_f32(const float* A, const float* B, int64_t ma, int64_t nb, int
 int tmf_fsm_pos_pass_f32(const tmf_segments* seg, const int32_t* other, const float* val, const float* X_old, const float* Y_old,
                          float* G_out, float* slab, const float* lse, float* loss_part, int n_components, void* stream);
 
+/* EXTENSION (the reference's scores have no item term): the scalar item bias of the table family - scores U[u] . V[i] + b[i] - as two
+ * passes around the pair step of the sliced user pass (csrc/tmf_itembias.hip).  Neither reads a factor table.  TMF_VERSION stays 203:
+ * nothing that existed changes.  No atomics and a fixed order of additions: every output is bit-identical from call to call and does
+ * not depend on the grid.  Nothing is allocated; both are stream-ordered and graph-capturable.
+ *
+ *   tmf_item_bias_add   sp[u, s] += b[R[u, s]] for u < n_users, s < n_samples and pk[k] += b[col[k]] for k < nnz: one fp32 add per
+ *                       score, so a non-finite b[i] reaches the scores of item i only.  b: [n_items] fp32; R, sp: [n_users, n_samples]
+ *                       contiguous (16-byte pieces where both are 16-byte aligned, element by element otherwise and behind the last
+ *                       whole piece); col, pk: [nnz].  The ids are the plan's, already checked to lie in [0, n_items).  n_users = 0,
+ *                       n_samples = 0 and nnz = 0 are TMF_OK (nothing to add: no launch when all scores are absent); a negative
+ *                       count or a null pointer to something that is read: TMF_E_INVALID before any launch.
+ *   tmf_item_bias_grad  g[i] = the sum of wbuf[ent_w[e]] over the entries e of the list rows blk * n_items + i, blk < user_chunks, of
+ *                       rowptr_e [user_chunks * n_items + 1] (the WmrbPlan entry lists; what lies behind the last list row is never
+ *                       read), then b_out[i] = fresh-Adam(b_old[i], g[i]) under TMF_EPI_ADAM (the arithmetic of tmf_adam_fresh_rows_f32)
+ *                       or b_out[i] = g[i] under TMF_EPI_GRAD (b_old may be NULL).  b_out may be b_old.  A list row is cut into chunks
+ *                       of `chunk` entries, every chunk summed by one wave in fp64: chunk 0 of every list row always, and the chunks
+ *                       c >= 1 the caller lists - xrow[k] / xchunk[k] (list row, chunk) for k < n_extra, ordered by (item, block,
+ *                       chunk), xptr [n_items + 1] the first k of every item - which must be all chunks c >= 1 that hold entries.
+ *                       The chunk sums go to the workspace; item i adds chunk 0 of its blocks in block order, then its further
+ *                       chunks in k order, and rounds to fp32 once.  An item without entries gets g = 0 exactly, and fresh-Adam
+ *                       leaves its bias as it is.  n_extra = 0: xrow / xchunk / xptr are not read.  n_items = 0: TMF_OK.
+ *   tmf_item_bias_grad_workspace_bytes  (user_chunks * n_items + n_extra) fp64 sums; the workspace is 8-byte aligned. */
+int tmf_item_bias_add(const float* b, int32_t n_items, const int32_t* R, int64_t n_users, int32_t n_samples, float* sp,
+                      const int32_t* col, int64_t nnz, float* pk, void* stream);
+size_t tmf_item_bias_grad_workspace_bytes(int32_t n_items, int32_t user_chunks, int64_t n_extra);
+int tmf_item_bias_grad(const int64_t* rowptr_e, int32_t n_items, int32_t user_chunks, const int32_t* ent_w, const float* wbuf,
+                       int32_t chunk, const int32_t* xrow, const int32_t* xchunk, const int64_t* xptr, int64_t n_extra,
+                       const float* b_old, float* b_out, int epi, tmf_adam adam, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

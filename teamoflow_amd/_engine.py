@@ -1019,6 +1019,55 @@ class Scores5Plan(_ScoreStreams):
         self.sync = torch.zeros(max(nb // 4, 1), dtype=i32, device=dev)
 
 
+ITEM_BIAS_CHUNK = DEFAULT_CHUNK   # list entries one wave of tmf_item_bias_grad sums (longer list rows are cut into several chunks)
+
+
+def item_bias_chunks(rowptr_e, n_items, chunk=ITEM_BIAS_CHUNK):
+    """The chunks c >= 1 of the entry lists ``rowptr_e`` (list row = block * n_items + item) as tmf_item_bias_grad takes them (chunk 0
+    of every list row needs no table): -> (xrow, xchunk int32 [n_extra], xptr int64 [n_items + 1], n_extra), ordered by (item, block,
+    chunk).  Built once per plan with torch, on the lists' device."""
+    dev = rowptr_e.device
+    lens = rowptr_e[1:] - rowptr_e[:-1]
+    extra = torch.clamp((lens + (chunk - 1)) // chunk - 1, min=0)
+    rows = torch.nonzero(extra).flatten()                       # the list rows longer than a chunk, ascending: block-major
+    rows = rows[torch.sort(rows % n_items, stable=True)[1]]     # by item, an item's blocks in their order
+    cnt = extra[rows]
+    n_extra = int(cnt.sum())
+    xrow = torch.repeat_interleave(rows, cnt, output_size=n_extra)
+    first = _excl_cumsum(cnt)[:-1]
+    xchunk = torch.arange(n_extra, device=dev) - torch.repeat_interleave(first, cnt, output_size=n_extra) + 1
+    per_item = torch.zeros(n_items, dtype=torch.int64, device=dev).index_add_(0, rows % n_items, cnt)
+    return xrow.to(torch.int32).contiguous(), xchunk.to(torch.int32).contiguous(), _excl_cumsum(per_item), n_extra
+
+
+class ItemScalarBias:
+    """The scalar item bias of a table-family state (scores U[u] . V[i] + b[i]; csrc/tmf_itembias.hip): ``b`` and its second buffer
+    ``b_nxt`` - the stepped bias under TMF_EPI_ADAM (TrainState.swap exchanges them), the raw gradient under TMF_EPI_GRAD (``epi``:
+    persistent Adam steps b in place from it) -, both fp32 [n_items rounded up to 4] with zeros behind n_items, so that the vector
+    is also a padded [rows, 4] table for the table steps; and, per WmrbPlan (``adopt``), the chunk tables and the fp64 workspace of
+    tmf_item_bias_grad.  The passes read everything else (R, rowptr_e, ent_w, wbuf) from the state's plan when they launch."""
+
+    def __init__(self, b0, n_items, dev):
+        b0 = torch.as_tensor(b0).detach().to(device=dev, dtype=torch.float32).reshape(-1)
+        if b0.numel() != n_items:
+            raise ValueError(f'item_scalar_bias of {b0.numel()} elements for {n_items} items')
+        self.n, self.chunk, self.epi = int(n_items), ITEM_BIAS_CHUNK, _lib.EPI_ADAM
+        self.b = torch.zeros(max(-(-self.n // 4) * 4, 4), dtype=torch.float32, device=dev)
+        self.b[:self.n] = b0
+        self.b_nxt = torch.zeros_like(self.b)
+
+    def adopt(self, wplan):
+        lib = _lib.load_library()
+        self.xrow = self.xchunk = self.xptr = self.ws = None   # the old plan's, before the next ones are built
+        self.xrow, self.xchunk, self.xptr, self.n_extra = item_bias_chunks(wplan.rowptr_e, self.n, self.chunk)
+        nb = lib.tmf_item_bias_grad_workspace_bytes(self.n, wplan.user_chunks, self.n_extra)
+        self.ws = torch.empty(max(nb // 8, 1), dtype=torch.float64, device=self.b.device)
+
+    @property
+    def value(self):
+        return self.b[:self.n]
+
+
 class TrainState:
     """Double-buffered factor tables [rows, ld] and the scratch the passes need.
     ``V_tables`` = (V, V_nxt) already padded: several states (the user batches of a mini-batch fit) step the SAME item table;
@@ -1026,8 +1075,16 @@ class TrainState:
     (``share_scratch``) instead of once per state."""
 
     def __init__(self, U0, V0, plan, n_components, wplan=None, dtype=torch.float32, V_tables=None, scratch=None, kl=False,
-                 user_bias=None, item_bias=None, user_feat=None, item_feat=None, user_relu=None, item_relu=None, full_softmax=False):
+                 user_bias=None, item_bias=None, user_feat=None, item_feat=None, user_relu=None, item_relu=None, full_softmax=False,
+                 item_scalar_bias=None):
         dev = plan.col_u.device
+        # the scalar item bias b0 [n_items] (None: today's state): everything it needs is allocated here and in set_negatives
+        self.ib = None
+        if item_scalar_bias is not None:
+            if wplan is None or not wplan.sliced or dtype is not torch.float32 or V_tables is not None or scratch is not None:
+                raise ValueError('item_scalar_bias needs a sliced WmrbPlan (wmrb_plan_for(force_sliced=True)) and float32 factor '
+                                 'tables and scratch of its own')
+            self.ib = ItemScalarBias(item_scalar_bias, plan.n_items, dev)
         if full_softmax:   # epoch_full_softmax: every user's log-partition (rewritten each epoch) and its number of positives, as fp32
             if dtype is not torch.float32 or int(n_components) > FULL_SOFTMAX_MAX_COMPONENTS or plan.seg_i is None or V_tables is not None:
                 raise ValueError(f'the full softmax needs float32 tables of its own with n_components <= {FULL_SOFTMAX_MAX_COMPONENTS} '
@@ -1158,6 +1215,8 @@ class TrainState:
             n_work = wplan.vrows.n_vrows if wplan.vrows is not None else plan.n_items
             nb = L.tmf_wsum_rows4_workspace_bytes(n_work, wplan.user_chunks, self.rows4_per_launch)
             self.rows4_sync = torch.zeros(max(nb // 4, 1), dtype=torch.int32, device=dev)
+        if self.ib is not None:
+            self.ib.adopt(wplan)
         return need
 
     def set_negatives(self, R):
@@ -1166,7 +1225,9 @@ class TrainState:
         (WmrbPlan.prepared: the sample ranks, the omega buffer - by Loss.prepare, by hand or by an epoch; no epoch after this call
         allocates) and everything derived from it again by _adopt_wplan.  The tables, the side objects, l2, the gradient tables and
         moments of persistent Adam and the InteractionPlan are not touched.  The old plan - its entry lists, score streams, slice
-        lists and ranks - is dropped BEFORE the new one is built, so the peak stays that of building the state.  ``sp`` / ``pk`` /
+        lists and ranks - is dropped BEFORE the new one is built, so the peak stays that of building the state.  The scalar item bias
+        carries over like the tables; its passes read R, rowptr_e, ent_w and wbuf from the plan the state holds when they launch, and
+        its chunk tables and workspace are built again for the new lists.  ``sp`` / ``pk`` /
         ``part`` keep their sizes (m, S and nnz do not change); the slab grows when the new lists need more, and the sync words are
         allocated and zeroed again.  A graph captured over this state holds the old plan's pointers: capture after, not across."""
         if self._bufs is None:
@@ -1242,6 +1303,8 @@ class TrainState:
             self.U, self.U_nxt = self.U_nxt, self.U
         if self.V_nxt is not None:
             self.V, self.V_nxt = self.V_nxt, self.V
+        if self.ib is not None and self.ib.epi == _lib.EPI_ADAM:
+            self.ib.b, self.ib.b_nxt = self.ib.b_nxt, self.ib.b
 
 
 class BiasSide:
@@ -1712,7 +1775,9 @@ def softmax_pairs(lib, st, c, prof, head, tail):
 
 
 def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, U_out=None, pairs='hinge'):
-    """Sliced user pass: scores -> the pair step PAIRS[pairs] -> gradU (+ weights into entry order) -> finish (csrc/tmf_wmrb.hip)."""
+    """Sliced user pass: scores -> the pair step PAIRS[pairs] -> gradU (+ weights into entry order) -> finish (csrc/tmf_wmrb.hip).
+    A state with a scalar item bias (TrainState.ib) adds b to the scores behind the scores kernel and takes b's gradient and step
+    behind the pair step (csrc/tmf_itembias.hip); without one, not a launch more."""
     p, w, r = st.plan, st.wplan, st.r
     m, s = p.n_users, _lib.stream_ptr()
     lists = w.lists(p)
@@ -1742,7 +1807,14 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
     else:
         _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores3' + st.sfx)(lists, st.U, st.V, st.sp,
                                                                                 st.pk, r, s))
+    ib = st.ib
+    if ib is not None:   # the scalar item bias, into the scores before any pair step reads them (tmf_kos_weights ranks positives by pk)
+        _timed(prof, 'item_bias_add', lambda: lib.tmf_item_bias_add(ib.b, p.n_items, w.R, m, w.S, st.sp, p.col_u, p.nnz, st.pk, s))
     PAIRS[pairs].pair_step(lib, st, c, prof, (p.rowptr_u, p.val_u, st.pk, st.sp), (w.delta, w.D, st.loss_part, w.hinge_order, s))
+    if ib is not None:   # its gradient: every item the sum of the weights of its list entries, and the step (or, EPI_GRAD, the gradient)
+        _timed(prof, 'item_bias_grad', lambda: lib.tmf_item_bias_grad(
+            w.rowptr_e, p.n_items, w.user_chunks, w.ent_w, w.wbuf, ib.chunk, ib.xrow, ib.xchunk, ib.xptr, ib.n_extra,
+            ib.b, ib.b_nxt, ib.epi, adam, ib.ws, ib.ws.numel() * 8, s))
     if st.row_stationary:
         # gradU + finish in one row-stationary kernel (lane groups own users and walk the slices; no partial rows)
         _timed(prof, 'wmrb_gradu', lambda: getattr(lib, 'tmf_wmrb_gradu4' + st.sfx)(

@@ -71,7 +71,30 @@ ROUTES = {feature: dict(zip(_SETTINGS, row.split(), strict=True)) for feature, r
 _BUILT = {'pair': 'only the single-GPU full-batch fit is built for this loss',
           'l2': 'L2 regularisation is built for the single-GPU full-batch fit and the generic loop only',
           'resample': 'the negative table is resampled in the single-GPU full-batch fit and the generic loop only',
-          'als': 'only the single-GPU full-batch fit is built, and its regulariser is reg'}   # how a refusal ends, per feature
+          'als': 'only the single-GPU full-batch fit is built, and its regulariser is reg',
+          'item_bias': 'the scalar item bias is built for the single-GPU full-batch fit on float32 tables and the generic loop only'}
+#                                                                                      how a refusal ends, per feature
+# scalar_item_bias = True, a table of its own beside ROUTES (DESIGN.md prints both; _route reads both): the settings the bias is
+# refused with whatever the trainer, and the families of _engine.LOSSES whose engine epoch has the two bias passes.  A loss that is
+# no engine loss (a subclass, a plug-in) trains its bias in the generic loop
+ITEM_BIAS_ROUTES = {'item_bias': dict(zip(_SETTINGS, 'ok refuse refuse refuse refuse refuse ok ok'.split(), strict=True))}
+ITEM_BIAS_FAMILIES = {'table': 'ok', 'list': 'refuse', 'catalog': 'refuse'}
+
+
+def augmented_tables(user_embedding, item_embedding, item_bias):
+    """([U | 1], [V | b], fused): the tables whose product is U V^T + 1 b^T - the ONE place the ranking calls of a model with a scalar
+    item bias get their operands from (MatrixFactorization._score_tables).  float32 [rows, r + 1] views of fresh tables whose rows are
+    padded to 16 bytes; the column of ones and b are exact in every arithmetic of the fused kernels (1.0 is its own first bf16 plane,
+    b splits into its three planes like any factor).  fused: whether the width r + 1 still fits the fused ranking kernels (r + 1 <=
+    _ops.FUSED_MAX_R); a wider model ranks through predict_gemm + topk_stable and the block form of item_ranks."""
+    (m, r), n = user_embedding.shape, item_embedding.shape[0]
+    ld, dev = (r + 1 + 3) // 4 * 4, user_embedding.device
+    Ua = torch.zeros(m, ld, dtype=torch.float32, device=dev)
+    Va = torch.zeros(n, ld, dtype=torch.float32, device=dev)
+    Ua[:, :r], Va[:, :r] = user_embedding.detach(), item_embedding.detach()
+    Ua[:, r] = 1.0
+    Va[:, r] = item_bias.detach().to(dev)
+    return Ua[:, :r + 1], Va[:, :r + 1], r + 1 <= _ops.FUSED_MAX_R
 
 
 class SampleTableMissing(AttributeError):
@@ -166,6 +189,12 @@ class MatrixFactorization:
         self.sample_seed = 0
         self.resample_rounds_ = 0     # tables the last fit trained on, round 0's included (0: its loss reads no table)
         self.resample_seconds_ = 0.0  # time the last fit spent drawing tables and rebuilding their plans (part of fit_seconds_)
+        # extension, OFF by default (the reference's score is U[u] . V[i]): True = one trainable scalar per item beside its factor
+        # (LightFM's item_biases), score U[u] . V[i] + item_bias_[i] in the loss and in every ranking call.  Starts from zeros at
+        # every fit, takes the optimiser's step like any other variable and is never penalised.  On the engine for the table family
+        # (_engine.ItemScalarBias), else in the generic loop; what it is refused with: ITEM_BIAS_ROUTES / ITEM_BIAS_FAMILIES
+        self.scalar_item_bias = False
+        self.item_bias_ = None        # the trained bias of the last fit: float32 [n_items] on the tables' device (None: it had none)
 
     # ------------------------------------------------------------------------------------------
     # training
@@ -174,13 +203,14 @@ class MatrixFactorization:
         return bool(self.data_parallel and torch.distributed.is_available() and torch.distributed.is_initialized()
                     and torch.distributed.get_world_size() > 1 or (self.data_parallel == 'force'))
 
-    def _answer(self, feature, what=None, also=()):
+    def _answer(self, feature, what=None, also=(), table=ROUTES):
         """'engine', or 'generic' / NotImplementedError for the first setting, in ROUTES' column order, that this model has left the
-        default of and ``feature`` has no engine form for.  what: a refusal's name for the feature; also: attributes refused when set."""
+        default of and ``feature`` has no engine form for.  what: a refusal's name for the feature; also: attributes refused when set;
+        table: the table ``feature`` is a row of."""
         def refuse(name):
             raise NotImplementedError(f'{what} with {name}={getattr(self, name)!r}: {_BUILT[feature]} (set {name} back to its default)')
         for setting, (name, left) in _SETTINGS.items():
-            answer = ROUTES[feature][setting]
+            answer = table[feature][setting]
             if answer != 'ok' and left(self):
                 return 'generic' if answer == 'generic' else refuse(name)
         for name in also:
@@ -198,6 +228,12 @@ class MatrixFactorization:
         loss, kinds = type(self.loss_graph), (type(self.user_repr_graph), type(self.item_repr_graph))
         rec = next((rec for rec in _engine.LOSSES.values() if rec.cls is loss), None)   # a class's records share route and family
         row = rec.route if rec else None
+        if self._item_bias_setting():   # the setting's own refusals (ITEM_BIAS_ROUTES, ITEM_BIAS_FAMILIES), whatever the trainer
+            self._answer('item_bias', 'scalar_item_bias=True', table=ITEM_BIAS_ROUTES)
+            if rec is not None and ITEM_BIAS_FAMILIES[rec.family] != 'ok':
+                raise NotImplementedError(f'scalar_item_bias=True with {loss.__name__}: the engine adds the bias to the scores of the '
+                                          f'table family only ({", ".join(c.__name__ for c in TABLE_LOSSES)}); the passes of the other '
+                                          f'engine losses form their scores inside the kernels (set scalar_item_bias back to its default)')
         # the refusals, in the order a model that meets several has always met them
         answers = [self._answer('pair', loss.__name__)] if row == 'pair' else []
         if any(self._alphas()):
@@ -251,6 +287,13 @@ class MatrixFactorization:
             out.append(a)
         return tuple(out)
 
+    def _item_bias_setting(self):
+        """scalar_item_bias as a bool (False on a model that never had the attribute); anything but a bool raises ValueError."""
+        v = getattr(self, 'scalar_item_bias', False)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f'scalar_item_bias={v!r}: True or False')
+        return bool(v)
+
     def _resample_setting(self):
         """(resample_every, sample_seed) as ints, checked (ValueError: negative or not an integer) - resample_every as 0 for a loss that
         reads no negative table.  The forms that cannot resample are refused by _route (ROUTES['resample'])."""
@@ -285,6 +328,7 @@ class MatrixFactorization:
         step), then stores user_embedding / item_embedding / *_trainable.  Returns None."""
         route = self._route(user_features, item_features)   # and the refusals: before any weight is drawn or plan built
         self.resample_rounds_, self.resample_seconds_, self.graph_epochs_ = 0, 0.0, 0
+        self.item_bias_ = None   # a fit with scalar_item_bias leaves its bias here; every fit starts it from zeros
         n_users, n_user_features = user_features.shape
         n_items, n_item_features = item_features.shape
         if not isinstance(self.user_repr_graph, ReLUEmbedding):
@@ -358,6 +402,7 @@ class MatrixFactorization:
             raise ValueError(f'interactions of shape {tuple(interactions.shape)} for {n_users} users and {n_items} items')
         U, V = _als.fit(self, int(epochs), n_users, n_items, interactions, U0, V0, reg, alpha, bool(implicit), solver, cg_steps)
         self._reset_fit_products((False, False))
+        self.item_bias_ = None              # ALS has no item term
         self.__dict__.pop('_state', None)   # an earlier engine fit's TrainState: its tables are not this model's any more
         self.user_embedding, self.item_embedding = U, V
         self.user_trainable, self.item_trainable = [U], [V]
@@ -450,9 +495,10 @@ class MatrixFactorization:
         if rec.global_moments and (plan.n_pos == 0 or int((plan.val_u <= 0).sum()) == 0):
             return None, 0.0
         wplan = None
+        biased = self._item_bias_setting()   # _route let it pass: a table loss.  WMRB then takes the sliced plan as the pair losses do
         if rec.table:
             R = _engine.checked_negatives(self.random_ind, n_users, n_items, dev)
-            wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype, force_sliced=rec.sliced_only)
+            wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype, force_sliced=rec.sliced_only or biased)
             rec.prepare(wplan, plan)   # before any epoch runs or is captured
         r = self.n_components
         # a biased side starts from the bias an earlier fit left on the model, as in the reference (:139-146), else from zeros
@@ -472,7 +518,8 @@ class MatrixFactorization:
                 feat[side] = None
         st = _engine.TrainState(U0, V0, plan, r, wplan, dtype=self.factor_dtype, user_bias=bias0[0], item_bias=bias0[1],
                                 user_feat=feat[0], item_feat=feat[1], user_relu=relu0[0], item_relu=relu0[1],
-                                **({rec.flag: True} if rec.flag else {}))
+                                **({rec.flag: True} if rec.flag else {}),
+                                **({'item_scalar_bias': torch.zeros(n_items, device=dev)} if biased else {}))
         alphas = self._alphas()
         if any(alphas):   # never called with zeros: an unpenalised fit is today's state, launch for launch
             st.set_l2(*alphas)
@@ -492,17 +539,22 @@ class MatrixFactorization:
         gU, gV = (torch.empty_like(W) if side is None else side.G for W, side in zip((st.U, st.V), st.sides))
         sides = [(W, G, torch.zeros_like(W), torch.zeros_like(W), l2)
                  for W, G, l2 in ((st.U, gU, st.l2[0]), (st.V, gV, st.l2[1]))]   # table, gradient, m, v, l2 = 2 alpha
+        if st.ib is not None:   # the scalar item bias, moments of its own, never penalised: the vector as a [rows, 4] table
+            st.ib.epi = _lib.EPI_GRAD   # its second buffer receives the raw gradient; b is stepped in place below
+            b4, g4 = st.ib.b.view(-1, 4), st.ib.b_nxt.view(-1, 4)
+            sides.append((b4, g4, torch.zeros_like(b4), torch.zeros_like(b4), 0.0))
 
         def persistent(epoch, out):   # raw gradients of both sides from the pre-update tables, then one Adam step with state, in place
             a = lib.tmf_adam_step(float(lr), epoch + 1)
             _engine.run_epoch(st, a, out, loss, c, _lib.EPI_GRAD, gV, None, _lib.EPI_GRAD, gU)
             for W, G, M, V2, l2 in sides:
+                width = 4 if st.ib is not None and W is sides[-1][0] else self.n_components
                 if l2:   # the moments see g' = g + l2 w
                     _lib.check(lib.tmf_adam_state_rows_l2_f32(W, G, M, V2, W.shape[0],
                                                               self.n_components, a, l2, _lib.stream_ptr()), lib)
                     continue
                 _lib.check(lib.tmf_adam_state_rows_f32(W, G, M, V2, W.shape[0],
-                                                       self.n_components, a, _lib.stream_ptr()), lib)
+                                                       width, a, _lib.stream_ptr()), lib)
         return persistent
 
     def _run_epochs(self, step, epochs, G, denom, dev, t_plan, every=0, resample=None):
@@ -561,6 +613,7 @@ class MatrixFactorization:
         self._state = st
         self.user_embedding, self.item_embedding = st.U[:, :r], st.V[:, :r]
         self.user_trainable, self.item_trainable = [self.user_embedding], [self.item_embedding]
+        self.item_bias_ = None if st.ib is None else st.ib.value
         if st.bias_u is not None:
             self.user_linear_bias = st.bias_u.b[:r].clone().view(1, r).requires_grad_(True)
             self.user_trainable = [st.bias_u.W[:, :r], self.user_linear_bias]
@@ -599,6 +652,8 @@ class MatrixFactorization:
         every = self._resample_setting()[0]
         self.resample_rounds_ = int(isinstance(self.loss_graph, TABLE_LOSSES) and random_ind is not None)
         feeds = next((feeds for feeds, classes in _FEEDS.items() if isinstance(self.loss_graph, classes)), 'dense')   # Loss.feeds
+        # scalar_item_bias: one more leaf, from zeros, stepped with the other variables and never penalised
+        bias = torch.zeros(item_features.shape[0], dtype=torch.float32, device=dev, requires_grad=True) if self._item_bias_setting() else None
         for epoch in range(epochs):
             start = timeit.default_timer()
             if every and epoch and epoch % every == 0 and random_ind is not None:   # round epoch // every: its own table, random_ind stays
@@ -615,6 +670,8 @@ class MatrixFactorization:
                 linear_bias=self.item_linear_bias)
             self._keep_aux_variables()
             predictions = user_embedding @ item_embedding.T
+            if bias is not None:
+                predictions = predictions + bias[None, :]
             tf_sample_predictions = tf_prediction_serial = None
             if feeds == 'samples':
                 if random_ind is None:
@@ -626,7 +683,7 @@ class MatrixFactorization:
             loss_fn = self.loss_graph.get_loss(tf_interactions=interactions, tf_sample_predictions=tf_sample_predictions,
                                                tf_prediction_serial=tf_prediction_serial, predictions=predictions,
                                                n_items=self.n_items, n_samples=self.n_samples)
-            variables = self.user_trainable + self.item_trainable
+            variables = self.user_trainable + self.item_trainable + ([] if bias is None else [bias])
             objective = loss_fn.sum()
             for penalty, graph, trainable in ((user_alpha, self.user_repr_graph, self.user_trainable),
                                               (item_alpha, self.item_repr_graph, self.item_trainable)):
@@ -643,6 +700,8 @@ class MatrixFactorization:
             self.loss_history_.append(loss_one_epoch)
             self._report(epoch, loss_one_epoch, cumulative_time)
         self.fit_seconds_ = cumulative_time
+        if bias is not None:
+            self.item_bias_ = bias.detach()
         with torch.no_grad():
             self.user_embedding, self.user_trainable = self.user_repr_graph.get_repr(
                 features=user_features, weights=U, relu_weight=self.user_relu_weight, relu_bias=self.user_relu_bias,
@@ -707,7 +766,8 @@ class MatrixFactorization:
             raise NotImplementedError('item-row-sharded fit: this rank holds only its item rows, the dense [n_users, n_items] score '
                                       'matrix is not available; recall_at_k / precision_at_k / retrieve_user_recs rank over the '
                                       'windows (dist.sharded_top_items), dist.gather_item_embedding assembles the table where it fits')
-        all_predictions = _ops.predict_gemm(self.user_embedding, self.item_embedding)
+        U, V, _ = self._score_tables()
+        all_predictions = _ops.predict_gemm(U, V)
         if A is not None:
             A = torch.as_tensor(A).to(all_predictions.device)
             return all_predictions, all_predictions[A == 0]
@@ -717,6 +777,15 @@ class MatrixFactorization:
         """:203-216.  Global descending ranking of the flattened unobserved predictions."""
         _, unobserved = self.predict(A)
         return torch.sort(unobserved, descending=True, stable=True)[1]
+
+    def _score_tables(self):
+        """(U, V, fused) every score and ranking of this model is formed from: the embeddings, or with a trained scalar item bias
+        (item_bias_) the augmented tables [U | 1], [V | b] (augmented_tables), whose product is U V^T + b.  fused: the width fits the
+        fused ranking kernels (always, without a bias: the calls decide by the width as before)."""
+        b = getattr(self, 'item_bias_', None)
+        if b is None:
+            return self.user_embedding, self.item_embedding, True
+        return augmented_tables(self.user_embedding, self.item_embedding, b)
 
     def _user_blocks(self):
         m, n = self.user_embedding.shape[0], self.item_embedding.shape[0]
@@ -744,14 +813,16 @@ class MatrixFactorization:
             top = tdist.sharded_top_items(self, k, clamp, users=users, exclude=ex)
             return top[0] if users is not None else top
 
+        U, V, fused = self._score_tables()   # with a scalar item bias [U | 1], [V | b]
+
         def ranked(b, e):   # users [b, e) through their block of scores; the exclusion is written into the block
-            scores = _ops.predict_gemm(self.user_embedding[b:e], self.item_embedding)
+            scores = _ops.predict_gemm(U[b:e], V)
             return _ops.topk_stable(scores, k, clamp_negatives=clamp, exclude=None if ex is None else ex.shifted(b), overwrite=True)
 
         if users is not None:
             return ranked(users, users + 1)[0]
-        if _ops.fused_topk_supported(self.user_embedding, self.item_embedding, k):
-            return _ops.predict_topk(self.user_embedding, self.item_embedding, k, clamp_negatives=clamp,
+        if fused and _ops.fused_topk_supported(U, V, k):
+            return _ops.predict_topk(U, V, k, clamp_negatives=clamp,
                                      arithmetic=getattr(self, 'predict_arithmetic', None), exclude=ex)
         out = [ranked(b, e) for b, e in self._user_blocks()]
         return torch.cat(out) if len(out) > 1 else out[0]
@@ -897,8 +968,11 @@ class MatrixFactorization:
             raise NotImplementedError('item-row-sharded fit: this rank holds only its item rows; full-catalog ranks need every '
                                       'window (dist.gather_item_embedding assembles the table where it fits)')
         ex = None if exclude is None else self._exclusion(exclude)
-        rowptr, cols, ranks = _ops.item_ranks(self.user_embedding, self.item_embedding, A, exclude=ex,
-                                              arithmetic=getattr(self, 'predict_arithmetic', None), return_pairs=True)
+        U, V, fused = self._score_tables()
+        arithmetic = getattr(self, 'predict_arithmetic', None)
+        if not fused and arithmetic == 'split':   # a bias made the width 257: the block form, which 'auto' and 'fp32' take by themselves
+            arithmetic = 'fp32'
+        rowptr, cols, ranks = _ops.item_ranks(U, V, A, exclude=ex, arithmetic=arithmetic, return_pairs=True)
         return rowptr, cols, ranks, ex
 
     def item_ranks(self, A, *, exclude=None):
@@ -1071,6 +1145,10 @@ def _save_to_disk(model, path, include_samples=True, allow_pickle=False):
             'resample_every': int(getattr(model, 'resample_every', 0)), 'sample_seed': int(getattr(model, 'sample_seed', 0)),
             'loss_history': [float(x) for x in (getattr(model, 'loss_history_', []) or [])],
             'random_ind': (torch.as_tensor(model.random_ind).cpu() if include_samples and model.random_ind is not None else None)}
+    if model._item_bias_setting():   # only then: a model without the setting writes the file it always wrote
+        bias = getattr(model, 'item_bias_', None)
+        blob['scalar_item_bias'] = True
+        blob['item_bias'] = None if bias is None else bias.detach().float().cpu()
     torch.save(blob, path)
 
 
@@ -1097,6 +1175,9 @@ def _load_from_disk(cls, path, device=None, allow_pickle=False):
         setattr(model, name, None if t is None else t.to(device=dev, dtype=dt))
     model.user_trainable = [model.user_embedding] if model.user_embedding is not None else None
     model.item_trainable = [model.item_embedding] if model.item_embedding is not None else None
+    model.scalar_item_bias = bool(blob.get('scalar_item_bias', False))
+    bias = blob.get('item_bias')
+    model.item_bias_ = None if bias is None else bias.to(device=dev, dtype=torch.float32)
     model.loss_history_ = blob['loss_history']
     if blob['random_ind'] is not None:
         model.random_ind = blob['random_ind'].to(dev)
