@@ -4,12 +4,14 @@ import numpy as np
 import torch
 
 
-def biased_reference(loss_graph, U, V, b, idx, val, R, n_items, n_samples, feeds='samples'):
+def biased_reference(loss_graph, U, V, b, idx, val, R, n_items, n_samples, feeds='samples', dtype=torch.float64):
     """One epoch's loss and gradients at (U, V, b) in float64.  idx: row-major (user, item) pairs, val their stored values, R [m, S]
     the negative table in the model's order (None for a loss that reads none).  feeds: what get_loss is handed ('samples': sample and
-    serial predictions, 'dense': the [m, n] matrix).  -> dict(loss_sum, n_terms, gU, gV, gb, scores) of NumPy float64."""
+    serial predictions, 'dense': the [m, n] matrix).  dtype: torch.float32 runs the same computation in fp32 - the error of that run
+    against the float64 one is what fp32 arithmetic costs this loss (tests/test_fuzz_draws_cpu.py derives a tolerance from it).
+    -> dict(loss_sum, n_terms, gU, gV, gb, scores) of NumPy float64."""
     from teamoflow_amd.mf.sparse import SparseInteractions
-    U, V, b = (torch.tensor(np.asarray(x, np.float64), dtype=torch.float64, requires_grad=True) for x in (U, V, b))
+    U, V, b = (torch.tensor(np.asarray(x, np.float64), dtype=dtype, requires_grad=True) for x in (U, V, b))
     idx = torch.as_tensor(np.asarray(idx, np.int64))
     inter = SparseInteractions(idx, torch.as_tensor(np.asarray(val, np.float32)), (U.shape[0], V.shape[0]), device='cpu')
     predictions = U @ V.T + b[None, :]
@@ -20,10 +22,10 @@ def biased_reference(loss_graph, U, V, b, idx, val, R, n_items, n_samples, feeds
     loss = loss_graph.get_loss(tf_interactions=inter, tf_sample_predictions=samples, tf_prediction_serial=serial,
                                predictions=predictions if feeds == 'dense' else None, n_items=n_items, n_samples=n_samples)
     gU, gV, gb = torch.autograd.grad(loss.sum(), (U, V, b), allow_unused=True)
-    out = dict(loss_sum=float(loss.detach().sum()), n_terms=int(loss.numel()), scores=predictions.detach().numpy())
+    out = dict(loss_sum=float(loss.detach().double().sum()), n_terms=int(loss.numel()), scores=predictions.detach().double().numpy())
     for name, g, like in (('gU', gU, U), ('gV', gV, V), ('gb', gb, b)):
         g = torch.zeros_like(like) if g is None else g
-        out[name] = g.detach().numpy().copy()
+        out[name] = g.detach().double().numpy().copy()
         out[name].setflags(write=False)
     return out
 

@@ -101,6 +101,27 @@ def test_add_is_one_add_per_score(tm, m, S, n, pad):
         assert torch.equal(~torch.isfinite(got_sp), R == n // 2) and torch.equal(~torch.isfinite(got_pk), col == n // 2)
 
 
+IB_ADD_BLOCKS, IB_THREADS = 16384, 256   # kIbAddBlocks and kIbThreads of csrc/tmf_itembias.hip: one pass of the add's grid-stride loops
+
+
+@pytest.mark.parametrize('pad', [4, 1], ids=['aligned', 'unaligned'])
+def test_add_past_one_pass_of_the_grid(tm, pad):
+    """4100 x 4100 scores and 16384 * 256 + 300 interactions: every grid-stride loop of the kernel takes a second trip (the float4
+    pieces and the interactions one pass and a bit, the scalar form of the unaligned table more than four)."""
+    m = S = 4100
+    n, nnz, one_pass = 1000, IB_ADD_BLOCKS * IB_THREADS + 300, IB_ADD_BLOCKS * IB_THREADS
+    assert m * S // 4 > one_pass and m * S > 4 * one_pass and nnz > one_pass
+    g = torch.Generator(device='cuda').manual_seed(4100 + pad)
+    b = torch.randn(n, generator=g, device='cuda')
+    R = torch.randint(0, n, (m, S), generator=g, dtype=torch.int32, device='cuda')
+    sp = torch.randn(m, S, generator=g, device='cuda')
+    col = torch.randint(0, n, (nnz,), generator=g, dtype=torch.int32, device='cuda')
+    pk = torch.randn(nnz, generator=g, device='cuda')
+    want_sp, want_pk = sp + b[R.long()], pk + b[col.long()]
+    got_sp, got_pk = run_add(tm, b, R, sp, col, pk, pad)
+    assert torch.equal(bits(got_sp), bits(want_sp)) and torch.equal(bits(got_pk), bits(want_pk))
+
+
 def test_add_on_tables_without_users_samples_or_entries(tm):
     b = torch.randn(5).cuda()
     empty_i, empty_f = torch.zeros(0, dtype=torch.int32).cuda(), torch.zeros(0).cuda()
@@ -201,6 +222,104 @@ def test_grad_on_hand_built_lists(tm, C):
     torch.cuda.synchronize()
     assert torch.equal(bits(stepped), bits(W[:n])) and torch.equal(bits(stepped[:1]), bits(b_old[:1]))
     assert not torch.equal(stepped[1:], b_old[1:])
+
+
+# list-row lengths around every border of k_item_bias_partial: the lanes of a wave (64), the first trip of the unrolled loop (a chunk
+# of more than 3 * 64 = 192 entries) and its later trips (256, 448), the chunk lengths 256 and 1024 and their multiples
+LENS = (0, 1, 63, 64, 65, 192, 193, 255, 256, 257, 448, 449, 1023, 1024, 1025, 2047, 2048, 2049, 3 * 1024 + 200)
+CANCELLING = np.array([3.0e6, -3.0e6, 1.5e-3, 7.25e5, -7.25e5, -1.0e-3], np.float32)   # hand_lists' item 2
+
+
+def border_lists(C):
+    """One item per length of LENS; block c gives item i the length LENS[(i + c) % len(LENS)].  ent_w a permutation, weights N(0, 1)
+    but for item 10 (448 entries in block 0: two trips of the unrolled loop and a tail), whose entries repeat CANCELLING and
+    end in terms of 1e-3; the row behind the lists NaN.  -> rowptr, ent_w, wbuf, lens [C, n], G, A (fp64 sums per item)."""
+    n = len(LENS)
+    rng = np.random.default_rng(700 + C)
+    lens = np.array([[LENS[(i + c) % n] for i in range(n)] for c in range(C)], np.int64)
+    rowptr = np.concatenate([[0], np.cumsum(lens.reshape(-1))]).astype(np.int64)
+    E_lists, tail = int(rowptr[-1]), 5
+    E = E_lists + tail
+    ent_w = rng.permutation(E).astype(np.int32)
+    wbuf = rng.standard_normal(E).astype(np.float32)
+    wbuf[ent_w[E_lists:]] = np.nan
+    for c in range(C):
+        row = c * n + 10
+        k = int(lens[c, 10])
+        w = np.tile(CANCELLING, k // 6 + 1)[:k]
+        w[k - k % 6:] = (1e-3 * rng.standard_normal(k % 6)).astype(np.float32)
+        wbuf[ent_w[rowptr[row]:rowptr[row + 1]]] = w
+    G, A = np.zeros(n), np.zeros(n)
+    for row in range(C * n):
+        w = wbuf[ent_w[rowptr[row]:rowptr[row + 1]]].astype(np.float64)
+        G[row % n] += w.sum()
+        A[row % n] += np.abs(w).sum()
+    return rowptr, ent_w, wbuf, lens, G, A
+
+
+def grad_in_kernel_order(rowptr, ent_w, wbuf, n, C, chunk):
+    """tmf_item_bias_grad restated in NumPy in the order its header promises: lane l of a chunk's wave adds the entries l, l + 64, ..
+    in ascending order in fp64 from 0.0; the butterfly acc += acc[lane ^ off], off = 32 .. 1; an item adds chunk 0 of its blocks
+    0 .. C - 1, then its further chunks in (block, chunk) order; one rounding to fp32."""
+    lanes = np.arange(64)
+
+    def chunk_sum(row, c):
+        beg = rowptr[row] + c * chunk
+        w = wbuf[ent_w[beg:min(beg + chunk, rowptr[row + 1])]].astype(np.float64)
+        acc = np.zeros(64)
+        for j in range(0, w.size, 64):
+            acc[:w[j:j + 64].size] += w[j:j + 64]
+        for off in (32, 16, 8, 4, 2, 1):
+            acc = acc + acc[lanes ^ off]
+        return acc[0]
+    out = np.zeros(n, np.float32)
+    for i in range(n):
+        acc = 0.0
+        for blk in range(C):
+            acc += chunk_sum(blk * n + i, 0)
+        for blk in range(C):
+            row = blk * n + i
+            for c in range(1, -(-int(rowptr[row + 1] - rowptr[row]) // chunk)):
+                acc += chunk_sum(row, c)
+        out[i] = np.float32(acc)
+    return out
+
+
+@pytest.mark.parametrize('chunk', [256, 1024])
+@pytest.mark.parametrize('C', [1, 3])
+def test_grad_at_the_borders_of_its_loops(tm, C, chunk):
+    """Every trip count of the unrolled loop and of its tail, chunks that end on and beside a border, further chunks at the length the
+    engine uses.  Against the fp64 sum within the file's bound (a lost or repeated N(0, 1) entry misses it by about 1) and, bit for
+    bit, against the order of additions the kernel's header states: fp64 additions in a fixed order, no fast-math."""
+    n = len(LENS)
+    rowptr, ent_w, wbuf, lens, G, A = border_lists(C)
+    d_rowptr, d_ent, d_w = dev(rowptr, torch.int64), dev(ent_w, torch.int32), dev(wbuf, torch.float32)
+    g, n_extra = run_grad(tm, d_rowptr, n, C, d_ent, d_w, chunk, tm.L.EPI_GRAD)
+    assert n_extra == int(np.maximum(-(-lens // chunk) - 1, 0).sum()) and n_extra > 0
+    assert int(lens.max()) > 3 * chunk and (lens > 192).any(axis=0).sum() >= n - 6      # further chunks; most items enter the unrolled loop
+    got = host(g).astype(np.float64)
+    assert np.isfinite(got).all() and abs(G[10]) < 1.0 and A[10] > 1e8
+    if C == 1:
+        assert got[0] == 0.0
+    miss = np.abs(got - G) - (ulp32(G) + 1e-12 * A)
+    print(f'[item bias] borders C={C} chunk={chunk}: n_extra {n_extra}, worst |got - G| - bound {miss.max():.3g}')
+    assert (miss <= 0).all(), (got, G)
+    want = grad_in_kernel_order(rowptr, ent_w, wbuf, n, C, chunk)
+    assert np.array_equal(host(g).view(np.int32), want.view(np.int32)), (host(g), want)
+    for other in (run_grad(tm, d_rowptr, n, C, d_ent, d_w, chunk, tm.L.EPI_GRAD)[0],                               # twice
+                  run_grad(tm, d_rowptr, n, C, d_ent, d_w, chunk, tm.L.EPI_GRAD, stream=torch.cuda.Stream())[0]):  # a stream of its own
+        assert torch.equal(bits(other), bits(g))
+    # TMF_EPI_ADAM = tmf_adam_fresh_rows_f32 on the TMF_EPI_GRAD output, bit for bit
+    b_old = torch.randn(n, generator=torch.Generator().manual_seed(C)).cuda()
+    stepped, _ = run_grad(tm, d_rowptr, n, C, d_ent, d_w, chunk, tm.L.EPI_ADAM, b_old=b_old)
+    rows = -(-n // 4)
+    W, Gp = torch.zeros(4 * rows, device='cuda'), torch.zeros(4 * rows, device='cuda')
+    W[:n], Gp[:n] = b_old, g
+    tm.L.check(tm.lib.tmf_adam_fresh_rows_f32(W, Gp, rows, 4, tm.E.adam_constants(LR), tm.L.stream_ptr()), tm.lib)
+    torch.cuda.synchronize()
+    assert torch.equal(bits(stepped), bits(W[:n])) and not torch.equal(stepped[1:], b_old[1:])
+    if C == 1:
+        assert torch.equal(bits(stepped[:1]), bits(b_old[:1]))                          # an item without entries keeps its bias
 
 
 def test_grad_on_the_lists_of_a_real_plan(tm):
@@ -573,14 +692,27 @@ def test_rankings_are_those_of_the_dense_scores(tm, ranked, arithmetic):
 
 
 def test_a_model_of_256_components_ranks_through_the_general_path(tm):
+    rank_a_wide_model(tm, 256, fused=False)
+
+
+@pytest.mark.parametrize('r', [127, 128, 255])
+def test_models_up_to_the_widest_fused_tables_rank_with_a_bias(tm, r):
+    """[U | 1], [V | b] of 128, 129 and 256 columns: the last width of the 128-column kernels, the first past it, and the widest the
+    fused ranking kernels take (_ops.FUSED_MAX_R)."""
+    assert r + 1 <= tm.ops.FUSED_MAX_R == 256
+    rank_a_wide_model(tm, r, fused=True)
+
+
+def rank_a_wide_model(tm, r, fused):
     g = torch.Generator().manual_seed(3)
-    model = tm.MF(256, n_users=40, n_items=90)
-    model.user_embedding = (torch.randn(40, 256, generator=g) * 0.1).cuda()
-    model.item_embedding = (torch.randn(90, 256, generator=g) * 0.1).cuda()
+    model = tm.MF(r, n_users=40, n_items=90)
+    model.user_embedding = (torch.randn(40, r, generator=g) * 0.1).cuda()
+    model.item_embedding = (torch.randn(90, r, generator=g) * 0.1).cuda()
     model.item_embedding[11] = model.item_embedding[4]
     model.item_bias_ = torch.randn(90, generator=g).cuda()
     model.item_bias_[11] = model.item_bias_[4]
-    assert model._score_tables()[2] is False
+    Ua, Va, says = model._score_tables()
+    assert says is fused and Ua.shape == (40, r + 1) and Va.shape == (90, r + 1)
     P = model.predict()
     want = host(model.user_embedding).astype(np.float64) @ host(model.item_embedding).astype(np.float64).T + host(model.item_bias_)[None, :]
     assert rel_err(host(P), want) < 1e-6
