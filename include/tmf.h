@@ -862,6 +862,27 @@ int tmf_sample_rows_supported(int32_t n_items, int32_t n_samples);
 int tmf_sample_rows(int32_t n_items, int64_t n_users, int32_t n_samples, int64_t seed, int64_t user_offset, int32_t* R,
                     int32_t* failed, void* stream);
 
+/* EXTENSION (the reference's table is uniform): the table of tmf_sample_rows with every draw WEIGHTED - item i with probability
+ * q_i / T - for popularity-weighted negatives (csrc/tmf_sample_weighted.hip).  TMF_VERSION stays 203: nothing that existed changes.
+ *
+ * cum: int64 [n_items], device memory, the inclusive prefix sum of integer weights q_i >= 0; T = cum[n_items - 1], 1 <= T < 2^33.
+ * R[i, :] (int32 [n_users, n_samples], row-major, every element written and nothing else) = n_samples DISTINCT items of non-zero
+ * weight in random order for user u = user_offset + i: a function of (seed, u, q) alone.  It is exactly the table
+ * teamoflow_amd/mf/utils.py random_sampler_device(weights=q) draws, which is the definition - tmf_sample_rows's program with
+ *   below(h) replaced by item(h) = the first i with cum[i] > (h >> 11) mod T   (an item of weight 0 is never drawn),
+ *   and redraw rounds rnd = 3 .. 258.
+ * A row that still holds a repeat when round 259 begins stores a non-zero value to *failed (int32, device memory, zeroed by the
+ * caller; a plain store, no atomic).  The CALLER admits the weights: with H the sum of the n_samples largest q_i, 4 H <= 3 T - then a
+ * redraw leaves the items of the row with probability >= 1/4, and the flag is set with probability <= 0.75^256 per place.  The
+ * call does not check the rule, nor that cum ascends: whatever cum holds, every id written lies in [0, n_items) and the call ends.
+ * tmf_sample_rows_weighted_supported: 1 <= n_samples <= 4096 (the row is sorted in LDS) and n_items >= 1; the call returns
+ * TMF_E_INVALID before any launch otherwise, for n_users < 0, user_offset < 0, a null pointer, or cum[n_items - 1] outside
+ * [1, 2^33) - the host reads that one word in stream order and waits for it (so the call cannot be captured into a graph) and hands
+ * it to the kernel, which does not read it again.  n_users == 0: TMF_OK, no launch and nothing read. */
+int tmf_sample_rows_weighted_supported(int32_t n_items, int32_t n_samples);
+int tmf_sample_rows_weighted(const int64_t* cum, int32_t n_items, int64_t n_users, int32_t n_samples, int64_t seed,
+                             int64_t user_offset, int32_t* R, int32_t* failed, void* stream);
+
 /* EXTENSION (the reference has no softmax): the softmax of a positive against the WHOLE catalog - FullSoftmaxLoss - without the
  * [m, n] score matrix (csrc/tmf_fullsoftmax.hip).  TMF_VERSION stays 203: nothing that existed changes.
  * All three take fp32 tables of 1 <= n_components <= tmf_fsm_max_components (128) - any value, not only multiples of 4 - on

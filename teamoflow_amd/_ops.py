@@ -922,12 +922,18 @@ def pair_scores(A, B, pair_a, pair_b):
     return out
 
 
-def sample_negatives(n_items, n_users, n_samples, seed=0, device=None, user_offset=0, out=None):
+def sample_negatives(n_items, n_users, n_samples, seed=0, device=None, user_offset=0, out=None, weights=None):
     """int32 [n_users, n_samples]: rows user_offset .. user_offset + n_users of the negative table of ``seed`` - exactly the table
     mf.utils.random_sampler_device draws (its definition), by one launch of tmf_sample_rows where the kernel takes the shape
     (tmf_sample_rows_supported: 2 n_samples <= n_items, n_samples within its LDS bound) and the device is a GPU, and by the torch
     function otherwise (most of the catalog per row, longer rows, the CPU): the same bits either way.  out: a contiguous int32
-    [n_users, n_samples] tensor on the device to draw into."""
+    [n_users, n_samples] tensor on the device to draw into.
+    weights (int64 [n_items], None = uniform): the weighted table random_sampler_device(weights=...) defines - item i drawn with
+    probability weights[i] / sum(weights) (utils.popularity_weights makes them; utils.weighted_cum states what is admitted and
+    raises otherwise) - by tmf_sample_rows_weighted where tmf_sample_rows_weighted_supported holds on a GPU, else by the torch
+    function: the same bits either way."""
+    if weights is not None:
+        return _sample_negatives_weighted(n_items, n_users, n_samples, seed, device, user_offset, out, weights)
     from .mf.sparse import default_device
     from .mf.utils import random_sampler_device
     n_items, n_users, n_samples, seed, user_offset = int(n_items), int(n_users), int(n_samples), int(seed), int(user_offset)
@@ -953,6 +959,39 @@ def sample_negatives(n_items, n_users, n_samples, seed=0, device=None, user_offs
         R = torch.empty(n_users, n_samples, dtype=torch.int32, device=device) if out is None else out
         failed = torch.zeros(1, dtype=torch.int32, device=R.device)
         _lib.check(lib.tmf_sample_rows(n_items, n_users, n_samples, seed, user_offset, R, failed, _lib.stream_ptr()),
+                   lib)
+        if n_users and int(failed):
+            raise RuntimeError('could not draw distinct samples')
+    return R
+
+
+def _sample_negatives_weighted(n_items, n_users, n_samples, seed, device, user_offset, out, weights):
+    """sample_negatives(weights=...)."""
+    from .mf.sparse import default_device
+    from .mf.utils import random_sampler_device, weighted_cum
+    n_items, n_users, n_samples, seed, user_offset = int(n_items), int(n_users), int(n_samples), int(seed), int(user_offset)
+    device = default_device() if device is None else torch.device(device)
+    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.int32 and tuple(out.shape) == (n_users, n_samples)
+                                and out.is_contiguous() and out.device.type == device.type):
+        raise ValueError(f'out must be a contiguous int32 [{n_users}, {n_samples}] tensor on {device}')
+    if n_users < 0 or user_offset < 0:
+        raise ValueError(f'n_users={n_users}, user_offset={user_offset}: negative')
+    cum = weighted_cum(weights, n_items, n_samples)   # length, sign, dtype, total and the admission rule: before anything is drawn
+    native = device.type == 'cuda' and n_items < 2 ** 31 and 0 < n_samples < 2 ** 31 and \
+        _lib.load_library().tmf_sample_rows_weighted_supported(n_items, n_samples)
+    if not native:
+        R = random_sampler_device(n_items, n_users, n_samples, seed=seed, device=device, user_offset=user_offset, weights=weights)
+        if out is None:
+            return R
+        out.copy_(R)
+        return out
+    lib = _lib.get()
+    seed = (seed + 2 ** 63) % 2 ** 64 - 2 ** 63   # the low 64 bits, as the torch function's wrapping arithmetic sees the seed
+    with torch.cuda.device(out.device if out is not None else device):
+        R = torch.empty(n_users, n_samples, dtype=torch.int32, device=device) if out is None else out
+        cum = cum.to(R.device)
+        failed = torch.zeros(1, dtype=torch.int32, device=R.device)
+        _lib.check(lib.tmf_sample_rows_weighted(cum, n_items, n_users, n_samples, seed, user_offset, R, failed, _lib.stream_ptr()),
                    lib)
         if n_users and int(failed):
             raise RuntimeError('could not draw distinct samples')

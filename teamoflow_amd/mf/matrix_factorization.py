@@ -27,7 +27,7 @@ from .embedding_graphs import BiasedLinearEmbedding, Embeddings, LinearEmbedding
 from .initializer_graphs import NormalInitializer
 from .loss_graphs import LossGraph, MSELoss  # noqa: F401  (what the engine knows of every other loss is _engine.LOSSES)
 from .sparse import IndicatorFeatures, SparseFeatures, SparseInteractions, default_device, is_indicator
-from .utils import gather_matrix_indices, random_sampler, random_sampler_device
+from .utils import gather_matrix_indices, popularity_weights, random_sampler, random_sampler_device
 
 PREDICT_CHUNK_BYTES = 2 << 30  # users are scored in blocks of at most this many bytes of scores
 HOST_SAMPLER_MAX_WORK = 2_000_000_000  # n_users * n_items above which generate_sample=True samples on the device
@@ -72,13 +72,18 @@ _BUILT = {'pair': 'only the single-GPU full-batch fit is built for this loss',
           'l2': 'L2 regularisation is built for the single-GPU full-batch fit and the generic loop only',
           'resample': 'the negative table is resampled in the single-GPU full-batch fit and the generic loop only',
           'als': 'only the single-GPU full-batch fit is built, and its regulariser is reg',
-          'item_bias': 'the scalar item bias is built for the single-GPU full-batch fit on float32 tables and the generic loop only'}
+          'item_bias': 'the scalar item bias is built for the single-GPU full-batch fit on float32 tables and the generic loop only',
+          'popularity': 'the negative table is drawn by popularity in the single-GPU full-batch fit and the generic loop only'}
 #                                                                                      how a refusal ends, per feature
 # scalar_item_bias = True, a table of its own beside ROUTES (DESIGN.md prints both; _route reads both): the settings the bias is
 # refused with whatever the trainer, and the families of _engine.LOSSES whose engine epoch has the two bias passes.  A loss that is
 # no engine loss (a subclass, a plug-in) trains its bias in the generic loop
 ITEM_BIAS_ROUTES = {'item_bias': dict(zip(_SETTINGS, 'ok refuse refuse refuse refuse refuse ok ok'.split(), strict=True))}
 ITEM_BIAS_FAMILIES = {'table': 'ok', 'list': 'refuse', 'catalog': 'refuse'}
+# negative_sampling = 'popularity' on a table loss, a table of its own like the bias's: the forms that draw their tables themselves
+# are where 'resample' is refused, and so is this.  With 'uniform' or without the attribute it is never looked at
+SAMPLING_ROUTES = {'popularity': dict(ROUTES['resample'])}
+NEGATIVE_SAMPLING = ('uniform', 'popularity')
 
 
 def augmented_tables(user_embedding, item_embedding, item_bias):
@@ -189,6 +194,14 @@ class MatrixFactorization:
         self.sample_seed = 0
         self.resample_rounds_ = 0     # tables the last fit trained on, round 0's included (0: its loss reads no table)
         self.resample_seconds_ = 0.0  # time the last fit spent drawing tables and rebuilding their plans (part of fit_seconds_)
+        # extension, OFF by default (the reference's table is uniform over the catalog): 'popularity' = a fit of one of the
+        # TABLE_LOSSES draws EVERY round's table, round 0's included, with item i weighted (c_i + 1)^sampling_power, c_i the number
+        # of training entries of item i with a value > 0 (word2vec's unigram^0.75; implicit's BPR): round j trains on
+        # _ops.sample_negatives(n_items, n_users, S, seed=sample_seed + j, weights=utils.popularity_weights(c, sampling_power)).
+        # random_ind is still required, gives S, and is never changed.  The losses read the table as they read a uniform one.
+        # Full-batch on one GPU, or the generic loop (SAMPLING_ROUTES); losses that read no table are not affected
+        self.negative_sampling = 'uniform'
+        self.sampling_power = 0.75
         # extension, OFF by default (the reference's score is U[u] . V[i]): True = one trainable scalar per item beside its factor
         # (LightFM's item_biases), score U[u] . V[i] + item_bias_[i] in the loss and in every ranking call.  Starts from zeros at
         # every fit, takes the optimiser's step like any other variable and is never penalised.  On the engine for the table family
@@ -220,7 +233,8 @@ class MatrixFactorization:
 
     def _route(self, user_features, item_features):
         """'engine' | 'generic': the trainer of this fit, after the refusals (NotImplementedError; ValueError for a bad user_alpha /
-        item_alpha / resample_every / sample_seed) - the one place that decides either, from ROUTES.  Nothing is drawn or built here.
+        item_alpha / resample_every / sample_seed / negative_sampling / sampling_power) - the one place that decides either, from
+        ROUTES.  Nothing is drawn or built here.
         The engine takes exactly the ENGINE_LOSSES over sides that are exactly LinearEmbedding / BiasedLinearEmbedding over indicator
         features or LinearEmbedding over SparseFeatures with entries (with relu_engine also exactly ReLUEmbedding over either, while
         its aux width 5 r fits a table row) when no feature of the fit answers 'generic'.  Unbiased MSE / WMRB have no row in ROUTES:
@@ -234,6 +248,8 @@ class MatrixFactorization:
                 raise NotImplementedError(f'scalar_item_bias=True with {loss.__name__}: the engine adds the bias to the scores of the '
                                           f'table family only ({", ".join(c.__name__ for c in TABLE_LOSSES)}); the passes of the other '
                                           f'engine losses form their scores inside the kernels (set scalar_item_bias back to its default)')
+        if self._sampling_setting()[0] == 'popularity':   # the setting's own refusals (SAMPLING_ROUTES); None for a loss without a table
+            self._answer('popularity', "negative_sampling='popularity'", table=SAMPLING_ROUTES)
         # the refusals, in the order a model that meets several has always met them
         answers = [self._answer('pair', loss.__name__)] if row == 'pair' else []
         if any(self._alphas()):
@@ -307,9 +323,36 @@ class MatrixFactorization:
             return 0, out[1]
         return tuple(out)
 
+    def _sampling_setting(self):
+        """(negative_sampling, sampling_power), checked (ValueError: a name that is not one of NEGATIVE_SAMPLING; under 'popularity' a
+        power that is not finite and >= 0) - ('uniform' on a model that never had the attribute) and (None, power) for a loss that
+        reads no negative table.  The forms that cannot draw by popularity are refused by _route (SAMPLING_ROUTES)."""
+        how, power = getattr(self, 'negative_sampling', 'uniform'), getattr(self, 'sampling_power', 0.75)
+        if not isinstance(how, str) or how not in NEGATIVE_SAMPLING:
+            raise ValueError(f"negative_sampling={how!r}: 'uniform' or 'popularity'")
+        if how == 'popularity':
+            if isinstance(power, bool) or not isinstance(power, (int, float, np.integer, np.floating)) \
+                    or not (np.isfinite(power) and power >= 0):
+                raise ValueError(f'sampling_power={power!r}: a finite number >= 0')
+            power = float(power)
+        return (how if isinstance(self.loss_graph, TABLE_LOSSES) else None), power
+
+    def _popularity_weights(self, interactions, n_items):
+        """The weights of this fit's tables under negative_sampling='popularity' (int64 [n_items], on the CPU), else None: c_i = the
+        stored entries of item i with a value > 0, q = utils.popularity_weights(c, sampling_power).  Once per fit."""
+        how, power = self._sampling_setting()
+        if how != 'popularity':
+            return None
+        items = interactions.indices[:, 1][interactions.values > 0].to(torch.int64)
+        return popularity_weights(torch.bincount(items, minlength=n_items).cpu(), power)
+
     def _draw_round(self, j, n_items, n_users, dev):
-        """The table of round j >= 1 (int32, on dev): a function of (sample_seed + j, shape) alone."""
+        """The table of round j (int32, on dev): a function of (sample_seed + j, shape) alone - under negative_sampling='popularity'
+        of the fit's weights too, and then for every j >= 0; else for j >= 1."""
         S = int(torch.as_tensor(self.random_ind).shape[1])
+        q = getattr(self, '_sampling_weights', None)
+        if q is not None:
+            return _ops.sample_negatives(n_items, n_users, S, seed=self._resample_setting()[1] + j, device=dev, weights=q)
         return _ops.sample_negatives(n_items, n_users, S, seed=self._resample_setting()[1] + j, device=dev)
 
     def _reset_fit_products(self, sparse_feature_sides):
@@ -321,6 +364,7 @@ class MatrixFactorization:
         self._sparse_feature_sides = tuple(sparse_feature_sides)
         self._feature_weights = [None, None]   # padded engine weights of a side trained over SparseFeatures (embed_users / embed_items)
         self._relu_sides = [None, None]        # the _engine.ReLUSide of a ReLU side trained on the engine (embed_users / embed_items)
+        self._sampling_weights = None          # the weights of a fit under negative_sampling='popularity' (fit sets them)
 
     def fit(self, epochs, user_features, item_features, tf_interactions, lr=1e-2):
         """matrix_factorization.py:96-187.  Re-initialises the weights on every call, runs ``epochs``
@@ -341,6 +385,7 @@ class MatrixFactorization:
             V = self.item_weight_graph.initialize_weights(self.item_aux_dim, self.n_components)
         interactions = _as_interactions(tf_interactions)
         self._reset_fit_products((isinstance(user_features, SparseFeatures), isinstance(item_features, SparseFeatures)))
+        self._sampling_weights = self._popularity_weights(interactions, n_items)
         if route == 'engine':
             feats = [f if sparse else None for f, sparse in zip((user_features, item_features), self._sparse_feature_sides)]
             if self._fit_sparse(epochs, n_users, n_items, interactions, lr, U, V, *feats):
@@ -498,6 +543,8 @@ class MatrixFactorization:
         biased = self._item_bias_setting()   # _route let it pass: a table loss.  WMRB then takes the sliced plan as the pair losses do
         if rec.table:
             R = _engine.checked_negatives(self.random_ind, n_users, n_items, dev)
+            if getattr(self, '_sampling_weights', None) is not None:   # round 0 is drawn too; random_ind gave the shape
+                R = self._draw_round(0, n_items, n_users, dev)
             wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype, force_sliced=rec.sliced_only or biased)
             rec.prepare(wplan, plan)   # before any epoch runs or is captured
         r = self.n_components
@@ -652,6 +699,8 @@ class MatrixFactorization:
         every = self._resample_setting()[0]
         self.resample_rounds_ = int(isinstance(self.loss_graph, TABLE_LOSSES) and random_ind is not None)
         feeds = next((feeds for feeds, classes in _FEEDS.items() if isinstance(self.loss_graph, classes)), 'dense')   # Loss.feeds
+        if random_ind is not None and getattr(self, '_sampling_weights', None) is not None:   # popularity: round 0 is drawn too
+            random_ind = self._draw_round(0, item_features.shape[0], user_features.shape[0], dev)
         # scalar_item_bias: one more leaf, from zeros, stepped with the other variables and never penalised
         bias = torch.zeros(item_features.shape[0], dtype=torch.float32, device=dev, requires_grad=True) if self._item_bias_setting() else None
         for epoch in range(epochs):
@@ -1145,6 +1194,9 @@ def _save_to_disk(model, path, include_samples=True, allow_pickle=False):
             'resample_every': int(getattr(model, 'resample_every', 0)), 'sample_seed': int(getattr(model, 'sample_seed', 0)),
             'loss_history': [float(x) for x in (getattr(model, 'loss_history_', []) or [])],
             'random_ind': (torch.as_tensor(model.random_ind).cpu() if include_samples and model.random_ind is not None else None)}
+    sampling = (getattr(model, 'negative_sampling', 'uniform'), getattr(model, 'sampling_power', 0.75))
+    if sampling != ('uniform', 0.75):   # only then, as below
+        blob['negative_sampling'], blob['sampling_power'] = str(sampling[0]), float(sampling[1])
     if model._item_bias_setting():   # only then: a model without the setting writes the file it always wrote
         bias = getattr(model, 'item_bias_', None)
         blob['scalar_item_bias'] = True
@@ -1175,6 +1227,7 @@ def _load_from_disk(cls, path, device=None, allow_pickle=False):
         setattr(model, name, None if t is None else t.to(device=dev, dtype=dt))
     model.user_trainable = [model.user_embedding] if model.user_embedding is not None else None
     model.item_trainable = [model.item_embedding] if model.item_embedding is not None else None
+    model.negative_sampling, model.sampling_power = blob.get('negative_sampling', 'uniform'), float(blob.get('sampling_power', 0.75))
     model.scalar_item_bias = bool(blob.get('scalar_item_bias', False))
     bias = blob.get('item_bias')
     model.item_bias_ = None if bias is None else bias.to(device=dev, dtype=torch.float32)
