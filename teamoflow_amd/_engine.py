@@ -7,6 +7,7 @@ matrix_factorization.py:130-176 with one loss of loss_graphs.py each - LOSSES, t
 every loss the engine trains is made of - and epoch_sides the same loop with plug-in sides: any of those losses, then the step of
 every side that is an object (TrainState.sides: PlainL2Side, BiasSide, FeatureSide, ReLUSide <- embedding_graphs.py:30-87).
 """
+import collections
 import ctypes
 import dataclasses
 import os
@@ -15,10 +16,50 @@ import torch
 
 from . import _lib
 
+# Every environment switch this file reads: name -> (meaning, whether it selects a kernel form: the tests clear those before they
+# set their own).  switch() below is the ONE reader and refuses a name that is not declared here; README's "Tunables" names them all.
+SWITCHES = {
+    'TMF_PART_BUDGET': ('bytes of gradU slice partials kept as one layer per slice (read once, at import)', False),
+    'TMF_SLAB_BUDGET': ('bytes of partial rows the WMRB item pass may use', False),
+    'TMF_USER_CHUNKS': ('user blocks of the item passes', True),
+    'TMF_ITEM_SLICES': ('item slices of the sliced WMRB user pass', True),
+    'TMF_SLICE_XCD': ('0 | 1: every XCD its own item slice', True),
+    'TMF_FORCE_SLICED': ('1: the sliced WMRB user pass whatever the shape', True),
+    'TMF_FORCE_FUSED': ('1: the one-kernel WMRB user pass where it fits', True),
+    'TMF_ROWS4': ('0 | 1: the row-stationary item pass (tmf_wsum_rows5)', True),
+    'TMF_ROWS5': ('0: the unbalanced row-stationary item pass (tmf_wsum_rows4)', True),
+    'TMF_ROWS5_TARGET': ('list entries per part of a cut row of tmf_wsum_rows5', True),
+    'TMF_ROWS4_PER_LAUNCH': ('rows per launch of the row-stationary item pass', True),
+    'TMF_HINGE_ORDER': ('0: the hinge kernel takes the users in their natural order', True),
+    'TMF_ROW_STATIONARY': ('0 | 1: the row-stationary gradU (tmf_wmrb_gradu4)', True),
+    'TMF_G4_USERS': ('users per launch of tmf_wmrb_gradu4', True),
+    'TMF_SCORES7': ('0 | 1: the item-run scores kernel (tmf_wmrb_scores7)', True),
+    'TMF_S7_SLICE_BYTES': ('bytes of V rows per slice of tmf_wmrb_scores7', True),
+    'TMF_S7_SLOTS': ('slots of a sub-chunk of tmf_wmrb_scores7', True),
+    'TMF_S7_FILL': ('0: its steps stay in item order (tmf_wmrb_scores7_f32)', True),
+    'TMF_S7_BUILD': ('device | torch: who builds the streams of tmf_wmrb_scores7', True),
+    'TMF_SCORES6': ('0 | 1: the flat-stream scores kernel (tmf_wmrb_scores6)', True),
+    'TMF_S6_SLICE_BYTES': ('bytes of V rows per slice of tmf_wmrb_scores6', True),
+    'TMF_SCORES5': ('1: the row-stationary scores kernel (tmf_wmrb_scores5), opt-in only', True),
+    'TMF_S5_SLICE_BYTES': ('bytes of V rows per slice of the stream of tmf_wmrb_scores5', True),
+    'TMF_S5_PACE': ('0: its workgroups run freely', True),
+    'TMF_S5_PACE_EVERY': ('slices between two rendezvous of its workgroups', True),
+    'TMF_S5_LAG': ('windows a workgroup of tmf_wmrb_scores5 may run ahead of its peers', True),
+    'TMF_S5_WGS': ('workgroups per launch of tmf_wmrb_scores5', True),
+}
+
+
+def switch(name, default=None):
+    """The value of a declared switch (SWITCHES) in the environment, else ``default``."""
+    if name not in SWITCHES:
+        raise KeyError(f'{name} is not declared in _engine.SWITCHES')
+    return os.environ.get(name, default)
+
+
 DEFAULT_CHUNK = 1024  # list entries per segment (heavy rows are cut into several segments)
 # bytes of gradU slice partials kept as one layer per slice (one launch); above it a single layer is summed in place by
 # per-slice launches (C4: 6.6 GB of layers, 0.8 ms faster than in place; the config-5 shard would need 82 GB and sums in place)
-PART_BUDGET = int(os.environ.get('TMF_PART_BUDGET', 8 << 30))
+PART_BUDGET = int(switch('TMF_PART_BUDGET', 8 << 30))
 
 
 def row_bytes(n_components, dtype=torch.float32):
@@ -197,7 +238,7 @@ class InteractionPlan:
 def _slab_budget():
     """Bytes of per-(user block, item) partial rows the item pass may use: TMF_SLAB_BUDGET, else a quarter of the card's
     memory capped at 64 GB (config-5 shard, 1M items: 8 blocks 118 ms, 33 -> 106, 67 -> 90; C4 needs 8.3 GB either way)."""
-    env = os.environ.get('TMF_SLAB_BUDGET')
+    env = switch('TMF_SLAB_BUDGET')
     if env:
         return int(env)
     total = torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory if torch.cuda.is_available() else 32 << 30
@@ -209,7 +250,7 @@ def default_user_chunks(n_users, ld, target_bytes=3 << 20, n_items=None):
     gather (n_users / chunks * ld * 4 bytes, most of one XCD L2) stay cache-resident while that block is processed.
     Measured at C4 (1M users, 512-byte rows), item pass ms: 48 blocks 69.7, 64 -> 60.4, 96 -> 45.2, 123 -> 35.8,
     160 -> 33.8, 256 -> 33.7 (profiles/r01_user_chunk_sweep.txt; with non-temporal partial-row stores)."""
-    env = os.environ.get('TMF_USER_CHUNKS')
+    env = switch('TMF_USER_CHUNKS')
     if env:
         return max(1, int(env))
     c = -(-n_users * ld * 4 // target_bytes)
@@ -222,7 +263,7 @@ def mse_user_chunks():
     """User blocks for the MSE item pass (CSC by (user block, item)).  Off by default: MSE lists are short (81M
     entries over 100K items at C4 against 1.1e9 for WMRB), so splitting them buys nothing - item pass 5.73 ms with
     1 block, 5.49 with 32, 8.57 with 123.  TMF_USER_CHUNKS forces a value (tests)."""
-    env = os.environ.get('TMF_USER_CHUNKS')
+    env = switch('TMF_USER_CHUNKS')
     return max(1, int(env)) if env else 1
 
 
@@ -235,7 +276,7 @@ def default_item_slices(n_items, ld, n_samples=None, target_bytes=4 << 20, elem_
     At C4 (profiles/r01_sliced_user_pass.txt): scores 33.6 ms + hinge 25.5 ms + gradU 24.9 ms + finish = 86 ms
     against 134 ms for the fused kernel, which is bound by the Infinity-Cache gather rate.  Used when the V table
     is larger than two slices; small catalogs are L2-resident anyway and keep the fused kernel."""
-    env = os.environ.get('TMF_ITEM_SLICES')
+    env = switch('TMF_ITEM_SLICES')
     if env:
         return max(1, int(env))
     # slices of ~4 MB of V rows in the table's OWN storage type (bf16 rows are half as long: C4 bf16 7 slices 65.4 ms, 13 68.0)
@@ -247,7 +288,7 @@ def default_item_slices(n_items, ld, n_samples=None, target_bytes=4 << 20, elem_
 def slices_xcd_major(n_slices):
     """Block order of the slice kernels (tmf_slice_lists.xcd_major): every XCD its own slice (eight resident at a time) or all
     of them the same one.  TMF_SLICE_XCD = 0 | 1 forces it (the library reads the same variable)."""
-    env = os.environ.get('TMF_SLICE_XCD')
+    env = switch('TMF_SLICE_XCD')
     if env in ('0', '1'):
         return env == '1'
     return XCD_MAJOR_DEFAULT and n_slices >= 8
@@ -266,9 +307,9 @@ def choose_wmrb_user_pass(n_users, n_items, ld, n_samples, n_positives, n_compon
     against 0.61 ms per user pass, item pass 0.20 against 0.26 (sorted negatives) - profiles/r02_hinge_rewrite.txt item 11.
     The slice count then only provides workgroups (the kernels also shrink their user groups, tmf_wmrb.hip)."""
     ns = default_item_slices(n_items, ld, elem_size=elem_size)
-    if ns > 1 or not fused_user_pass_fits(n_samples, n_components) or os.environ.get('TMF_FORCE_SLICED') == '1':
+    if ns > 1 or not fused_user_pass_fits(n_samples, n_components) or switch('TMF_FORCE_SLICED') == '1':
         return ns, True
-    if os.environ.get('TMF_ITEM_SLICES') or os.environ.get('TMF_FORCE_FUSED') == '1':
+    if switch('TMF_ITEM_SLICES') or switch('TMF_FORCE_FUSED') == '1':
         return ns, False
     if (n_positives / max(n_users, 1)) * n_samples >= SLICED_MIN_HINGE_TERMS and n_users * n_samples >= SLICED_MIN_SCORES:
         groups = -(-n_users // 16)
@@ -285,10 +326,10 @@ def rows4_wanted(n_components, dtype=torch.float32, plan=None, R=None, n_users=N
 
     Default: row-stationary exactly when the slab form cannot block the users for the L2s - its slab (user blocks x items x fp32
     row) would exceed the budget at ~4 MB blocks, so the blocks grow (config-5 shard: 64 blocks of 10 MB, L2 hit rate 0.43, 128 GB
-    of slab traffic per epoch; profiles/r05_c5_item_pass.txt).  Where the slab fits (C4: 163 blocks, 8.3 GB) the slab form stays:
+    of slab traffic per epoch; profiles/r05_c5_shard.txt).  Where the slab fits (C4: 163 blocks, 8.3 GB) the slab form stays:
     register-resident rows halve the waves per CU there (68 ms against 33, profiles/r03_c5_experiments.txt item 5).
     TMF_ROWS4 = 1 | 0 forces the choice."""
-    env = os.environ.get('TMF_ROWS4')
+    env = switch('TMF_ROWS4')
     if env == '0':
         return False
     if not _lib.load_library().tmf_wsum_rows4_rows_per_group(int(n_components), int(dtype is torch.bfloat16)):
@@ -312,7 +353,7 @@ ROWS5_BLOCK_BYTES = 4 << 20   # user blocks of the row-stationary item pass (con
 
 def rows5_user_chunks(n_users, n_components, dtype=torch.float32):
     """User blocks of the row-stationary item pass: ~4 MB of U rows as stored, at most 256 (TMF_USER_CHUNKS overrides)."""
-    env = os.environ.get('TMF_USER_CHUNKS')
+    env = switch('TMF_USER_CHUNKS')
     if env:
         return max(1, int(env))
     return int(min(max(1, -(-int(n_users) * row_bytes(n_components, dtype) // ROWS5_BLOCK_BYTES)), 256))
@@ -329,7 +370,7 @@ class VirtualRows:
         lens = (rowptr_e[1:] - rowptr_e[:-1]).view(n_blocks, n_rows).sum(0)                       # entries of every output row
         mean = float(lens.to(torch.float64).mean()) if n_rows else 0.0
         median = float(lens.to(torch.float64).median()) if n_rows else 0.0
-        env = os.environ.get('TMF_ROWS5_TARGET')
+        env = switch('TMF_ROWS5_TARGET')
         # just above the bulk of the rows: the ordinary rows stay whole (a cut row costs a slab slot and a second pass over it), whatever
         # lies above is cut to about the bulk's size.  Config-5 shard (median 1,300, mean 1,405 entries per item), item pass ms by
         # target: 500: 103   700: 96   1000: 95   1200: 100 (every row cut in two)   1500: 81   2100: 93   4000: 170
@@ -368,7 +409,7 @@ def hinge_user_order(rowptr_u):
     """Order in which the hinge kernel's waves take the users: by passes over their interactions (ceil(degree / 255)),
     most first, users of equal cost in their natural order (the bulk - one pass - keeps streaming its rows in sequence).
     None when no user needs a second pass.  Speed only (tmf_wmrb_hinge2_ordered)."""
-    if os.environ.get('TMF_HINGE_ORDER', '1') == '0':
+    if switch('TMF_HINGE_ORDER', '1') == '0':
         return None
     deg = rowptr_u[1:] - rowptr_u[:-1]
     passes = (deg + (HINGE_CHUNK - 1)) // HINGE_CHUNK
@@ -459,7 +500,7 @@ class WmrbPlan:
         self.ent_w = ent_id
         self.rows4 = bool(rows4)
         # the row-stationary item pass walks VIRTUAL rows (popular items cut into parts); TMF_ROWS5=0: the plain form (tmf_wsum_rows4)
-        self.vrows = VirtualRows(self.rowptr_e, C, n) if self.rows4 and os.environ.get('TMF_ROWS5', '1') != '0' else None
+        self.vrows = VirtualRows(self.rowptr_e, C, n) if self.rows4 and switch('TMF_ROWS5', '1') != '0' else None
         if not item_lists or self.rows4:
             self.seg_e = None   # the caller cuts the lists into windows itself (SegmentTable.of_rows) / row-stationary item pass
         elif C > 1:
@@ -472,7 +513,8 @@ class WmrbPlan:
         self.hinge_order = hinge_user_order(plan.rowptr_u)
         self.D = self.wbuf[nnz:].view(m, S)
         self._lists = None
-        self.s5 = self.s6 = self.s7 = None   # Scores5Plan / Scores6Plan / Scores7Plan, built by the TrainState that wants that scores kernel (scores5_wanted ...)
+        self.s5 = self.s6 = self.s7 = None   # Scores5Plan / Scores6Plan / Scores7Plan: the adopting TrainState fills at most one (scores_form)
+        self.row_stationary = None   # wmrb_plan_for's answer to row_stationary_wanted (it sized the slices by it); None: a hand-built plan
         self.route = None   # wmrb_plan_for's keyword arguments where it built this plan: TrainState.set_negatives builds the next one alike
         self.prepared = []   # (method, arguments) of what was built on this plan for its loss - sample_rank, kos_omega: set_negatives calls them on the next plan
 
@@ -541,7 +583,7 @@ def row_stationary_wanted(n_users, n_items, n_samples, nnz, n_components, dtype=
     """Whether gradU runs row-stationary (tmf_wmrb_gradu4: lane groups own users, keep their gradient rows in registers and walk
     all slices; no partial rows, no finish kernel).  TMF_ROW_STATIONARY = 1 | 0 forces it; default: where the visits are short
     (short_visits) and the kernel exists for the geometry."""
-    env = os.environ.get('TMF_ROW_STATIONARY')
+    env = switch('TMF_ROW_STATIONARY')
     if env == '0' or not sliced:
         return False
     if not _lib.load_library().tmf_wmrb_gradu4_supported(int(n_components), int(dtype is torch.bfloat16)):
@@ -563,30 +605,13 @@ def wmrb_plan_for(plan, R, n_components, dtype=torch.float32, n_items=None, forc
     # short visits (config-5 shard): the row-stationary gradU with its own slice size, unless the environment decides
     # (TMF_ROW_STATIONARY = 0 | 1, TMF_ITEM_SLICES)
     rs = row_stationary_wanted(m, n, int(R.shape[1]), plan.nnz, n_components, dtype, sliced)
-    if rs and not os.environ.get('TMF_ITEM_SLICES'):
+    if rs and not switch('TMF_ITEM_SLICES'):
         ns = int(max(1, -(-n * row_bytes(n_components, dtype) // GRADU4_SLICE_BYTES)))
     rows4 = rows4_wanted(n_components, dtype, plan, R)
     C = rows5_user_chunks(m, n_components, dtype) if rows4 else default_user_chunks(m, _lib.padded_ld(n_components), n_items=plan.n_items)
     wplan = WmrbPlan(plan, R, user_chunks=C, item_slices=ns, n_components=n_components, sliced=sliced, rows4=rows4)
-    wplan.route = dict(n_items=n_items, force_sliced=bool(force_sliced))
+    wplan.route, wplan.row_stationary = dict(n_items=n_items, force_sliced=bool(force_sliced)), rs
     return wplan
-
-
-def scores6_wanted(plan, wplan, n_components, dtype=torch.float32):
-    """Whether the sliced user pass computes its scores with flat streams on the slice-major grid (tmf_wmrb_scores6, Scores6Plan)
-    instead of per-(user, slice) visits (tmf_wmrb_scores3).  TMF_SCORES6 = 1 | 0 forces the choice; see SCORES6_MAX_VISIT for the
-    default.  Needs rows of 32 lanes, fewer than 2^24 items, a table below 4 GB and int32 places (m S, nnz < 2^31)."""
-    env = os.environ.get('TMF_SCORES6')
-    if env == '0' or wplan is None or not wplan.sliced or not plan.col_u.is_cuda or os.environ.get('TMF_SCORES5') == '1':
-        return False
-    m, S = wplan.R.shape
-    if m * S >= 2 ** 31 or plan.nnz >= 2 ** 31:
-        return False
-    if not _lib.load_library().tmf_wmrb_scores6_supported(int(n_components), int(dtype is torch.bfloat16), int(plan.n_items)):
-        return False
-    if env == '1':
-        return True
-    return SCORES6_DEFAULT and short_visits(m, plan.n_items, S, plan.nnz, n_components, dtype)
 
 
 def short_visits(n_users, n_items, n_samples, nnz, n_components, dtype=torch.float32):
@@ -617,6 +642,9 @@ class _ScoreStreams:
     with its last id (a valid user, a resident row) and the PAD place."""
 
     PAD = -2 ** 31
+
+    def ready(self):
+        """Nothing is left to build behind the constructor (Scores7Plan.ready)."""
 
     def _build(self, plan, wplan, users_per_owner, key_of, n_keys, keys_per_stream=1):
         """key_of(owner = user // users_per_owner, item) -> int32 key in [0, n_keys).  Sets ids, outs, n_entries, n_padded;
@@ -674,11 +702,16 @@ class Scores6Plan(_ScoreStreams):
         UG = int(lib.tmf_wmrb_scores6_users_per_group())
         n = plan.n_items
         self.n_groups = ng = -(-wplan.R.shape[0] // UG)
-        slice_bytes = int(os.environ.get('TMF_S6_SLICE_BYTES', slice_bytes or SCORES6_SLICE_BYTES))
+        slice_bytes = int(switch('TMF_S6_SLICE_BYTES', slice_bytes or SCORES6_SLICE_BYTES))
         ns = int(min(max(1, -(-n * row_bytes(n_components, dtype) // slice_bytes)), max(1, (2 ** 31 - 1) // max(ng, 1))))
         width = -(-n // ns)
         self.n_slices = ns = -(-n // width)
         self.chunk_ptr, _ = self._build(plan, wplan, UG, lambda grp, item: (item // width) * ng + grp, ns * ng)
+
+    def scores(self, lib, st):
+        """One workgroup per (slice, group of 32 users) chunk, the group's rows in LDS."""
+        return getattr(lib, 'tmf_wmrb_scores6' + st.sfx)(self.ids, self.outs, self.chunk_ptr, self.n_groups, self.n_slices, st.plan.n_users,
+                                                         st.plan.n_items, st.U, st.V, st.sp, st.pk, st.r, _lib.stream_ptr())
 
 
 SCORES7_SLICE_BYTES = 4 << 20   # slices of the item-run scores kernel (TMF_S7_SLICE_BYTES)
@@ -691,35 +724,10 @@ SCORES7_COST_STEP, SCORES7_COST_SLOT = 3, 2
 SCORES7_FILL = True             # the default of TMF_S7_FILL
 
 
-def scores7_wanted(plan, wplan, n_components, dtype=torch.float32):
-    """Whether the sliced user pass computes its scores by item runs (tmf_wmrb_scores7, Scores7Plan): a group of users' rows in LDS,
-    one load of a row of V for all users of the group that need it.  TMF_SCORES7 = 1 | 0 forces the choice (where the kernel exists:
-    fp32 rows of 65..128 components, fewer than 2^24 items, a table below 4 GB, int32 places); TMF_SCORES5=1 / TMF_SCORES6=1 win
-    over the default, which is on where the catalog is far beyond one slice and a group of users meets every row of a slice
-    SCORES7_MIN_SHARE times or more: UG (S + nnz / m) / n."""
-    env = os.environ.get('TMF_SCORES7')
-    if env == '0' or wplan is None or not wplan.sliced or not plan.col_u.is_cuda:
-        return False
-    m, S = wplan.R.shape
-    if m * S >= 2 ** 31 or plan.nnz >= 2 ** 31:
-        return False
-    lib = _lib.load_library()
-    if not lib.tmf_wmrb_scores7_supported(int(n_components), int(dtype is torch.bfloat16), int(plan.n_items)):
-        return False
-    if env == '1':
-        return True
-    if os.environ.get('TMF_SCORES5') == '1' or os.environ.get('TMF_SCORES6') == '1':
-        return False
-    if plan.n_items * row_bytes(n_components, dtype) < 8 * VISIT_SLICE_BYTES:
-        return False
-    UG = int(lib.tmf_wmrb_scores7_users_per_group())
-    return UG * (S + plan.nnz / max(m, 1)) / plan.n_items >= SCORES7_MIN_SHARE
-
-
 def scores7_fill_wanted():
     """Whether a TrainState that adopts a Scores7Plan puts its steps into fill order (Scores7Plan.order_by_fill) and runs
     tmf_wmrb_scores7_fill_f32.  TMF_S7_FILL = 0 | 1 forces the choice; 0 leaves the plan in item order for tmf_wmrb_scores7_f32."""
-    return os.environ.get('TMF_S7_FILL', '1' if SCORES7_FILL else '0') != '0'
+    return switch('TMF_S7_FILL', '1' if SCORES7_FILL else '0') != '0'
 
 
 def scores7_sub_wave(cnt, W):
@@ -762,13 +770,13 @@ class Scores7Plan:
         dev, i32, i64, K = plan.col_u.device, torch.int32, torch.int64, self.K
         self.users_per_group = UG = int(lib.tmf_wmrb_scores7_users_per_group())
         self.pad_slot = cap = int(lib.tmf_wmrb_scores7_slots())
-        self.slots = SL = max(1, min(cap, int(os.environ.get('TMF_S7_SLOTS', slots or cap))))
+        self.slots = SL = max(1, min(cap, int(switch('TMF_S7_SLOTS', slots or cap))))
         m, S = wplan.R.shape
         n, nnz = plan.n_items, plan.nnz
         E = nnz + m * S
         self.n_groups = ng = -(-m // UG)
         # a slice is a range of whole rows: a size below one row (0 and negative values of TMF_S7_SLICE_BYTES included) means one row
-        slice_bytes = max(1, int(os.environ.get('TMF_S7_SLICE_BYTES', slice_bytes or SCORES7_SLICE_BYTES)))
+        slice_bytes = max(1, int(switch('TMF_S7_SLICE_BYTES', slice_bytes or SCORES7_SLICE_BYTES)))
         ns = int(min(max(1, -(-n * row_bytes(n_components, dtype) // slice_bytes)), max(1, (2 ** 31 - 1) // max(ng, 1))))
         self.width = width = -(-n // ns)
         self.n_slices = ns = -(-n // width)
@@ -776,7 +784,7 @@ class Scores7Plan:
         # builder: 'device' = the chunk-local kernels of csrc/tmf_s7plan.hip (GPU tensors, the shapes the scores kernel itself takes),
         # 'torch' = the global sorts below (any device; the oracle of the kernels).  None: TMF_S7_BUILD, else 'device' where it exists
         fits = n < 2 ** 24 and nnz < 2 ** 31 and m * S < 2 ** 31 and hasattr(lib, 'tmf_s7plan_chunks')   # (TMF_LIB_OLDER: an A/B library without them)
-        builder = builder or os.environ.get('TMF_S7_BUILD') or ('device' if dev.type == 'cuda' and fits else 'torch')
+        builder = builder or switch('TMF_S7_BUILD') or ('device' if dev.type == 'cuda' and fits else 'torch')
         if builder not in ('device', 'torch'):
             raise ValueError(f"Scores7Plan: builder={builder!r} is neither 'device' nor 'torch'")
         if builder == 'device':
@@ -918,6 +926,13 @@ class Scores7Plan:
     _dev = None                  # a device-built plan in item order: (rowptr_u, col_u, R, chunk_ent, sub_fill) for order_by_fill
     sub_wave = sub_fill = None   # the tables of tmf_wmrb_scores7_fill_f32: order_by_fill() builds them
 
+    def ready(self):
+        """What an adopting state asks before the first launch, inside its out-of-memory fallback: the steps in fill order where that
+        is wanted (a plan that has its tables stays as it is); a device-built plan writes its streams here at the latest."""
+        if scores7_fill_wanted():
+            self.order_by_fill()
+        self.steps
+
     def order_by_fill(self):
         """The second step of the plan, for tmf_wmrb_scores7_fill_f32 (include/tmf.h): the step records of every sub-chunk, stably, into
         descending FILL (= slots that are no pads), so the kernel runs each class with a loop that computes its slots only and a pad
@@ -964,19 +979,14 @@ class Scores7Plan:
         self.sub_wave = scores7_sub_wave(cnt, W)
         return self
 
-
-def scores5_wanted(plan, wplan, n_components, dtype=torch.float32):
-    """Whether the sliced user pass computes its scores with the row-stationary kernel (tmf_wmrb_scores5: workgroups own 256
-    users, keep their rows in LDS and walk one flat stream of (user, item) pairs ordered by item) instead of tmf_wmrb_scores3.
-    OPT-IN (TMF_SCORES5=1), never the default: built in round 4 for the config-5 shard (1M items x 512 bytes, 9 rows per
-    (user, slice) visit of scores3) and measured there at 68 - 124 ms against 63 ms for scores3, whatever the pacing
-    (profiles/r04_scores5_experiment.txt).  Needs rows of 32 lanes, fewer than 2^24 items and a table below 4 GB."""
-    if os.environ.get('TMF_SCORES5') != '1' or wplan is None or not wplan.sliced or not plan.col_u.is_cuda:
-        return False
-    m, S = wplan.R.shape
-    if m * S >= 2 ** 31 or plan.nnz >= 2 ** 31:   # the stream's int32 places (sp index / ~p index): such shapes stay with scores3
-        return False
-    return bool(_lib.load_library().tmf_wmrb_scores5_supported(int(n_components), int(dtype is torch.bfloat16), int(plan.n_items)))
+    def scores(self, lib, st):
+        """One workgroup per (slice, group of 256 users) chunk, the group's rows in LDS, one load of a V row per run; a plan in fill
+        order (order_by_fill) runs the kernel whose pad slots cost no work."""
+        head = (self.steps, self.place, self.sub_step, self.sub_place, self.chunk_sub)
+        tail = (self.n_groups, self.n_slices, st.plan.n_users, st.plan.n_items, st.U, st.V, st.sp, st.pk, st.r, _lib.stream_ptr())
+        if self.sub_wave is None:
+            return lib.tmf_wmrb_scores7_f32(*head, *tail)
+        return lib.tmf_wmrb_scores7_fill_f32(*head, self.sub_wave, self.sub_fill, *tail)
 
 
 class Scores5Plan(_ScoreStreams):
@@ -991,7 +1001,7 @@ class Scores5Plan(_ScoreStreams):
         UB = int(lib.tmf_wmrb_scores5_users_per_workgroup())
         n = plan.n_items
         self.n_wg = n_wg = -(-wplan.R.shape[0] // UB)
-        slice_bytes = int(os.environ.get('TMF_S5_SLICE_BYTES', slice_bytes or (512 << 10)))
+        slice_bytes = int(switch('TMF_S5_SLICE_BYTES', slice_bytes or (512 << 10)))
         ns = int(min(max(1, -(-n * row_bytes(n_components, dtype) // slice_bytes)), 4096, max(1, (2 ** 31 - 1) // max(n_wg, 1))))
         width = -(-n // ns)
         self.n_slices = ns
@@ -1005,18 +1015,82 @@ class Scores5Plan(_ScoreStreams):
         # of every window in every workgroup's stream; the padding sits behind a workgroup's last entry, so offsets inside a
         # workgroup are those of the sorted list
         # at most kS5MaxWindows (4096) windows: their first steps sit in LDS - a smaller request is widened, never an error
-        every = max(1, int(os.environ.get('TMF_S5_PACE_EVERY', 32)), -(-ns // 4000))
+        every = max(1, int(switch('TMF_S5_PACE_EVERY', 32)), -(-ns // 4000))
         firsts = list(range(0, ns, every))
         off = rowptr[:n_wg * ns].view(n_wg, ns)[:, firsts] - wg_ptr[:-1, None]
         self.n_windows = nwin = len(firsts) + 1
         self.wstart = torch.zeros(n_wg, nwin + 1, dtype=i32, device=dev)
         self.wstart[:, 1:nwin] = ((off + 7) // 8).to(i32)
         self.wstart[:, nwin] = ((wg_ptr8[1:] - wg_ptr8[:-1]) // 8).to(i32)
-        self.lag = int(os.environ.get('TMF_S5_LAG', 0))
-        self.wgs_per_launch = int(os.environ.get('TMF_S5_WGS', 0))
-        self.paced = os.environ.get('TMF_S5_PACE', '1') != '0' and ns > 1
+        self.lag = int(switch('TMF_S5_LAG', 0))
+        self.wgs_per_launch = int(switch('TMF_S5_WGS', 0))
+        self.paced = switch('TMF_S5_PACE', '1') != '0' and ns > 1
         nb = lib.tmf_wmrb_scores5_workspace_bytes(n_wg, nwin, self.wgs_per_launch) if self.paced else 0
         self.sync = torch.zeros(max(nb // 4, 1), dtype=i32, device=dev)
+
+    def scores(self, lib, st):
+        """Workgroups own 256 users (rows in LDS) and walk one flat stream of (user, item) pairs."""
+        return getattr(lib, 'tmf_wmrb_scores5' + st.sfx)(
+            self.ids, self.outs, self.wg_ptr, self.n_wg, st.plan.n_users, st.plan.n_items, st.U, st.V, st.sp, st.pk, st.r,
+            self.wgs_per_launch, self.wstart if self.paced else None, self.n_windows, self.lag, self.sync if self.paced else None,
+            self.sync.numel() * 4, _lib.stream_ptr())
+
+
+# A stream form of the sliced user pass's scores kernel, a row of SCORES_FORMS: the kernel tmf_wmrb_<name>; its switch (0: never, 1:
+# forced, where `open` holds and the kernel exists); the library's query (n_components, bf16, n_items) -> 0 | 1; the plan class, built
+# by the adopting TrainState into WmrbPlan.<slot>; open(q): what even a forced choice needs; default(q): the choice where the switch
+# is not set (q: a ScoresQuery, the arguments of scores_form by name)
+ScoresForm = collections.namedtuple('ScoresForm', 'name switch supported plan slot open default')
+ScoresQuery = collections.namedtuple('ScoresQuery', 'n_users n_items n_samples nnz n_components dtype item_lists')
+
+
+def _scores7_default(q):
+    """Where the catalog is far beyond one slice and a group of UG users meets every row of a slice SCORES7_MIN_SHARE times or more;
+    TMF_SCORES5=1 / TMF_SCORES6=1 win over it."""
+    if switch('TMF_SCORES5') == '1' or switch('TMF_SCORES6') == '1' or q.n_items * row_bytes(q.n_components, q.dtype) < 8 * VISIT_SLICE_BYTES:
+        return False
+    UG = int(_lib.load_library().tmf_wmrb_scores7_users_per_group())
+    return UG * (q.n_samples + q.nnz / max(q.n_users, 1)) / q.n_items >= SCORES7_MIN_SHARE
+
+
+# In precedence order: the first row that is chosen runs, and when none is, tmf_wmrb_scores3 - one visit per (user, slice).
+SCORES_FORMS = (
+    # item runs: a group of 256 users' rows in LDS, one load of a row of V for all of them that need it.  fp32 rows of 65..128
+    # components, fewer than 2^24 items, a table below 4 GB.  The default at C4 (2.9 entries per row of a group; config-5 shard: 0.29)
+    ScoresForm('scores7', 'TMF_SCORES7', 'tmf_wmrb_scores7_supported', Scores7Plan, 's7', lambda q: True, _scores7_default),
+    # flat streams on the slice-major grid.  Rows of 32 lanes, fewer than 2^24 items, a table below 4 GB.  The default where the visits
+    # of scores3 are short (SCORES6_MAX_VISIT: the config-5 shard); TMF_SCORES5=1 wins even over TMF_SCORES6=1
+    ScoresForm('scores6', 'TMF_SCORES6', 'tmf_wmrb_scores6_supported', Scores6Plan, 's6', lambda q: switch('TMF_SCORES5') != '1',
+               lambda q: SCORES6_DEFAULT and short_visits(q.n_users, q.n_items, q.n_samples, q.nnz, q.n_components, q.dtype)),
+    # row-stationary: workgroups own 256 users and walk one flat stream ordered by item.  Same geometries as scores6, and a plan with
+    # item lists.  OPT-IN, never the default: built for the config-5 shard and measured there at 68 - 124 ms against 63 ms for scores3,
+    # whatever the pacing (profiles/r04_scores5_experiment.txt)
+    ScoresForm('scores5', 'TMF_SCORES5', 'tmf_wmrb_scores5_supported', Scores5Plan, 's5', lambda q: q.item_lists, lambda q: False),
+)
+
+
+def scores_form(n_users, n_items, n_samples, nnz, n_components, dtype=torch.float32, sliced=True, on_gpu=True, item_lists=True,
+                after=None):
+    """(name, forced): the kernel that computes the scores of the sliced user pass - the first row of SCORES_FORMS (behind the row
+    ``after``, where one is named: that form's streams did not fit) that is chosen, else 'scores3' - and whether its switch forced it.
+    Every stream form needs the sliced pass, the plan on the GPU and int32 places (n_users n_samples, nnz < 2^31)."""
+    rows = SCORES_FORMS[[f.name for f in SCORES_FORMS].index(after) + 1:] if after else SCORES_FORMS
+    if sliced and on_gpu and n_users * n_samples < 2 ** 31 and nnz < 2 ** 31:
+        q, lib = ScoresQuery(n_users, n_items, n_samples, nnz, n_components, dtype, item_lists), _lib.load_library()
+        for f in rows:
+            forced = switch(f.switch) == '1'
+            if switch(f.switch) != '0' and f.open(q) and getattr(lib, f.supported)(int(n_components), int(dtype is torch.bfloat16), int(n_items)) \
+                    and (forced or f.default(q)):
+                return f.name, forced
+    return 'scores3', False
+
+
+def scores_form_of(plan, wplan, n_components, dtype=torch.float32, after=None):
+    """scores_form of a state over (plan, wplan): what TrainState._adopt_wplan asks."""
+    if wplan is None:
+        return 'scores3', False
+    m, S = wplan.R.shape
+    return scores_form(m, plan.n_items, S, plan.nnz, n_components, dtype, wplan.sliced, plan.col_u.is_cuda, wplan.seg_e is not None, after=after)
 
 
 ITEM_BIAS_CHUNK = DEFAULT_CHUNK   # list entries one wave of tmf_item_bias_grad sums (longer list rows are cut into several chunks)
@@ -1156,8 +1230,9 @@ class TrainState:
                 relu_forward(side, E, self.slab)
 
     def _adopt_wplan(self):
-        """Everything the state derives from its WmrbPlan (``self.wplan``; None: nothing): the form of gradU, the scores plans the
-        sliced pass wants, the launch sizes and sync words of the row-stationary passes.  -> the scratch sizes that depend on the plan
+        """Everything the state derives from its WmrbPlan (``self.wplan``; None: nothing): the form of gradU, the one stream plan the
+        sliced pass's scores kernel wants (scores_form), the launch sizes and sync words of the row-stationary passes.  -> the scratch
+        sizes that depend on the plan
         (``slab`` always; ``sp`` / ``pk`` / ``part`` of the sliced pass).  __init__ and set_negatives both come through here."""
         plan, wplan, dtype, dev = self.plan, self.wplan, self.dtype, self.plan.col_u.device
         need = dict(slab=max(self._slab_fixed,
@@ -1166,8 +1241,10 @@ class TrainState:
         self.row_stationary = False
         if wplan is not None and wplan.sliced:
             m, S = wplan.R.shape
-            self.row_stationary = row_stationary_wanted(m, plan.n_items, S, plan.nnz, self.r, dtype)
-            self.users_per_launch = int(os.environ.get('TMF_G4_USERS', 32768))
+            self.row_stationary = wplan.row_stationary   # decided once, where the slices were sized for it (wmrb_plan_for)
+            if self.row_stationary is None:
+                self.row_stationary = row_stationary_wanted(m, plan.n_items, S, plan.nnz, self.r, dtype)
+            self.users_per_launch = int(switch('TMF_G4_USERS', 32768))
             if self.row_stationary:
                 nb = _lib.load_library().tmf_wmrb_gradu4_workspace_bytes(m, wplan.n_slices, self.users_per_launch)
                 self.g4_sync = torch.zeros(max(nb // 4, 1), dtype=torch.int32, device=dev)
@@ -1181,37 +1258,31 @@ class TrainState:
             else:
                 self.part_layers, self.gradu_launches = 1, 1           # a launch per slice
             need.update(sp=m * S, pk=max(plan.nnz, 1), part=self.part_layers * max(m, 1) * self.ld)
-            if scores7_wanted(plan, wplan, self.r, dtype):
+            name, forced = scores_form_of(plan, wplan, self.r, dtype)
+            while True:   # the ONE stream plan the answer names; every other slot is emptied
+                form = next((f for f in SCORES_FORMS if f.name == name), None)
+                for f in SCORES_FORMS:
+                    if f is not form:
+                        setattr(wplan, f.slot, None)
                 try:
-                    if wplan.s7 is None or wplan.s7.key != (self.r, dtype):
-                        wplan.s7 = Scores7Plan(plan, wplan, self.r, dtype)
-                    if scores7_fill_wanted():
-                        wplan.s7.order_by_fill()   # a plan that has its tables stays as it is
-                    wplan.s7.steps                 # a device-built plan writes its streams here at the latest: inside the fallback
+                    if form is not None:
+                        have = getattr(wplan, form.slot)
+                        if have is None or have.key != (self.r, dtype):
+                            setattr(wplan, form.slot, form.plan(plan, wplan, self.r, dtype))
+                        getattr(wplan, form.slot).ready()
+                    break
                 except torch.OutOfMemoryError:
-                    # the default: streams of ~10 bytes per entry that do not fit leave the pass with scores3 / scores6
-                    if os.environ.get('TMF_SCORES7') == '1':
+                    # a default form whose streams (~10 bytes per entry) do not fit leaves the pass to the rows below it
+                    if forced:
                         raise
-                    wplan.s7 = None
-            else:
-                wplan.s7 = None
-            if wplan.s7 is None and scores6_wanted(plan, wplan, self.r, dtype):
-                if wplan.s6 is None or wplan.s6.key != (self.r, dtype):
-                    wplan.s6 = Scores6Plan(plan, wplan, self.r, dtype)
-            else:
-                wplan.s6 = None
-            if wplan.seg_e is not None and scores5_wanted(plan, wplan, self.r, dtype):
-                if wplan.s5 is None or wplan.s5.key != (self.r, dtype):
-                    wplan.s5 = Scores5Plan(plan, wplan, self.r, dtype)
-            else:
-                wplan.s5 = None
+                    name, forced = scores_form_of(plan, wplan, self.r, dtype, after=name)
         if wplan is not None and wplan.rows4:
             L = _lib.load_library()
             per_group = L.tmf_wsum_rows4_rows_per_group(self.r, int(dtype is torch.bfloat16))
             if not per_group:
                 raise ValueError('the row-stationary item pass needs rows of at least 16 lanes')
             cus = torch.cuda.get_device_properties(dev).multi_processor_count if torch.cuda.is_available() else 256
-            self.rows4_per_launch = int(os.environ.get('TMF_ROWS4_PER_LAUNCH', 2 * cus * per_group))   # two workgroups per CU resident
+            self.rows4_per_launch = int(switch('TMF_ROWS4_PER_LAUNCH', 2 * cus * per_group))   # two workgroups per CU resident
             n_work = wplan.vrows.n_vrows if wplan.vrows is not None else plan.n_items
             nb = L.tmf_wsum_rows4_workspace_bytes(n_work, wplan.user_chunks, self.rows4_per_launch)
             self.rows4_sync = torch.zeros(max(nb // 4, 1), dtype=torch.int32, device=dev)
@@ -1781,32 +1852,9 @@ def _wmrb_user_pass_sliced(lib, st, adam, c, prof=None, user_epi=_lib.EPI_ADAM, 
     p, w, r = st.plan, st.wplan, st.r
     m, s = p.n_users, _lib.stream_ptr()
     lists = w.lists(p)
-    s5, s6, s7 = w.s5, w.s6, w.s7
-    if s7 is not None and s7.sub_wave is not None:
-        # item runs, the steps of a sub-chunk classed by fill: a pad slot costs no work (Scores7Plan.order_by_fill)
-        _timed(prof, 'wmrb_scores', lambda: lib.tmf_wmrb_scores7_fill_f32(
-            s7.steps, s7.place, s7.sub_step, s7.sub_place, s7.chunk_sub,
-            s7.sub_wave, s7.sub_fill, s7.n_groups, s7.n_slices, m, p.n_items, st.U, st.V,
-            st.sp, st.pk, r, s))
-    elif s7 is not None:
-        # item runs: one workgroup per (slice, group of 256 users) chunk, the group's rows in LDS, one load of a V row per run
-        _timed(prof, 'wmrb_scores', lambda: lib.tmf_wmrb_scores7_f32(
-            s7.steps, s7.place, s7.sub_step, s7.sub_place, s7.chunk_sub, s7.n_groups,
-            s7.n_slices, m, p.n_items, st.U, st.V, st.sp, st.pk, r, s))
-    elif s6 is not None:
-        # flat streams on the slice-major grid: one workgroup per (slice, group of 32 users) chunk, the group's rows in LDS
-        _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores6' + st.sfx)(
-            s6.ids, s6.outs, s6.chunk_ptr, s6.n_groups, s6.n_slices, m, p.n_items, st.U,
-            st.V, st.sp, st.pk, r, s))
-    elif s5 is not None:
-        # row-stationary scores: workgroups own 256 users (rows in LDS) and walk one flat stream of (user, item) pairs
-        _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores5' + st.sfx)(
-            s5.ids, s5.outs, s5.wg_ptr, s5.n_wg, m, p.n_items, st.U, st.V,
-            st.sp, st.pk, r, s5.wgs_per_launch, s5.wstart if s5.paced else None, s5.n_windows,
-            s5.lag, s5.sync if s5.paced else None, s5.sync.numel() * 4, s))
-    else:
-        _timed(prof, 'wmrb_scores', lambda: getattr(lib, 'tmf_wmrb_scores3' + st.sfx)(lists, st.U, st.V, st.sp,
-                                                                                st.pk, r, s))
+    stream = w.s7 or w.s6 or w.s5   # the state's one stream plan (TrainState._adopt_wplan), else a visit per (user, slice)
+    _timed(prof, 'wmrb_scores', (lambda: stream.scores(lib, st)) if stream is not None else
+           lambda: getattr(lib, 'tmf_wmrb_scores3' + st.sfx)(lists, st.U, st.V, st.sp, st.pk, r, s))
     ib = st.ib
     if ib is not None:   # the scalar item bias, into the scores before any pair step reads them (tmf_kos_weights ranks positives by pk)
         _timed(prof, 'item_bias_add', lambda: lib.tmf_item_bias_add(ib.b, p.n_items, w.R, m, w.S, st.sp, p.col_u, p.nnz, st.pk, s))

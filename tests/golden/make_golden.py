@@ -303,9 +303,97 @@ def fit_routes():
           + ', '.join(f'{rows.count(o)} {o[:40]}' for o in texts[:3]))
 
 
+# ------------------------------------------------------------------------------------------------------------------------
+# kernel_forms.json: which kernel forms _engine chooses for a WMRB fit over a grid of shapes, widths and switches
+# ------------------------------------------------------------------------------------------------------------------------
+FORM_SHAPES = dict(   # n_users, n_items, n_samples, nnz
+    c4=(1_000_000, 100_000, 1024, 100_000_000), c5_shard=(156_250, 1_000_000, 1024, 15_600_000),
+    c5_gpu=(1_250_000, 1_000_000, 1024, 124_800_000), c3=(6040, 3706, 1853, 1_000_209), mid=(100_000, 20_000, 256, 5_000_000),
+    tiny=(50, 40, 8, 200), past_int32=(3_000_000, 100_000, 1024, 1000))
+FORM_WIDTHS = ((8, 'float32'), (64, 'float32'), (100, 'float32'), (128, 'float32'), (200, 'float32'), (256, 'float32'),
+               (128, 'bfloat16'), (256, 'bfloat16'))
+FORM_SWITCHES = ('TMF_SCORES5', 'TMF_SCORES6', 'TMF_SCORES7', 'TMF_ROW_STATIONARY', 'TMF_ROWS4')
+FORM_SETTINGS = ((),) + tuple(((k, v),) for k in FORM_SWITCHES for v in '01') + (
+    (('TMF_SCORES5', '1'), ('TMF_SCORES7', '1')), (('TMF_SCORES5', '1'), ('TMF_SCORES6', '1')), (('TMF_SCORES6', '1'), ('TMF_SCORES7', '0')),
+    (('TMF_FORCE_SLICED', '1'),), (('TMF_ITEM_SLICES', '7'),))
+FORM_SLAB_BUDGET = 64 << 30
+
+
+def parent_scores_form(eng, m, n, S, nnz, r, dtype, sliced, item_lists):
+    """(name, forced) as the parent of the commit that introduced _engine.scores_form launched it: its three predicates over stand-in
+    plan objects (a plan 'on the GPU'), the cascade of its TrainState._adopt_wplan and the precedence of its user pass."""
+    import torch
+
+    class P:
+        pass
+    plan, w = P(), P()
+    plan.n_items, plan.nnz, plan.n_users, plan.col_u = n, nnz, m, P()
+    plan.col_u.is_cuda = True
+    w.sliced, w.S, w.R, w.seg_e = sliced, S, torch.zeros(m, S, dtype=torch.int8, device='meta'), (P() if item_lists else None)
+    if not sliced:
+        return 'scores3', False
+    s7 = eng.scores7_wanted(plan, w, r, dtype)
+    s6 = not s7 and eng.scores6_wanted(plan, w, r, dtype)
+    s5 = w.seg_e is not None and eng.scores5_wanted(plan, w, r, dtype)
+    name = 'scores7' if s7 else 'scores6' if s6 else 'scores5' if s5 else 'scores3'
+    return name, name != 'scores3' and os.environ.get('TMF_' + name.upper()) == '1'
+
+
+def kernel_form_outcomes(scores=None):
+    """[(outcome text, n_slices)] per case, shape-major, then width, then setting: the scores form and whether its switch forced it
+    (``scores``; None: today's _engine.scores_form), row_stationary and rows4 as wmrb_plan_for asks for them, (n_slices, sliced) of
+    choose_wmrb_user_pass.  Every case runs with TMF_SLAB_BUDGET = 64 GiB and no other TMF_* variable but its setting's; the
+    caller's environment is put back.  Needs libtmf.so's host queries, no GPU."""
+    import torch
+    from teamoflow_amd import _engine as eng, _lib
+    scores = scores or (lambda eng, *a: eng.scores_form(*a[:6], sliced=a[6], on_gpu=True, item_lists=a[7]))
+    kept = {k: os.environ.pop(k) for k in list(os.environ) if k.startswith('TMF_') and k != 'TMF_LIB'}
+    out = []
+    try:
+        for m, n, S, nnz in FORM_SHAPES.values():
+            for r, dt in FORM_WIDTHS:
+                dtype = getattr(torch, dt)
+                for setting in FORM_SETTINGS:
+                    os.environ.update(dict(setting, TMF_SLAB_BUDGET=str(FORM_SLAB_BUDGET)))
+                    ns, sliced = eng.choose_wmrb_user_pass(m, n, _lib.padded_ld(r, dtype), S, nnz, r, elem_size=2 if dt == 'bfloat16' else 4)
+                    rs = eng.row_stationary_wanted(m, n, S, nnz, r, dtype, sliced)
+                    rows4 = eng.rows4_wanted(r, dtype, n_users=m, n_items=n)
+                    name, forced = scores(eng, m, n, S, nnz, r, dtype, sliced, not rows4)
+                    flags = [f for f, on in (('forced', forced), ('row_stationary', rs), ('rows4', rows4), ('sliced', sliced)) if on]
+                    out.append((' '.join([name] + flags), int(ns)))
+                    for k, _ in setting:
+                        del os.environ[k]
+    finally:
+        os.environ.pop('TMF_SLAB_BUDGET', None)
+        os.environ.update(kept)
+    return out
+
+
+def kernel_forms():
+    """Writes kernel_forms.json, the record of what the PARENT of the commit that introduced _engine.scores_form chose.  Like
+    fit_routes: run in a worktree of that parent with this file copied into it (``python tests/golden/make_golden.py kernel_forms``),
+    never regenerated from a later tree; tests/test_scores_form_cpu.py replays it.  A row is one character, the index of its outcome
+    text, and its slice count."""
+    import json
+    got = kernel_form_outcomes(parent_scores_form)
+    texts = sorted({o for o, _ in got})
+    letter = dict(zip(texts, string.ascii_letters[:len(texts)], strict=True))
+    doc = dict(shapes={k: list(v) for k, v in FORM_SHAPES.items()}, widths=[list(w) for w in FORM_WIDTHS],
+               settings=[[list(kv) for kv in s] for s in FORM_SETTINGS], slab_budget=FORM_SLAB_BUDGET, outcomes=texts,
+               rows=''.join(letter[o] for o, _ in got), n_slices=[ns for _, ns in got])
+    path = os.path.join(HERE, 'kernel_forms.json')
+    with open(path, 'w') as f:
+        json.dump(doc, f)
+        f.write('\n')
+    print(f'kernel_forms: {len(got)} rows, {len(texts)} outcomes, {os.path.getsize(path) / 1024:.1f} KiB; '
+          + ', '.join(f"{sum(o.split()[0] == k for o, _ in got)} {k}" for k in ('scores3', 'scores5', 'scores6', 'scores7')))
+
+
 if __name__ == '__main__':
     if sys.argv[1:] == ['fit_routes']:
         sys.exit(fit_routes())
+    if sys.argv[1:] == ['kernel_forms']:
+        sys.exit(kernel_forms())
     plugins()
     gather_known_answer()
     c1_mse()

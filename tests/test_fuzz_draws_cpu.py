@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import assert_step, rel_err
+from teamoflow_amd._engine import SWITCHES
 from test_bpr_cpu import bpr_closed_form, bpr_pairs_fp32_kernel_order, bpr_problem, fresh_adam_fp32
 from test_softmax_cpu import softmax_closed_form, softmax_pairs_fp32_kernel_order, sum_identity_gaps
 from test_warp_cpu import decidedness, warp_closed_form, warp_pairs_fp32_kernel_order, warp_problem
@@ -21,9 +22,7 @@ DEFAULT_SEEDS = 24
 LR = 0.05
 
 # every variable that chooses a form of a pass: a test clears them all before it sets its own
-FORM_KEYS = ('TMF_ROWS4', 'TMF_ROWS5', 'TMF_ROWS5_TARGET', 'TMF_SCORES5', 'TMF_SCORES6', 'TMF_S6_SLICE_BYTES', 'TMF_SCORES7',
-             'TMF_S7_SLICE_BYTES', 'TMF_S7_SLOTS', 'TMF_S7_FILL', 'TMF_ROW_STATIONARY', 'TMF_ITEM_SLICES', 'TMF_USER_CHUNKS',
-             'TMF_FORCE_SLICED', 'TMF_SLICE_XCD', 'TMF_G4_USERS', 'TMF_ROWS4_PER_LAUNCH')
+FORM_KEYS = tuple(k for k, (_, form) in SWITCHES.items() if form)   # declared once, beside their one reader
 
 S7_R = (65, 72, 96, 100, 127, 128)                    # the widths tmf_wmrb_scores7 exists for: both ends, pad columns, none
 S7_SLOTS = (1, 3, 4, 64, 100, 512, None)              # TMF_S7_SLOTS; None = unset (the library's buffer)

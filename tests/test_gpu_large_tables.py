@@ -391,7 +391,7 @@ def test_wmrb_epoch_against_fp64_at_and_past_4gb(eng, monkeypatch, n, r, dtype):
     e = wmrb_epoch(eng, monkeypatch, p, 'asked_s6' if past else 's6')
     check_wmrb_against_fp64(p, e, r, f'n={n} {dtype}')
     assert (e['wplan'].s6 is None) == past and e['wplan'].s5 is None
-    assert eng.scores6_wanted(e['plan'], e['wplan'], r, dtype) == (not past)
+    assert eng.scores_form_of(e['plan'], e['wplan'], r, dtype) == (('scores3', False) if past else ('scores6', True))
     assert lib.tmf_wmrb_scores6_supported(r, bf, n) == (0 if past else 1)
     assert lib.tmf_wmrb_scores5_supported(r, bf, n) == (0 if past else 1)
     del e, p

@@ -106,35 +106,3 @@ def test_plain_rows4_is_still_there_and_agrees(eng, monkeypatch):
     gc, _, w, _ = item_gradient(eng, monkeypatch, 'rows5', idx, val, R, U, V, m, n, r, S, torch.float32, 4, target=10 ** 9)
     assert float((ga - gb).abs().max()) <= 2e-6 * float(ga.abs().max())
     assert w.vrows.n_long == 0 and w.vrows.n_vrows == n and torch.equal(gb, gc)   # no row cut: rows5 IS rows4, bit for bit
-
-
-def test_the_item_pass_form_follows_the_shape(eng, monkeypatch):
-    """Row-stationary exactly where the slab form cannot block the users for the L2s (its slab would exceed the budget at ~4 MB
-    blocks): the config-5 shard, not C4 and not the small shapes.  TMF_ROWS4 = 0 | 1 forces either."""
-    monkeypatch.delenv('TMF_ROWS4', raising=False)
-    monkeypatch.delenv('TMF_SLAB_BUDGET', raising=False)
-    bf, f32 = torch.bfloat16, torch.float32
-    assert eng.rows4_wanted(256, bf, n_users=1_250_000, n_items=1_000_000)          # one GPU's share of config 5
-    assert not eng.rows4_wanted(128, f32, n_users=1_000_000, n_items=100_000)       # C4: 163 blocks, 8.3 GB of slab
-    assert not eng.rows4_wanted(64, f32, n_users=6040, n_items=3706)                # C3
-    assert not eng.rows4_wanted(8, f32, n_users=10_000_000, n_items=10_000_000)     # rows of fewer than 16 lanes: no such kernel
-    monkeypatch.setenv('TMF_ROWS4', '1')
-    assert eng.rows4_wanted(128, f32, n_users=1000, n_items=1000)
-    monkeypatch.setenv('TMF_ROWS4', '0')
-    assert not eng.rows4_wanted(256, bf, n_users=1_250_000, n_items=1_000_000)
-    assert eng.rows5_user_chunks(1_250_000, 256, bf) == 153      # 4 MB of bf16 rows per block
-
-
-def test_the_user_pass_forms_follow_the_shape_too(eng, monkeypatch):
-    """Short (user, 4 MB slice) visits - the config-5 shard: 9 rows - take the flat-stream scores kernel and the row-stationary
-    gradU with 3.2 MB slices; C4 (88 rows per visit) and the small configurations keep scores3 / gradu3."""
-    for k in ('TMF_ROW_STATIONARY', 'TMF_SCORES6', 'TMF_SCORES5', 'TMF_ITEM_SLICES'):
-        monkeypatch.delenv(k, raising=False)
-    bf, f32 = torch.bfloat16, torch.float32
-    assert eng.short_visits(1_250_000, 1_000_000, 1024, 125_000_000, 256, bf)
-    assert not eng.short_visits(1_000_000, 100_000, 1024, 100_000_000, 128, f32)
-    assert not eng.short_visits(6040, 3706, 1853, 1_000_209, 64, f32) and not eng.short_visits(50, 100, 5, 200, 128, f32)
-    assert eng.row_stationary_wanted(1_250_000, 1_000_000, 1024, 125_000_000, 256, bf)
-    assert not eng.row_stationary_wanted(1_000_000, 100_000, 1024, 100_000_000, 128, f32)
-    monkeypatch.setenv('TMF_ROW_STATIONARY', '0')
-    assert not eng.row_stationary_wanted(1_250_000, 1_000_000, 1024, 125_000_000, 256, bf)

@@ -120,11 +120,13 @@ def test_scores5_is_opt_in_only(eng, monkeypatch):
                                           (1_000_000, 64, torch.float32, False), (20_000_000, 128, torch.float32, False)):
         plan, w = P(), P()
         plan.n_items, plan.nnz, plan.n_users, plan.col_u = n_items, 100 * 1000, 1000, torch.zeros(1, device='cuda')
-        w.sliced, w.S, w.R = True, 1024, torch.zeros(1000, 1024)
+        w.sliced, w.S, w.R, w.seg_e = True, 1024, torch.zeros(1000, 1024), object()
         monkeypatch.delenv('TMF_SCORES5', raising=False)
-        assert not eng.scores5_wanted(plan, w, r, dtype)
+        assert eng.scores_form_of(plan, w, r, dtype)[0] != 'scores5'
         monkeypatch.setenv('TMF_SCORES5', '1')
-        assert eng.scores5_wanted(plan, w, r, dtype) == has_kernel, (n_items, r)
+        assert eng.scores_form_of(plan, w, r, dtype) == (('scores5', True) if has_kernel else ('scores3', False)), (n_items, r)
+        w.seg_e = None   # a plan without item lists (the row-stationary item pass) has no such streams
+        assert eng.scores_form_of(plan, w, r, dtype) == ('scores3', False)
 
 
 @pytest.mark.parametrize('lag', [0, 2])

@@ -101,12 +101,13 @@ def test_scores6_geometries(eng, monkeypatch):
                                           (1_000_000, 64, torch.float32, False), (20_000_000, 128, torch.float32, False)):
         plan, w = P(), P()
         plan.n_items, plan.nnz, plan.n_users, plan.col_u = n_items, 100 * 1000, 1000, torch.zeros(1, device='cuda')
-        w.sliced, w.R = True, torch.zeros(1000, 1024)
+        w.sliced, w.R, w.seg_e = True, torch.zeros(1000, 1024), object()
         monkeypatch.setenv('TMF_SCORES5', '0')
         monkeypatch.setenv('TMF_SCORES6', '0')
-        assert not eng.scores6_wanted(plan, w, r, dtype)
+        monkeypatch.setenv('TMF_SCORES7', '0')   # scores6's own answer, not what wins over it
+        assert eng.scores_form_of(plan, w, r, dtype) == ('scores3', False)
         monkeypatch.setenv('TMF_SCORES6', '1')
-        assert eng.scores6_wanted(plan, w, r, dtype) == has_kernel, (n_items, r)
+        assert eng.scores_form_of(plan, w, r, dtype) == (('scores6', True) if has_kernel else ('scores3', False)), (n_items, r)
 
 
 def test_stated_catalog_size_is_checked_on_request(eng, monkeypatch):

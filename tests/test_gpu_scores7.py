@@ -3,6 +3,8 @@ in LDS, one load of a row of V for all users of the group that need it; csrc/tmf
 tmf_wmrb_scores3 and an fp64 product.  Both compute sp[u, s] = <U[u], V[R[u, s]]> and p[k] = <U[u_k], V[j_k]>; they differ in the
 order of the fp32 sum inside a dot product only: equal to rounding on real data, bit for bit on dyadic data - and then the whole
 epoch (hinge, gradients, fresh Adam) is bit-identical too."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -170,41 +172,6 @@ def test_scores7_bpr_step_equals_the_scores3_path(eng, monkeypatch):
     assert a['loss'] == b['loss']
 
 
-def test_scores7_selection(eng, monkeypatch):
-    """Default: on at C4 (a group of 256 users meets every row of a slice 2.9 times), off at the config-5 shard (0.29: scores6
-    stays), off at C3 and every small shape; TMF_SCORES7 forces it where the kernel exists; TMF_SCORES5 / TMF_SCORES6 = 1 win over
-    the default; the other choices answer as before."""
-    class P:
-        pass
-
-    def shape(m, n, nnz, S):
-        plan, w = P(), P()
-        plan.n_items, plan.nnz, plan.n_users, plan.col_u = n, nnz, m, torch.zeros(1, device='cuda')
-        w.sliced, w.S, w.R = True, S, torch.zeros(m, S, dtype=torch.int8, device='meta')
-        return plan, w
-    for name in ('TMF_SCORES5', 'TMF_SCORES6', 'TMF_SCORES7'):
-        monkeypatch.delenv(name, raising=False)
-    c4 = shape(1_000_000, 100_000, 100_000_000, 1024)
-    c5 = shape(156_250, 1_000_000, 15_600_000, 1024)
-    c3 = shape(100_000, 20_000, 5_000_000, 256)
-    f32, bf16 = torch.float32, torch.bfloat16
-    assert eng.scores7_wanted(*c4, 128, f32) and not eng.scores6_wanted(*c4, 128, f32)
-    assert not eng.scores7_wanted(*c5, 256, bf16) and eng.scores6_wanted(*c5, 256, bf16)
-    assert not eng.scores7_wanted(*c5, 128, f32)                       # fp32 rows there too: 0.29 entries per row of a group
-    assert not eng.scores7_wanted(*c3, 128, f32) and not eng.scores6_wanted(*c3, 128, f32)
-    assert not eng.scores7_wanted(*c4, 128, bf16) and not eng.scores7_wanted(*c4, 64, f32) and not eng.scores7_wanted(*c4, 256, f32)
-    for other in ('TMF_SCORES5', 'TMF_SCORES6'):
-        monkeypatch.setenv(other, '1')
-        assert not eng.scores7_wanted(*c4, 128, f32)
-        monkeypatch.delenv(other)
-    monkeypatch.setenv('TMF_SCORES7', '0')
-    assert not eng.scores7_wanted(*c4, 128, f32)
-    monkeypatch.setenv('TMF_SCORES7', '1')
-    assert eng.scores7_wanted(*c3, 128, f32) and eng.scores7_wanted(*c5, 128, f32)
-    assert not eng.scores7_wanted(*c3, 128, bf16) and not eng.scores7_wanted(*c3, 200, f32)
-    assert not eng.scores7_wanted(*shape(3_000_000, 100_000, 1000, 1024), 128, f32)   # m S >= 2^31: int32 places
-
-
 def test_scores7_default_falls_back_when_the_streams_do_not_fit(eng, monkeypatch):
     """The default construction that runs out of memory leaves the pass with scores3; a forced one raises."""
     m, n, r, S = 300, 2000, 128, 50
@@ -212,14 +179,17 @@ def test_scores7_default_falls_back_when_the_streams_do_not_fit(eng, monkeypatch
 
     def no_memory(*a, **k):
         raise torch.OutOfMemoryError('streams of tmf_wmrb_scores7')
-    monkeypatch.setattr(eng, 'Scores7Plan', no_memory)
-    monkeypatch.setattr(eng, 'scores7_wanted', lambda *a, **k: True)
+    rows = tuple(f._replace(plan=no_memory) if f.name == 'scores7' else f for f in eng.SCORES_FORMS)
+    monkeypatch.setattr(eng, 'SCORES_FORMS', rows)
+    real = eng.scores_form   # scores7 at this small shape, as the default unless its switch forces it; behind it, the rows' own answers
+    monkeypatch.setattr(eng, 'scores_form', lambda *a, after=None, **k: real(*a, after=after, **k) if after else
+                        ('scores7', os.environ.get('TMF_SCORES7') == '1'))
     for name in ('TMF_SCORES5', 'TMF_SCORES6', 'TMF_SCORES7'):
         monkeypatch.delenv(name, raising=False)
     plan = eng.InteractionPlan(idx, val, m, n)
     wplan = eng.WmrbPlan(plan, R, item_slices=2, n_components=r, sliced=True)
     st = eng.TrainState(U, V, plan, r, wplan)
-    assert wplan.s7 is None
+    assert wplan.s7 is None and wplan.s6 is None and wplan.s5 is None
     loss = torch.zeros(1, dtype=torch.float64, device='cuda')
     eng.epoch_wmrb(st, eng.adam_constants(0.05), n / S, loss)
     torch.cuda.synchronize()
