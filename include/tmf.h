@@ -455,6 +455,25 @@ int tmf_warp_pairs_kos(const int64_t* rowptr, const float* val, const float* p, 
  * only: heavy users first).  Finite for every finite score; a NaN or an infinity stays inside its user. */
 int tmf_softmax_pairs(const int64_t* rowptr, const float* val, const float* p, const float* sp, int32_t n_users, int32_t n_samples,
                       float c, float* delta, float* D, float* loss_part, const int32_t* user_order, void* stream);
+/* The logQ correction of SampledSoftmaxLoss (an extension; TMF_VERSION stays 203: nothing that existed changes).
+ * tmf_softmax_pairs_offset is tmf_softmax_pairs - the same kernel body, a template parameter apart - on the corrected scores
+ * x[u, s] = fl(sp[u, s] - off[u, s]), one fp32 subtraction each: M, e_s, Z and D are those of x, p[k] stays raw, and D is the
+ * derivative with respect to sp as well.  off: fp32 [n_users, n_samples] in the slot order of sp, read once where sp is read once
+ * (tile 0 of the corrected scores stays in registers from that read to the D write; a longer row reads both streams again), both
+ * streams' loads of a tile in flight together.  Everything else as above: every output element overwritten, zeros for a user
+ * without a value > 0 (neither sp nor off of a user without entries is read), no atomics, every sum in one fixed order, bits
+ * independent of user_order; off = 0 gives the bits of tmf_softmax_pairs.  A NaN or an infinity among a user's offsets stays
+ * inside that user.  n_users = 0 is TMF_OK; a negative count, n_samples = 0 with users, or a null rowptr / sp / off / D:
+ * TMF_E_INVALID before any launch.
+ * tmf_slot_offsets builds that table: off[j] = ell[R[j]] over the flat [n_users * n_samples] table R of item ids, which the caller
+ * has checked to lie in [0, n_items) - ell: fp32 [n_items].  16-byte pieces where R and off are both 16-byte aligned, element by
+ * element otherwise and behind the last whole piece.  Once per table, not per epoch.  n_users = 0 or n_samples = 0: TMF_OK, no
+ * launch; a negative count or a null ell / R / off with samples: TMF_E_INVALID before any launch.  Plain vector loads and stores. */
+int tmf_softmax_pairs_offset(const int64_t* rowptr, const float* val, const float* p, const float* sp, const float* off,
+                             int32_t n_users, int32_t n_samples, float c, float* delta, float* D, float* loss_part,
+                             const int32_t* user_order, void* stream);
+int tmf_slot_offsets(const float* ell, int32_t n_items, const int32_t* R, int64_t n_users, int32_t n_samples, float* off,
+                     void* stream);
 int tmf_wmrb_gradu3_f32(const tmf_slice_lists* lists, const float* D, const float* delta, const void* V, float* part,
                         int per_slice_launches, int n_components, void* stream);
 int tmf_wmrb_gradu3_bf16(const tmf_slice_lists* lists, const float* D, const float* delta, const void* V, float* part,

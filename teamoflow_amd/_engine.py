@@ -516,7 +516,8 @@ class WmrbPlan:
         self.s5 = self.s6 = self.s7 = None   # Scores5Plan / Scores6Plan / Scores7Plan: the adopting TrainState fills at most one (scores_form)
         self.row_stationary = None   # wmrb_plan_for's answer to row_stationary_wanted (it sized the slices by it); None: a hand-built plan
         self.route = None   # wmrb_plan_for's keyword arguments where it built this plan: TrainState.set_negatives builds the next one alike
-        self.prepared = []   # (method, arguments) of what was built on this plan for its loss - sample_rank, kos_omega: set_negatives calls them on the next plan
+        self.prepared = []   # (method, arguments) of what was built on this plan for its loss - sample_rank, kos_omega, slot_offsets: set_negatives calls them on the next plan
+        self.off = None      # slot_offsets(): the logQ offsets of this table, in the order of R / sp / D (None: an uncorrected fit)
 
     def release(self):
         """Drops every index structure (entry lists, sorted table, weights, score streams, slice lists, ranks) whoever still holds the
@@ -568,6 +569,27 @@ class WmrbPlan:
             self.omega = torch.empty(nnz, dtype=torch.float32, device=self.R.device)
             self.prepared.append(('kos_omega', (nnz,)))
         return self.omega
+
+    def slot_offsets(self, ell):
+        """The offsets of a SampledSoftmaxLoss fit under sampling_correction='logq': off[u, s] = ell[R[u, s]], fp32 [n_users, n_samples]
+        in the plan's slot order (the order of sp and D), ell fp32 [n_items] on the plan's device (utils.log_expected_count).  Built
+        once per table by tmf_slot_offsets - the pair step then reads it as a coalesced stream instead of gathering from ell every
+        epoch - and kept with the plan; noted in ``prepared`` with ell, so TrainState.set_negatives builds it again for the next
+        table and no epoch allocates."""
+        if self.off is None:
+            m, S = self.R.shape
+            ell = ell.to(device=self.R.device, dtype=torch.float32).contiguous()
+            n = (self.rowptr_e.numel() - 1) // self.user_chunks   # the plan's n_items: R's ids were checked against it
+            if ell.numel() != n:
+                raise ValueError(f'slot_offsets: {ell.numel()} offsets for {n} items')
+            if self.R.is_cuda:
+                lib = _lib.get()
+                self.off = torch.empty(m, S, dtype=torch.float32, device=self.R.device)
+                _lib.check(lib.tmf_slot_offsets(ell, n, self.R, m, S, self.off, _lib.stream_ptr()), lib)
+            else:
+                self.off = ell[self.R.to(torch.int64)]
+            self.prepared.append(('slot_offsets', (ell,)))
+        return self.off
 
     def D_in_model_order(self):
         """D[u, s] indexed like the model's random_ind (the sliced pass keeps every user's negatives sorted by item)."""
@@ -1841,7 +1863,13 @@ def kos_pairs(lib, st, c, prof, head, tail):
 
 def softmax_pairs(lib, st, c, prof, head, tail):
     """SampledSoftmaxLoss (csrc/tmf_softmax.hip), the hinge kernel's arguments, c = 1 or n_items / n_samples:
-    -log(exp(p_k) / (exp(p_k) + c sum_s exp(sp[u, s]))) per positive.  No dependence on the order of a user's samples."""
+    -log(exp(p_k) / (exp(p_k) + c sum_s exp(sp[u, s]))) per positive.  No dependence on the order of a user's samples.
+    A plan with logQ offsets (WmrbPlan.slot_offsets: sampling_correction='logq' on tables drawn by popularity) takes the same step on
+    sp - off, with c = 1: the form is chosen from the state, as the bias passes are from st.ib."""
+    off = st.wplan.off
+    if off is not None:
+        _timed(prof, 'softmax_pairs', lambda: lib.tmf_softmax_pairs_offset(*head, off, st.plan.n_users, st.wplan.S, 1.0, *tail))
+        return
     _timed(prof, 'softmax_pairs', lambda: lib.tmf_softmax_pairs(*head, st.plan.n_users, st.wplan.S, c, *tail))
 
 

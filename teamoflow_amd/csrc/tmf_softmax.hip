@@ -30,6 +30,11 @@
 // not 0.  exp(x) = exp2(h) (1 + l ln 2) with h + l = x log2(e) to 48 bits: an argument of -100 costs no more than one near 0.
 // A NaN or an infinity among a user's scores may make that user's outputs non-finite (a sample of -inf alone does not: e_s = 0);
 // no other user reads them.
+//
+// The logQ correction (tmf_softmax_pairs_offset): the same body on x_s = sp[u, s] - off[u, s], off[u, s] = the log of how often the
+// sampler proposes the item in slot s - a table built once per negative table by tmf_slot_offsets (off[j] = ell[R[j]]), because the
+// gather it replaces would move a 128-byte line per 4-byte offset in every epoch.  The pair step reads it as a third
+// coalesced stream beside sp and D: 12 S bytes per user where the plain step moves 8 S.
 #include <math.h>
 
 #include "tmf_common.h"
@@ -55,12 +60,25 @@ __device__ __forceinline__ float wave_sum_f32(float v) {   // fixed butterfly: e
     return v;
 }
 
-// The scores of tile s0 (-inf beyond the row) and the largest of the lane's
-__device__ __forceinline__ float softmax_load_tile(const float* __restrict__ spu, int64_t s0, int S, int lane, float (&x)[XSPL]) {
+// The scores of tile s0 (-inf beyond the row) and the largest of the lane's.  OFF: the corrected scores sp[u, s] - off[u, s], one
+// fp32 subtraction each; both streams' loads of the tile are in flight together (offu is not read otherwise)
+template <bool OFF>
+__device__ __forceinline__ float softmax_load_tile(const float* __restrict__ spu, const float* __restrict__ offu, int64_t s0, int S,
+                                                   int lane, float (&x)[XSPL]) {
 #pragma unroll
     for (int j = 0; j < XSPL; ++j) {                       // the loads of a tile are in flight together
         const int64_t s = s0 + lane + 64 * j;
         x[j] = (s < S) ? spu[s] : -INFINITY;
+    }
+    if constexpr (OFF) {
+        float o[XSPL];
+#pragma unroll
+        for (int j = 0; j < XSPL; ++j) {
+            const int64_t s = s0 + lane + 64 * j;
+            o[j] = (s < S) ? offu[s] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < XSPL; ++j) x[j] = __fsub_rn(x[j], o[j]);
     }
     float mx = x[0];
 #pragma unroll
@@ -87,9 +105,13 @@ __device__ __forceinline__ void softmax_store_tile(float* __restrict__ Du, int64
     }
 }
 
+// OFF = false: the plain step (off is not read).  OFF = true: the same step on x_s = sp[u, s] - off[u, s] - M, e_s, Z and D are those
+// of the corrected scores; p_k stays raw.
+template <bool OFF>
 __global__ __launch_bounds__(64) void k_softmax_pairs(const int64_t* __restrict__ rowptr, const float* __restrict__ val,
-                                                      const float* __restrict__ p, const float* __restrict__ sp, int S, float c,
-                                                      int64_t n_users, float* __restrict__ delta, float* __restrict__ D,
+                                                      const float* __restrict__ p, const float* __restrict__ sp,
+                                                      const float* __restrict__ off, int S, float c, int64_t n_users,
+                                                      float* __restrict__ delta, float* __restrict__ D,
                                                       float* __restrict__ loss_part, const int32_t* __restrict__ order) {
     const int lane = threadIdx.x;
     const int64_t slot = blockIdx.x;
@@ -99,6 +121,7 @@ __global__ __launch_bounds__(64) void k_softmax_pairs(const int64_t* __restrict_
     const int64_t u = order ? (int64_t)order[slot] : slot;
     const int64_t rb = rowptr[u], re = rowptr[u + 1];
     const float* spu = sp + u * (int64_t)S;
+    const float* offu = OFF ? off + u * (int64_t)S : nullptr;
     float* Du = D + u * (int64_t)S;
 
     if (rb == re) {                                        // nothing stored: the row is not read
@@ -109,10 +132,10 @@ __global__ __launch_bounds__(64) void k_softmax_pairs(const int64_t* __restrict_
 
     // ---- the row: M, e_s, Z ----
     float e[XSPL];                                         // tile 0: scores, then e_s, until the D write
-    float mx = softmax_load_tile(spu, 0, S, lane, e);
+    float mx = softmax_load_tile<OFF>(spu, offu, 0, S, lane, e);
     for (int64_t s0 = XCAP; s0 < S; s0 += XCAP) {
         float y[XSPL];
-        mx = fmaxf(mx, softmax_load_tile(spu, s0, S, lane, y));
+        mx = fmaxf(mx, softmax_load_tile<OFF>(spu, offu, s0, S, lane, y));
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
@@ -120,7 +143,7 @@ __global__ __launch_bounds__(64) void k_softmax_pairs(const int64_t* __restrict_
     float z = softmax_exps(e, M);
     for (int64_t s0 = XCAP; s0 < S; s0 += XCAP) {
         float y[XSPL];
-        (void)softmax_load_tile(spu, s0, S, lane, y);
+        (void)softmax_load_tile<OFF>(spu, offu, s0, S, lane, y);
         z += softmax_exps(y, M);                           // tile after tile
     }
     const float cZ = c * wave_sum_f32(z);
@@ -158,13 +181,44 @@ __global__ __launch_bounds__(64) void k_softmax_pairs(const int64_t* __restrict_
     softmax_store_tile(Du, 0, S, lane, e, C);
     for (int64_t s0 = XCAP; s0 < S; s0 += XCAP) {
         float y[XSPL];
-        (void)softmax_load_tile(spu, s0, S, lane, y);
+        (void)softmax_load_tile<OFF>(spu, offu, s0, S, lane, y);
         (void)softmax_exps(y, M);
         softmax_store_tile(Du, s0, S, lane, y, C);
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) lacc += __shfl_xor(lacc, off, 64);  // fixed butterfly: every lane ends with the same bits
     if (lane == 0 && loss_part) loss_part[u] = (float)lacc;
+}
+
+constexpr int kSoThreads = 256;
+constexpr unsigned kSoBlocks = 16384;          // grid-stride workgroups (64 per CU), as tmf_item_bias_add
+
+static inline bool so_aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
+// off[j] = ell[R[j]] over the flat table - n4 int4 / float4 pieces when both are 16-byte aligned (VEC), the elements behind the last
+// whole piece (or all of them) one by one: k_item_bias_add's walk with a store where it adds.
+template <bool VEC>
+__global__ __launch_bounds__(kSoThreads) void k_slot_offsets(const float* __restrict__ ell, const int32_t* __restrict__ R,
+                                                             float* __restrict__ off, int64_t total) {
+    const int64_t gid = (int64_t)blockIdx.x * kSoThreads + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * kSoThreads;
+    int64_t done = 0;
+    if constexpr (VEC) {
+        const int64_t n4 = total / 4;
+        const int4* R4 = reinterpret_cast<const int4*>(R);
+        float4* off4 = reinterpret_cast<float4*>(off);
+        for (int64_t i = gid; i < n4; i += stride) {
+            const int4 id = R4[i];
+            float4 v;
+            v.x = ell[id.x];
+            v.y = ell[id.y];
+            v.z = ell[id.z];
+            v.w = ell[id.w];
+            off4[i] = v;
+        }
+        done = 4 * n4;
+    }
+    for (int64_t j = done + gid; j < total; j += stride) off[j] = ell[R[j]];
 }
 
 }  // namespace tmf
@@ -178,7 +232,41 @@ extern "C" int tmf_softmax_pairs(const int64_t* rowptr, const float* val, const 
     // val, p and delta are read only where a row has entries: a table without interactions may pass NULL for them
     TMF_REQUIRE(rowptr && sp && D && n_users > 0 && n_samples > 0, "softmax_pairs: bad arguments");
     TMF_REQUIRE_LAUNCH(n_users, 64, "tmf_softmax_pairs");
-    hipLaunchKernelGGL(k_softmax_pairs, dim3((unsigned)n_users), dim3(64), 0, (hipStream_t)stream, rowptr, val, p, sp, (int)n_samples,
-                       c, (int64_t)n_users, delta, D, loss_part, user_order);
+    hipLaunchKernelGGL(k_softmax_pairs<false>, dim3((unsigned)n_users), dim3(64), 0, (hipStream_t)stream, rowptr, val, p, sp,
+                       (const float*)nullptr, (int)n_samples, c, (int64_t)n_users, delta, D, loss_part, user_order);
     return check_launch("tmf_softmax_pairs");
+}
+
+extern "C" int tmf_softmax_pairs_offset(const int64_t* rowptr, const float* val, const float* p, const float* sp, const float* off,
+                                        int32_t n_users, int32_t n_samples, float c, float* delta, float* D, float* loss_part,
+                                        const int32_t* user_order, void* stream) {
+    TMF_REQUIRE(n_users >= 0 && n_samples >= 0, "softmax_pairs_offset: n_users=%d n_samples=%d", n_users, n_samples);
+    if (n_users == 0) return TMF_OK;
+    TMF_REQUIRE(rowptr && sp && off && D && n_samples > 0, "softmax_pairs_offset: bad arguments");
+    TMF_REQUIRE_LAUNCH(n_users, 64, "tmf_softmax_pairs_offset");
+    hipLaunchKernelGGL(k_softmax_pairs<true>, dim3((unsigned)n_users), dim3(64), 0, (hipStream_t)stream, rowptr, val, p, sp, off,
+                       (int)n_samples, c, (int64_t)n_users, delta, D, loss_part, user_order);
+    return check_launch("tmf_softmax_pairs_offset");
+}
+
+// off[j] = ell[R[j]] over the flat [n_users * n_samples] table: the slot offsets of a logQ-corrected fit, once per table
+extern "C" int tmf_slot_offsets(const float* ell, int32_t n_items, const int32_t* R, int64_t n_users, int32_t n_samples, float* off,
+                                void* stream) {
+    TMF_REQUIRE(n_items >= 0 && n_users >= 0 && n_samples >= 0, "slot_offsets: n_items=%d n_users=%lld n_samples=%d", n_items,
+                (long long)n_users, n_samples);
+    const int64_t total = n_users * (int64_t)n_samples;
+    if (total == 0) return TMF_OK;
+    TMF_REQUIRE(ell != nullptr && n_items > 0, "slot_offsets: samples without a table of offsets (n_items=%d)", n_items);
+    TMF_REQUIRE(R && off, "slot_offsets: null R / off for %lld samples", (long long)total);
+    TMF_REQUIRE(so_aligned(ell, 4) && so_aligned(R, 4) && so_aligned(off, 4), "slot_offsets: a pointer is not 4-byte aligned");
+    const bool vec = total >= 4 && so_aligned(R, 16) && so_aligned(off, 16);
+    const int64_t work = vec ? total / 4 : total;
+    const int64_t want = (work + kSoThreads - 1) / kSoThreads;
+    const unsigned blocks = (unsigned)(want < (int64_t)kSoBlocks ? want : kSoBlocks);
+    if (vec) {
+        hipLaunchKernelGGL(k_slot_offsets<true>, dim3(blocks), dim3(kSoThreads), 0, (hipStream_t)stream, ell, R, off, total);
+    } else {
+        hipLaunchKernelGGL(k_slot_offsets<false>, dim3(blocks), dim3(kSoThreads), 0, (hipStream_t)stream, ell, R, off, total);
+    }
+    return check_launch("tmf_slot_offsets");
 }

@@ -15,6 +15,7 @@ through the ``_l2`` twins of the table steps (``_engine.TrainState.set_l2``), in
 ``fit_als`` (an extension) trains the same tables by alternating least squares instead of gradient steps, and ``fold_in_users`` /
 ``fold_in_items`` embed rows that arrived after a fit from their interactions (``teamoflow_amd/_als.py``, ``csrc/tmf_als.hip``).
 """
+import copy
 import os
 import timeit
 import warnings
@@ -27,7 +28,7 @@ from .embedding_graphs import BiasedLinearEmbedding, Embeddings, LinearEmbedding
 from .initializer_graphs import NormalInitializer
 from .loss_graphs import LossGraph, MSELoss  # noqa: F401  (what the engine knows of every other loss is _engine.LOSSES)
 from .sparse import IndicatorFeatures, SparseFeatures, SparseInteractions, default_device, is_indicator
-from .utils import gather_matrix_indices, popularity_weights, random_sampler, random_sampler_device
+from .utils import gather_matrix_indices, log_expected_count, popularity_weights, random_sampler, random_sampler_device
 
 PREDICT_CHUNK_BYTES = 2 << 30  # users are scored in blocks of at most this many bytes of scores
 HOST_SAMPLER_MAX_WORK = 2_000_000_000  # n_users * n_items above which generate_sample=True samples on the device
@@ -73,7 +74,8 @@ _BUILT = {'pair': 'only the single-GPU full-batch fit is built for this loss',
           'resample': 'the negative table is resampled in the single-GPU full-batch fit and the generic loop only',
           'als': 'only the single-GPU full-batch fit is built, and its regulariser is reg',
           'item_bias': 'the scalar item bias is built for the single-GPU full-batch fit on float32 tables and the generic loop only',
-          'popularity': 'the negative table is drawn by popularity in the single-GPU full-batch fit and the generic loop only'}
+          'popularity': 'the negative table is drawn by popularity in the single-GPU full-batch fit and the generic loop only',
+          'logq': 'the logQ correction is built for the single-GPU full-batch fit and the generic loop only'}
 #                                                                                      how a refusal ends, per feature
 # scalar_item_bias = True, a table of its own beside ROUTES (DESIGN.md prints both; _route reads both): the settings the bias is
 # refused with whatever the trainer, and the families of _engine.LOSSES whose engine epoch has the two bias passes.  A loss that is
@@ -84,6 +86,11 @@ ITEM_BIAS_FAMILIES = {'table': 'ok', 'list': 'refuse', 'catalog': 'refuse'}
 # are where 'resample' is refused, and so is this.  With 'uniform' or without the attribute it is never looked at
 SAMPLING_ROUTES = {'popularity': dict(ROUTES['resample'])}
 NEGATIVE_SAMPLING = ('uniform', 'popularity')
+# sampling_correction = 'logq' on SampledSoftmaxLoss (and its subclasses), a table of its own like the two above and refused exactly
+# where 'popularity' is: the forms that draw their tables themselves know neither the weights nor the offsets.  With 'none' or without
+# the attribute, or on a loss that reads no negative table, it is never looked at
+CORRECTION_ROUTES = {'logq': dict(SAMPLING_ROUTES['popularity'])}
+SAMPLING_CORRECTION = ('none', 'logq')
 
 
 def augmented_tables(user_embedding, item_embedding, item_bias):
@@ -202,6 +209,15 @@ class MatrixFactorization:
         # Full-batch on one GPU, or the generic loop (SAMPLING_ROUTES); losses that read no table are not affected
         self.negative_sampling = 'uniform'
         self.sampling_power = 0.75
+        # extension, OFF by default: 'logq' = a SampledSoftmaxLoss fit subtracts from every sampled logit the log of how often the
+        # sampler proposes that item, l_i = utils.log_expected_count(q, S)[i] - loss_k = logaddexp(p_k, logsumexp_s(sp[u, s] -
+        # l[R[u, s]])) - p_k, the positive keeps its raw score - so that the sum over the samples estimates the full-catalog
+        # partition again whatever the proposal (the sampled-softmax / logQ correction of retrieval models).  Under 'uniform' l is the
+        # constant log(S / n_items) and the fit IS SampledSoftmaxLoss(catalog_scale=True), bit for bit; under 'popularity' l comes
+        # from the fit's weights, once per fit, and stays in sample_log_q_.  Only the training loss sees it: predict and the ranking
+        # calls do not.  The other table losses refuse it (CORRECTION_ROUTES; losses that read no table are not affected)
+        self.sampling_correction = 'none'
+        self.sample_log_q_ = None     # l of the last fit: float32 [n_items] on the CPU (None: the fit built no table of offsets)
         # extension, OFF by default (the reference's score is U[u] . V[i]): True = one trainable scalar per item beside its factor
         # (LightFM's item_biases), score U[u] . V[i] + item_bias_[i] in the loss and in every ranking call.  Starts from zeros at
         # every fit, takes the optimiser's step like any other variable and is never penalised.  On the engine for the table family
@@ -233,7 +249,7 @@ class MatrixFactorization:
 
     def _route(self, user_features, item_features):
         """'engine' | 'generic': the trainer of this fit, after the refusals (NotImplementedError; ValueError for a bad user_alpha /
-        item_alpha / resample_every / sample_seed / negative_sampling / sampling_power) - the one place that decides either, from
+        item_alpha / resample_every / sample_seed / negative_sampling / sampling_power / sampling_correction) - the one place that decides either, from
         ROUTES.  Nothing is drawn or built here.
         The engine takes exactly the ENGINE_LOSSES over sides that are exactly LinearEmbedding / BiasedLinearEmbedding over indicator
         features or LinearEmbedding over SparseFeatures with entries (with relu_engine also exactly ReLUEmbedding over either, while
@@ -250,6 +266,16 @@ class MatrixFactorization:
                                           f'engine losses form their scores inside the kernels (set scalar_item_bias back to its default)')
         if self._sampling_setting()[0] == 'popularity':   # the setting's own refusals (SAMPLING_ROUTES); None for a loss without a table
             self._answer('popularity', "negative_sampling='popularity'", table=SAMPLING_ROUTES)
+        if self._correction_setting() == 'logq':   # the setting's own refusals (CORRECTION_ROUTES); 'none' for a loss without a table
+            softmax = _engine.LOSSES['softmax'].cls
+            if not isinstance(self.loss_graph, softmax):
+                raise NotImplementedError(f"sampling_correction='logq' with {loss.__name__}: the correction is built for "
+                                          f'{softmax.__name__} only - an importance-weighted hinge and a rank estimate under a '
+                                          f'proposal are different mathematics (set sampling_correction back to its default)')
+            if getattr(self.loss_graph, 'catalog_scale', False):
+                raise ValueError(f"sampling_correction='logq' with {loss.__name__}(catalog_scale=True): the correction contains that "
+                                 f'constant (under uniform sampling it is exactly it) - use one of the two')
+            self._answer('logq', "sampling_correction='logq'", table=CORRECTION_ROUTES)
         # the refusals, in the order a model that meets several has always met them
         answers = [self._answer('pair', loss.__name__)] if row == 'pair' else []
         if any(self._alphas()):
@@ -337,6 +363,23 @@ class MatrixFactorization:
             power = float(power)
         return (how if isinstance(self.loss_graph, TABLE_LOSSES) else None), power
 
+    def _correction_setting(self):
+        """sampling_correction, checked (ValueError: not one of SAMPLING_CORRECTION) - 'none' on a model that never had the attribute
+        and for a loss that reads no negative table.  What 'logq' is refused with: _route (CORRECTION_ROUTES)."""
+        how = getattr(self, 'sampling_correction', 'none')
+        if not isinstance(how, str) or how not in SAMPLING_CORRECTION:
+            raise ValueError(f"sampling_correction={how!r}: 'none' or 'logq'")
+        return how if isinstance(self.loss_graph, TABLE_LOSSES) else 'none'
+
+    def _sample_log_q(self):
+        """l of a fit under sampling_correction='logq' whose tables are drawn by popularity (float32 [n_items] on the CPU:
+        utils.log_expected_count of the fit's weights and the S of random_ind), else None - under 'uniform' the correction is the
+        constant c = n_items / n_samples and no table exists.  Once per fit, after _popularity_weights."""
+        q = getattr(self, '_sampling_weights', None)
+        if self._correction_setting() != 'logq' or q is None or self.random_ind is None:
+            return None
+        return log_expected_count(q, int(torch.as_tensor(self.random_ind).shape[1]))
+
     def _popularity_weights(self, interactions, n_items):
         """The weights of this fit's tables under negative_sampling='popularity' (int64 [n_items], on the CPU), else None: c_i = the
         stored entries of item i with a value > 0, q = utils.popularity_weights(c, sampling_power).  Once per fit."""
@@ -365,6 +408,7 @@ class MatrixFactorization:
         self._feature_weights = [None, None]   # padded engine weights of a side trained over SparseFeatures (embed_users / embed_items)
         self._relu_sides = [None, None]        # the _engine.ReLUSide of a ReLU side trained on the engine (embed_users / embed_items)
         self._sampling_weights = None          # the weights of a fit under negative_sampling='popularity' (fit sets them)
+        self.sample_log_q_ = None              # the offsets of a fit under sampling_correction='logq' on such tables (likewise)
 
     def fit(self, epochs, user_features, item_features, tf_interactions, lr=1e-2):
         """matrix_factorization.py:96-187.  Re-initialises the weights on every call, runs ``epochs``
@@ -386,6 +430,7 @@ class MatrixFactorization:
         interactions = _as_interactions(tf_interactions)
         self._reset_fit_products((isinstance(user_features, SparseFeatures), isinstance(item_features, SparseFeatures)))
         self._sampling_weights = self._popularity_weights(interactions, n_items)
+        self.sample_log_q_ = self._sample_log_q()
         if route == 'engine':
             feats = [f if sparse else None for f, sparse in zip((user_features, item_features), self._sparse_feature_sides)]
             if self._fit_sparse(epochs, n_users, n_items, interactions, lr, U, V, *feats):
@@ -547,6 +592,8 @@ class MatrixFactorization:
                 R = self._draw_round(0, n_items, n_users, dev)
             wplan = _engine.wmrb_plan_for(plan, R, self.n_components, self.factor_dtype, force_sliced=rec.sliced_only or biased)
             rec.prepare(wplan, plan)   # before any epoch runs or is captured
+            if getattr(self, 'sample_log_q_', None) is not None:   # the logQ offsets of this table: likewise, and noted on the plan
+                wplan.slot_offsets(self.sample_log_q_.to(dev))
         r = self.n_components
         # a biased side starts from the bias an earlier fit left on the model, as in the reference (:139-146), else from zeros
         bias0 = [None if type(graph) is not BiasedLinearEmbedding else torch.zeros(r) if kept is None else kept
@@ -570,6 +617,8 @@ class MatrixFactorization:
         alphas = self._alphas()
         if any(alphas):   # never called with zeros: an unpenalised fit is today's state, launch for launch
             st.set_l2(*alphas)
+        if self._correction_setting() == 'logq' and wplan is not None and wplan.off is None:
+            return st, _engine.catalog_ratio(self)   # uniform tables: l is the constant log(S / n_items) - catalog_scale's c, its kernel
         return st, rec.param(self)
 
     def _sparse_step(self, st, loss, c, lr):
@@ -703,6 +752,13 @@ class MatrixFactorization:
             random_ind = self._draw_round(0, item_features.shape[0], user_features.shape[0], dev)
         # scalar_item_bias: one more leaf, from zeros, stepped with the other variables and never penalised
         bias = torch.zeros(item_features.shape[0], dtype=torch.float32, device=dev, requires_grad=True) if self._item_bias_setting() else None
+        # sampling_correction='logq' (SampledSoftmaxLoss and its subclasses; _route refused the rest): l[R] off the sampled scores of
+        # the round's table; under uniform tables l is the constant log(S / n_items), which is the loss's own catalog_scale
+        loss_graph, ell = self.loss_graph, getattr(self, 'sample_log_q_', None)
+        ell = None if ell is None else ell.to(dev)
+        if self._correction_setting() == 'logq' and ell is None:
+            loss_graph = copy.copy(loss_graph)
+            loss_graph.catalog_scale = True
         for epoch in range(epochs):
             start = timeit.default_timer()
             if every and epoch and epoch % every == 0 and random_ind is not None:   # round epoch // every: its own table, random_ind stays
@@ -726,12 +782,14 @@ class MatrixFactorization:
                 if random_ind is None:
                     raise SampleTableMissing(f'{type(self.loss_graph).__name__} needs generate_sample=True (random_ind is None)')
                 tf_sample_predictions = torch.gather(predictions, 1, random_ind.to(torch.int64))
+                if ell is not None:
+                    tf_sample_predictions = tf_sample_predictions - ell[random_ind.to(torch.int64)]
             if feeds != 'dense':
                 tf_prediction_serial = predictions[idx[:, 0], idx[:, 1]]
                 predictions = None
-            loss_fn = self.loss_graph.get_loss(tf_interactions=interactions, tf_sample_predictions=tf_sample_predictions,
-                                               tf_prediction_serial=tf_prediction_serial, predictions=predictions,
-                                               n_items=self.n_items, n_samples=self.n_samples)
+            loss_fn = loss_graph.get_loss(tf_interactions=interactions, tf_sample_predictions=tf_sample_predictions,
+                                          tf_prediction_serial=tf_prediction_serial, predictions=predictions,
+                                          n_items=self.n_items, n_samples=self.n_samples)
             variables = self.user_trainable + self.item_trainable + ([] if bias is None else [bias])
             objective = loss_fn.sum()
             for penalty, graph, trainable in ((user_alpha, self.user_repr_graph, self.user_trainable),
@@ -1197,6 +1255,8 @@ def _save_to_disk(model, path, include_samples=True, allow_pickle=False):
     sampling = (getattr(model, 'negative_sampling', 'uniform'), getattr(model, 'sampling_power', 0.75))
     if sampling != ('uniform', 0.75):   # only then, as below
         blob['negative_sampling'], blob['sampling_power'] = str(sampling[0]), float(sampling[1])
+    if getattr(model, 'sampling_correction', 'none') != 'none':   # only then, likewise
+        blob['sampling_correction'] = str(model.sampling_correction)
     if model._item_bias_setting():   # only then: a model without the setting writes the file it always wrote
         bias = getattr(model, 'item_bias_', None)
         blob['scalar_item_bias'] = True
@@ -1228,6 +1288,7 @@ def _load_from_disk(cls, path, device=None, allow_pickle=False):
     model.user_trainable = [model.user_embedding] if model.user_embedding is not None else None
     model.item_trainable = [model.item_embedding] if model.item_embedding is not None else None
     model.negative_sampling, model.sampling_power = blob.get('negative_sampling', 'uniform'), float(blob.get('sampling_power', 0.75))
+    model.sampling_correction = blob.get('sampling_correction', 'none')
     model.scalar_item_bias = bool(blob.get('scalar_item_bias', False))
     bias = blob.get('item_bias')
     model.item_bias_ = None if bias is None else bias.to(device=dev, dtype=torch.float32)

@@ -86,6 +86,27 @@ def popularity_weights(item_counts, power):
     return torch.from_numpy(q.astype(np.int64))
 
 
+def log_expected_count(q, n_samples):
+    """float32 [n_items] on the CPU: l_i = log(min(1, S q_i / T)), T = sum(q) - what sampling_correction='logq' subtracts from the
+    sampled logit of item i under a table of S = n_samples columns drawn with the weights q (any non-negative numbers, not all zero;
+    ``popularity_weights`` makes the ones a fit uses).  S q_i / T is the WITH-REPLACEMENT expected count of item i among the S draws
+    of a row, clamped at the one appearance a row of distinct items can hold.  It is not the exact inclusion probability of the
+    rejection sampler, which redraws repeated items and so proposes light items a little more often than this says.  0.0 where
+    q_i = 0: that item is never drawn, so the value is never read.  Computed ON THE HOST in float64 whatever device q is on, like
+    popularity_weights, and rounded to float32 once: a CPU fit and a GPU fit subtract the same numbers.  Equal weights give the one
+    value float32(log(S / n_items)) (0.0 once S >= n_items)."""
+    S = int(n_samples)
+    w = torch.as_tensor(q).detach().cpu().numpy().astype(np.float64).reshape(-1)
+    if S < 1:
+        raise ValueError(f'n_samples={n_samples!r}: at least one sample')
+    if w.size == 0 or not np.all(np.isfinite(w)) or w.min() < 0 or not w.sum() > 0:
+        raise ValueError('q must be a non-empty vector of finite weights >= 0 with a positive total')
+    count = np.minimum(1.0, S * w / w.sum())
+    ell = np.zeros_like(count)
+    np.log(count, out=ell, where=count > 0)
+    return torch.from_numpy(ell.astype(np.float32))
+
+
 def weighted_cum(weights, n_items, n_samples):
     """The checked prefix sums of a weighted table: int64 [n_items] on the CPU, cum[i] = q_0 + ... + q_i.  weights: int64 [n_items],
     q_i >= 0, total T = sum(q) with 1 <= T < 2^33 (TypeError / ValueError otherwise).  The admission rule, in integers: with H the sum
